@@ -137,7 +137,7 @@ def test_bench_eight_rank_rehearsal_of_both_workloads_with_the_slice_fan_out():
     """the driver's N = 8 launch, rehearsed over gloo: `bench.py --gpus 8` carries the weak-scaling headline AND the
     configs[4] line (segment images broadcast, ONE batch sharded over 8 ranks) in `secondary`; the images travel by the
     slice fan-out (scatter of slices from rank 0 + all-gather among the ranks)"""
-    rc, out, err = _run_bench(["--gpus", "8"], {"FMX_FAN_OUT_BROADCAST": "1"}, timeout=900)
+    rc, out, err = _run_bench(["--gpus", "8", "--full"], {"FMX_FAN_OUT_BROADCAST": "1"}, timeout=900)
     assert rc == 0, err[-2000:]
     assert out["dry_run"] and out["n_gpus"] == 8 and sorted(r[0] for r in out["ranks_seen"]) == list(range(8))
     seg = out["secondary"][0]

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_two_ranks_on_one_gpu_run_the_whole_multi_gpu_path():
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-one-gpu", "--steps", "4", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-one-gpu", "--full", "--steps", "4", "--warmup", "1",
            "--cpu-budget", "0.5", "--text-log2", "24", "--segment-log2", "22", "--patterns-total", "1048576",
            "--segments-check", "2000"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
@@ -43,7 +43,7 @@ def test_single_process_form_drives_three_replicas_through_the_c_abi():
     """`bench.py --gpus 3 --single-process`: ONE host process, fmx_replicate + fmx_count_batch_multi_dev (three replicas sharing the
     one GPU of the box), every pattern of batch 0 checked against the oracle, the contract line of the launcher form"""
     env = dict(os.environ)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--single-process", "--share-one-gpu", "--steps", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--single-process", "--share-one-gpu", "--full", "--steps", "4",
            "--warmup", "1", "--text-log2", "24", "--patterns", "300001", "--batches", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -9,5 +9,5 @@ for s in d.get("secondary") or []:
         rows.append((s["config"][15:40], s["ms"]))
 print(sys.argv[1], " | ".join("%s %.4f" % (k, v) for k, v in rows))'
 for l in "$@"; do
-FMX_LIBRARY=$PWD/$l python bench.py --cpu-budget 0.2 2>/dev/null | python tools/bench_detail.py | python -c "$show" "[$l]"
+FMX_LIBRARY=$PWD/$l python bench.py --full --cpu-budget 0.2 2>/dev/null | python tools/bench_detail.py | python -c "$show" "[$l]"
 done

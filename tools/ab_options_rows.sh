@@ -10,5 +10,5 @@ for s in d.get("secondary") or []:
         rows.append((s["config"][15:40], s["ms"]))
 print(sys.argv[1], " | ".join("%s %.4f" % (k, v) for k, v in rows))'
 for o in "$@"; do
-FMX_OPTIONS="$o" python bench.py --cpu-budget 0.2 2>/dev/null | python tools/bench_detail.py | python -c "$show" "[$o]"
+FMX_OPTIONS="$o" python bench.py --full --cpu-budget 0.2 2>/dev/null | python tools/bench_detail.py | python -c "$show" "[$o]"
 done

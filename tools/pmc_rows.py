@@ -84,7 +84,8 @@ def main():
         ctx.dist, ctx.shared = None, False
         ctx.t_start = __import__('time').time()
         seg = argparse.Namespace(segments=8, pattern_len=8, patterns_total=bench.SHARE_PATTERNS, segment_log2=args.text_log2,
-                                 sample_rate=32, steps=args.calls, warmup=0, gpus=1, no_cpu_baseline=True, segments_check=0)
+                                 sample_rate=32, steps=args.calls, warmup=0, gpus=1, no_cpu_baseline=True, segments_check=0, full=True,
+                                 dump_outputs=None)
         bench.run_segments(ctx, seg)
         # (run_segments: one step with LF-step outputs, `steps` timed steps, each stage once more for the stage times)
         print("PMC_ROW_CALLS %d QUERIES %d" % (args.calls + 2, bench.SHARE_PATTERNS))

@@ -2994,7 +2994,7 @@ int launch_extract_boundary(const DevIndex &ix, int n_cu, const int32_t *from, i
     const dim3 grid(scratch ? blocks_accel : grid_for(n, blk, n_cu));
     // the group kernel's redo list lives behind the windows; its count is cleared in front of every launch
     int32_t *redo = (scratch && G > 0) ? reinterpret_cast<int32_t *>(static_cast<uint8_t *>(workspace) + ((windows_bytes + 15) & ~(size_t)15)) : nullptr;
-    // The NARROW first round (option "boundary_narrow", default 1; the default group of 4, sample rates the marked replay serves,
+    // The NARROW first round (option "boundary_narrow", default 0: off, see g_boundary_narrow; the default group of 4, sample rates the marked replay serves,
     // batches of "boundary_narrow_min" queries or more): the walks are what this costs (one sector per LF-step, at the chip's
     // random-sector rate) and the wide form fetches 8 sample intervals per query where a line needs 3.1 — so every query first
     // gets the two intervals on each side of `from` (G = 2, a lane's two walks interleaved: HALF the LF-steps), and only a query

@@ -101,6 +101,16 @@ def main():
                 "boundary_narrow": rnd.choice([0, 0, 1]),  # extractUntilBoundary: a narrow first round + the wide form over the list
                 "boundary_narrow_min": rnd.choice([4096, 1, 1])}
         check_seed = rnd.randrange(1 << 30)
+        # launch shape and plan-stage order: from a generator of their own, so that `rnd` draws what it drew before they were
+        # added (a FAILED line recorded then still replays with --only-case)
+        shape = random.Random((args.seed << 32) | cases)
+        opts.update({"block": shape.choice([512, 1024]),
+                     "groups_per_cu": shape.choice([16, 1]),  # 1: the grid-stride loops run several passes
+                     "coarse_bits": shape.choice([12, 12, 4, 8, 13]),
+                     "sort_bits": shape.choice([28, 28, 1, 9, 32]),
+                     "plan_fine": shape.choice([1, 1, 0, 2]),
+                     "walk_pack": shape.choice([1, 1, 0, 2, 3]),
+                     "count_halve_uniform": shape.choice([1, 1, 0])})
         if args.only_case >= 0 and cases != args.only_case:
             if cases % 3 == 1:
                 rnd.random()  # (the draw of the device-construction check below)

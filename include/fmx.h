@@ -385,6 +385,43 @@ int fmx_rrr_rank_ones_batch_dev(const fmx_index *idx, const int32_t *d_positions
 int fmx_rrr_access_batch_dev(const fmx_index *idx, const int32_t *d_positions, int32_t n, uint8_t *d_bits, int32_t *d_status,
                              void *stream);
 
+/* ---- SuffixArray (the reference's public class suffixarray/SuffixArray.java, "SA") --------------------------------
+ * The plain suffix-array index: the text and its suffix array of n + 1 entries (entry 0 = n, the empty suffix; then the
+ * suffixes in the order of their chars as unsigned 16-bit values, a proper prefix first: SA:56-68, 89-91).
+ * fmx_sa_build: build_device >= 0 sorts the suffixes by prefix doubling in that device's HBM and leaves the array there
+ * (the handle is then resident on it); build_device = -1 sorts them on the host (SA-IS).  n <= 2^31 - 2.
+ * The handle answers the fmx_sa_* calls, fmx_to_device (the resident form: text, array and a fence table made from the
+ * options "sa_fences" / "sa_fence_chars"), fmx_free, fmx_input_length and fmx_device_of; every other call refuses it
+ * with FMX_E_ARG.  Queries need a resident handle (FMX_E_NO_DEVICE otherwise). */
+int fmx_sa_build(const uint16_t *text, int32_t n, int build_device, fmx_index **out);
+/* SA:186-199 (raw or ObjectOutputStream-framed): FMX_E_FORMAT unless len(sa) = text length + 1, every entry lies in
+ * [0, text length], the stream is complete and its text is well-formed UTF-8; FMX_E_VERSION for another version byte */
+int fmx_sa_load(const uint8_t *ser, size_t len, fmx_index **out);
+/* SA:172-184; *buf is owned by the library until fmx_free_buffer */
+int fmx_sa_save(const fmx_index *idx, int framed, uint8_t **buf, size_t *len);
+/* getSuffixArray (SA:164-166): copies min(cap, n + 1) entries; returns n + 1, or a negative FMX_E_* code */
+int64_t fmx_sa_get(const fmx_index *idx, int32_t *sa, int64_t cap);
+/* hashCode (SA:202-204): String.hashCode(text) + Arrays.hashCode(sa) in int32 arithmetic */
+int fmx_sa_hash_code(const fmx_index *idx, int32_t *hash);
+/* count (SA:100-104), batched: counts[i] = right - left of the reference's two searches (one fewer than the occurrences
+ * when the largest suffix starts with the pattern) */
+int fmx_sa_count_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t *counts);
+/* locate(p, offsets) (SA:116-129), batched with offsets.length = max_matches: found[i] = min(count, max_matches), and
+ * locs[i * max_matches + k] = the array's entry at row left + k for k < found[i] (slots from found[i] on keep their values);
+ * counts (nullable) as fmx_sa_count_batch.  n * max_matches < 2^31. */
+int fmx_sa_locate_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t max_matches,
+                        int32_t *locs, int32_t *found, int32_t *counts);
+/* the same with operands in HBM, asynchronous on `stream` */
+int fmx_sa_count_batch_dev(const fmx_index *idx, const uint16_t *d_pat, const int32_t *d_pat_off, int32_t n, int32_t *d_counts,
+                           void *stream);
+int fmx_sa_locate_batch_dev(const fmx_index *idx, const uint16_t *d_pat, const int32_t *d_pat_off, int32_t n,
+                            int32_t max_matches, int32_t *d_locs, int32_t *d_found, int32_t *d_counts, void *stream);
+
+/* BurrowsWheelerTransform.createBurrowsWheelerTransform (BWT:43-113): bwt = n + 1 chars, the transform of text + '\0' (that
+ * '\0' an ordinary symbol, tied with any '\0' of the text).  build_device as fmx_sa_build.  FMX_E_ALPHABET when text + '\0'
+ * has more than 32,767 distinct chars ("Charset has more than 32767 different characters."). */
+int fmx_bwt(const uint16_t *text, int32_t n, int build_device, uint16_t *bwt);
+
 /* ---- helpers ------------------------------------------------------------------------------ */
 
 /* FmIndex.convertBytePatternToCharPattern FM:239-298.  Returns the number of chars, or -1 with

@@ -18,7 +18,10 @@ from .fmindex import (  # noqa: F401
 from .replicas import ReplicaSet, SegmentReplicaSet, shard_range  # noqa: F401
 from .rrr import RrrVector  # noqa: F401
 from .segments import SegmentedFmIndex, cut_points  # noqa: F401
+from .suffixarray import SuffixArray  # noqa: F401
+from . import bwt  # noqa: F401
+from .bwt import computeRedundancyOfText, createBurrowsWheelerTransform  # noqa: F401
 from .wavelet import WaveletFixedBlockBoosting  # noqa: F401
 
-__all__ = ["ReplicaSet", "SegmentReplicaSet", "shard_range", "WaveletFixedBlockBoosting", "RrrVector", "SegmentedFmIndex", "cut_points", "FmIndex", "FmIndexBuilder", "FmxError", "as_chars", "chars_to_str", "pack_patterns",
+__all__ = ["SuffixArray", "bwt", "createBurrowsWheelerTransform", "computeRedundancyOfText", "ReplicaSet", "SegmentReplicaSet", "shard_range", "WaveletFixedBlockBoosting", "RrrVector", "SegmentedFmIndex", "cut_points", "FmIndex", "FmIndexBuilder", "FmxError", "as_chars", "chars_to_str", "pack_patterns",
            "raise_for_status", "synth_log", "synth_log_multichar", "synth_patterns", "lib", "LIB_PATH", "SYMBOLS"]

@@ -37,6 +37,8 @@ SYMBOLS = [
     "fmx_count_locate_segments_multi_dev", "fmx_multi_synchronize",
     "fmx_wavelet_build", "fmx_wavelet_rank_batch", "fmx_wavelet_inverse_select_batch",
     "fmx_rrr_build", "fmx_rrr_rank_ones_batch", "fmx_rrr_access_batch", "fmx_rrr_rank_ones_batch_dev", "fmx_rrr_access_batch_dev",
+    "fmx_sa_build", "fmx_sa_load", "fmx_sa_save", "fmx_sa_get", "fmx_sa_hash_code", "fmx_sa_count_batch", "fmx_sa_locate_batch",
+    "fmx_sa_count_batch_dev", "fmx_sa_locate_batch_dev", "fmx_bwt",
     "fmx_convert_byte_pattern", "fmx_status_message", "fmx_status_kind", "fmx_last_error", "fmx_release_scratch", "fmx_device_count", "fmx_set_option",
     "fmx_synth_log", "fmx_synth_log_multichar", "fmx_synth_patterns",
 ]
@@ -118,6 +120,17 @@ def _load():
     L.fmx_count_batch_is_planned.argtypes = [vp, i32]
     L.fmx_rrr_rank_ones_batch_dev.argtypes = [vp, vp, i32, vp, vp]
     L.fmx_rrr_access_batch_dev.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.fmx_sa_build.argtypes = [vp, i32, C.c_int, P(vp)]
+    L.fmx_sa_load.argtypes = [vp, sz, P(vp)]
+    L.fmx_sa_save.argtypes = [vp, C.c_int, P(vp), P(sz)]
+    L.fmx_sa_get.argtypes = [vp, vp, C.c_int64]
+    L.fmx_sa_get.restype = C.c_int64
+    L.fmx_sa_hash_code.argtypes = [vp, P(i32)]
+    L.fmx_sa_count_batch.argtypes = [vp, vp, vp, i32, vp]
+    L.fmx_sa_locate_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
+    L.fmx_sa_count_batch_dev.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.fmx_sa_locate_batch_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.fmx_bwt.argtypes = [vp, i32, C.c_int, vp]
     L.fmx_convert_byte_pattern.argtypes = [vp, i32, i32, vp, P(i32)]
     L.fmx_status_message.argtypes = [C.c_int]
     L.fmx_status_message.restype = C.c_char_p

@@ -6,6 +6,7 @@
 #include "fmx_build_stage.hpp"
 #include "fmx_model.hpp"
 #include "fmx_plan.hpp"
+#include "fmx_sa_index.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -111,6 +112,7 @@ struct fmx_index {
     bool owns_device = false;
     bool wavelet_only = false;  // built by fmx_wavelet_build: only the wavelet entry points apply
     bool rrr_only = false;      // built by fmx_rrr_build: only the RrrVector entry points apply
+    std::unique_ptr<fmx::SaIndex> sa;  // made by fmx_sa_build / fmx_sa_load: only the fmx_sa_* entry points apply
     double wavelet_device_seconds = 0;  // fmx_build_on_device: seconds of the wavelet encode in HBM (0: host encoder)
     void *d_suffix_table = nullptr;     // DevIndex.suffix_table (owned, whoever owns the image)
     void *d_suffix_order1 = nullptr;    // DevIndex.suffix_order1 (owned likewise)
@@ -295,6 +297,7 @@ int publish_dev_index(fmx_index *idx) {
 
 int require_device(const fmx_index *idx, bool rrr_handle = false) {
     if (!idx) return fail(FMX_E_ARG, "null index");
+    if (idx->sa) return fail(FMX_E_ARG, "a SuffixArray handle answers only fmx_sa_* calls");
     if (idx->rrr_only != rrr_handle)
         return fail(FMX_E_ARG, rrr_handle ? "not an RrrVector handle" : "an RrrVector handle answers only fmx_rrr_* calls");
     if (!idx->d_blob) return fail(FMX_E_NO_DEVICE, "index is not resident on a HIP device (call fmx_to_device)");
@@ -743,6 +746,13 @@ static int guarded(F &&body) {
 // fmx_multi.cpp: a shard's failure, reported by a worker thread, becomes the CALLING thread's fmx_last_error
 namespace fmx {
 int api_fail(int code, const std::string &msg) { return fail(code, msg); }
+// fmx_sa_api.cpp: a SuffixArray behind an fmx_index handle
+fmx_index *sa_handle(std::unique_ptr<SaIndex> sa) {
+    std::unique_ptr<fmx_index> idx(new fmx_index());
+    idx->sa = std::move(sa);
+    return idx.release();
+}
+SaIndex *sa_of(const fmx_index *idx) { return idx ? idx->sa.get() : nullptr; }
 }  // namespace fmx
 
 extern "C" {
@@ -875,6 +885,11 @@ int fmx_set_option(const char *name, int value) {
     if (!strcmp(name, "segments_overlap")) {
         g_segments_overlap = value != 0;
         return FMX_OK;
+    }
+    {  // options of the suffix-array kernels (which also follow "block" and "groups_per_cu")
+        const int rc = fmx::sa_set_option(name, value);
+        if (rc < 0) return fail(FMX_E_ARG, "bad value");
+        if (rc == 0) return FMX_OK;
     }
     {  // launch options go to both kernel sets
         const int a = fmx::set_option(name, value), b = fmxc::set_option(name, value);
@@ -1017,7 +1032,10 @@ void fmx_free(fmx_index *idx) {
     delete idx;
 }
 
-int32_t fmx_input_length(const fmx_index *idx) { return idx->has_model ? idx->model.length : idx->hdr.length; }
+int32_t fmx_input_length(const fmx_index *idx) {
+    if (idx->sa) return idx->sa->length();
+    return idx->has_model ? idx->model.length : idx->hdr.length;
+}
 int32_t fmx_alphabet_length(const fmx_index *idx) {
     return idx->has_model ? (int32_t)idx->model.map_keys.size() : idx->hdr.n_keys;
 }
@@ -1170,7 +1188,7 @@ static void build_window_cells(fmx_index *idx) {
 
 int fmx_window_cells_info(const fmx_index *idx, int64_t *bytes) {
     return guarded([&]() -> int {
-    if (!idx) return fail(FMX_E_ARG, "null index");
+    if (!idx || idx->sa) return fail(FMX_E_ARG, "not an FM-index handle");
     if (bytes) *bytes = (int64_t)idx->win_bytes;
     return FMX_OK;
     });
@@ -1178,7 +1196,7 @@ int fmx_window_cells_info(const fmx_index *idx, int64_t *bytes) {
 
 int fmx_resident_bytes(const fmx_index *idx, int64_t *image, int64_t *suffix_table, int64_t *window_directory) {
     return guarded([&]() -> int {
-    if (!idx) return fail(FMX_E_ARG, "null index");
+    if (!idx || idx->sa) return fail(FMX_E_ARG, "not an FM-index handle");
     const bool resident = idx->d_blob != nullptr;
     if (image) *image = resident ? (int64_t)idx->d_len : 0;
     if (suffix_table)
@@ -1190,7 +1208,10 @@ int fmx_resident_bytes(const fmx_index *idx, int64_t *image, int64_t *suffix_tab
     });
 }
 
-int fmx_device_of(const fmx_index *idx) { return (idx && idx->d_blob) ? idx->device : -1; }
+int fmx_device_of(const fmx_index *idx) {
+    if (idx && idx->sa) return idx->sa->device;
+    return (idx && idx->d_blob) ? idx->device : -1;
+}
 
 // The suffix table of a resident FM-index (fmx_device.hpp): grown level by level on the device — the strings of 2, 3, ... codes
 // that occur in the text, each with its SA interval — and ALL levels hashed into one table of 16-byte slots (a pattern shorter
@@ -1341,7 +1362,7 @@ static void build_suffix_table(fmx_index *idx) {
 
 int fmx_suffix_table_info(const fmx_index *idx, int32_t *chars, int64_t *bytes) {
     return guarded([&]() -> int {
-    if (!idx) return fail(FMX_E_ARG, "null index");
+    if (!idx || idx->sa) return fail(FMX_E_ARG, "not an FM-index handle");
     if (chars) *chars = idx->dev.suffix_table ? idx->dev.suffix_chars : 0;
     if (bytes) *bytes = (int64_t)idx->suffix_table_bytes;
     return FMX_OK;
@@ -1363,6 +1384,11 @@ int fmx_blob(const fmx_index *idx_c, const uint8_t **blob, size_t *len) {
 int fmx_to_device(fmx_index *idx, int device) {
     return guarded([&]() -> int {
     if (!idx) return fail(FMX_E_ARG, "null index");
+    if (idx->sa) {
+        std::string err;
+        const int rc = fmx::sa_to_device(*idx->sa, device, err);
+        return rc ? fail(rc, err) : FMX_OK;
+    }
     int rc = ensure_blob(idx);
     if (rc) return rc;
     int n = 0;
@@ -1437,7 +1463,7 @@ int fmx_attach_device_blob(void *device_blob, size_t len, int device, fmx_index 
 int fmx_replicate(const fmx_index *src_c, const int32_t *devices, int32_t n_devices, fmx_index **out) {
     return guarded([&]() -> int {
     fmx_index *src = const_cast<fmx_index *>(src_c);
-    if (!src || !devices || !out || n_devices < 1) return fail(FMX_E_ARG, "bad arguments");
+    if (!src || !devices || !out || n_devices < 1 || src->sa) return fail(FMX_E_ARG, "bad arguments");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(FMX_E_NO_DEVICE, "no HIP device visible");
     for (int32_t i = 0; i < n_devices; ++i)
@@ -1635,6 +1661,7 @@ int fmx_count_plan_dev(const fmx_index *idx, const uint16_t *d_pat, const int32_
 // kind 0 = count(): is the batch planned (fmx_count_batch_is_planned); 1 = locate(): are the hits walked by the first row of
 // their ranges (walk_order_min); 2 = extractUntilBoundary: are the queries taken by text position (boundary_order_min)
 int fmx_batch_policy(const fmx_index *idx, int kind, int64_t n) {
+    if (idx && idx->sa) return FMX_E_ARG;
     if (!idx || n <= 0 || n > INT32_MAX) return 0;
     if (kind == 0) return fmx_count_batch_is_planned(idx, (int32_t)n);
     if (kind == 1) return k_walk_workspace_bytes(idx, idx->dev, (int32_t)n) != 0 ? 1 : 0;
@@ -1643,6 +1670,7 @@ int fmx_batch_policy(const fmx_index *idx, int kind, int64_t n) {
 }
 
 int fmx_count_batch_is_planned(const fmx_index *idx, int32_t n) {
+    if (idx && idx->sa) return FMX_E_ARG;
     if (!idx || n <= 0) return 0;
     return (k_count_workspace_bytes(idx, idx->dev, n) != 0 && plan_pays(idx, n)) ? 1 : 0;
 }

@@ -45,6 +45,10 @@ int device_sa_stage(const int16_t *seq, int32_t n, int sample_rate, bool extract
 int device_alphabet_stage(const uint16_t *input, int32_t n_in, int device, std::vector<int32_t> &first,
                           std::vector<int64_t> &count, void **d_text, std::string &err) __attribute__((weak));
 void device_release(void *d_ptr) __attribute__((weak));  // hipFree of a buffer a device stage handed out
+// SuffixArray / BurrowsWheelerTransform: the prefix doubling of device_sa_stage alone over `seq` (L codes below `alphabet`, code 0
+// at L-1 only); *d_sa = the suffix array, left in HBM on `device` (L entries; free it with device_release)
+int device_suffix_array(const int16_t *seq, int32_t L, int alphabet, int device, uint32_t **d_sa, SaStageStats *stats,
+                        std::string &err) __attribute__((weak));
 int device_pack_values(const uint32_t *d_vals, int64_t n_vals, int64_t length, int width, int64_t wrap_index,
                        PackedVec &out, std::string &err) __attribute__((weak));
 int device_rrr_of_bits(const uint64_t *d_bits, int64_t nbits, int sample, RrrModel &m, std::string &err)

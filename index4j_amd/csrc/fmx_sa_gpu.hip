@@ -58,6 +58,11 @@ struct DevMem {
         *out = static_cast<T *>(p);
         return e;
     }
+    void *detach(void *p) {  // the caller takes the buffer over
+        for (void *&q : ptrs)
+            if (q == p) q = nullptr;
+        return p;
+    }
     void release(void *p) {  // ahead of the destructor
         for (void *&q : ptrs)
             if (q == p && p) {
@@ -217,6 +222,115 @@ int ceil_log2(uint64_t v) {
     return b;
 }
 
+// The buffers of the prefix doubling, for what a caller derives from the finished array (`sa`; the rest is scratch it
+// may reuse).  All of them belong to the DevMem the doubling was given.
+struct Doubling {
+    uint64_t *keys = nullptr, *keys_alt = nullptr;
+    uint32_t *sa = nullptr, *vals = nullptr, *vals_alt = nullptr, *rank = nullptr, *head = nullptr, *rows = nullptr;
+    uint8_t *tmp = nullptr;  // rocPRIM's temporary storage, tmp_bytes long
+    size_t tmp_bytes = 0;
+};
+
+// The suffix array of d_seq (L codes below `alphabet`, code 0 at L-1 only; uploaded from `seq` first unless that is null)
+// into out.sa by prefix doubling.  Adds the doubling rounds and the rows they sorted to `rounds` / `sorted_rows`.
+int sort_suffixes(DevMem &mem, const int16_t *seq, int16_t *d_seq, uint32_t L, int alphabet, Doubling &out, int &rounds,
+                  uint64_t &sorted_rows, std::string &err) {
+    uint64_t *d_keys = nullptr, *d_keys_alt = nullptr;
+    uint32_t *d_sa = nullptr, *d_vals = nullptr, *d_vals_alt = nullptr, *d_rank = nullptr, *d_head = nullptr,
+             *d_rows = nullptr, *d_rows_alt = nullptr, *d_count = nullptr;
+    uint8_t *d_active = nullptr;
+    SA_TRY(mem.alloc(&d_keys, (size_t)L));
+    SA_TRY(mem.alloc(&d_keys_alt, (size_t)L));
+    SA_TRY(mem.alloc(&d_sa, (size_t)L));
+    SA_TRY(mem.alloc(&d_vals, (size_t)L));
+    SA_TRY(mem.alloc(&d_vals_alt, (size_t)L));
+    SA_TRY(mem.alloc(&d_rank, (size_t)L));
+    SA_TRY(mem.alloc(&d_head, (size_t)L));
+    SA_TRY(mem.alloc(&d_rows, (size_t)L));
+    SA_TRY(mem.alloc(&d_rows_alt, (size_t)L));
+    SA_TRY(mem.alloc(&d_active, (size_t)L));
+    SA_TRY(mem.alloc(&d_count, 1));
+    if (seq) SA_TRY(hipMemcpy(d_seq, seq, (size_t)L * 2, hipMemcpyHostToDevice));
+
+    // one temporary buffer for all rocPRIM calls (sizes queried for the full length)
+    const int low_bits = ceil_log2((uint64_t)L + 1), high_bits = ceil_log2((uint64_t)L);
+    size_t tmp_sort = 0, tmp_scan = 0, tmp_select = 0;
+    SA_TRY(rocprim::radix_sort_pairs(nullptr, tmp_sort, d_keys, d_keys_alt, d_vals, d_vals_alt, (size_t)L, 0u, 64u));
+    SA_TRY(rocprim::inclusive_scan(nullptr, tmp_scan, d_head, d_head, (size_t)L, rocprim::maximum<uint32_t>()));
+    SA_TRY(rocprim::select(nullptr, tmp_select, rocprim::counting_iterator<uint32_t>(0), d_active, d_rows, d_count,
+                           (size_t)L));
+    size_t tmp_select_rows = 0;
+    SA_TRY(rocprim::select(nullptr, tmp_select_rows, d_rows, d_active, d_rows_alt, d_count, (size_t)L));
+    size_t tmp_bytes = tmp_sort > tmp_scan ? tmp_sort : tmp_scan;
+    if (tmp_select > tmp_bytes) tmp_bytes = tmp_select;
+    if (tmp_select_rows > tmp_bytes) tmp_bytes = tmp_select_rows;
+    uint8_t *d_tmp = nullptr;
+    SA_TRY(mem.alloc(&d_tmp, tmp_bytes));
+
+    // round 0
+    const int code_bits = alphabet > 0 ? (ceil_log2((uint64_t)alphabet) > 0 ? ceil_log2((uint64_t)alphabet) : 1) : 16;
+    const int first_chars = 64 / code_bits > 16 ? 16 : 64 / code_bits;
+    hipLaunchKernelGGL(k_sa_first_keys, dim3(grid_of(L)), dim3(kThreads), 0, 0, d_seq, L, first_chars, code_bits, d_keys, d_vals);
+    size_t bytes = tmp_bytes;
+    SA_TRY(rocprim::radix_sort_pairs(d_tmp, bytes, d_keys, d_keys_alt, d_vals, d_sa, (size_t)L, 0u,
+                                     (unsigned)(first_chars * code_bits)));
+    hipLaunchKernelGGL(k_sa_mark_heads, dim3(grid_of(L)), dim3(kThreads), 0, 0, d_keys_alt, (const uint32_t *)nullptr, L,
+                       d_head);
+    bytes = tmp_bytes;
+    SA_TRY(rocprim::inclusive_scan(d_tmp, bytes, d_head, d_head, (size_t)L, rocprim::maximum<uint32_t>()));
+    hipLaunchKernelGGL(k_sa_assign_ranks, dim3(grid_of(L)), dim3(kThreads), 0, 0, d_sa, (const uint32_t *)nullptr, d_head,
+                       L, d_rank, d_sa);
+
+    uint32_t n_prev = 0xffffffffu;  // tied rows of the previous round (none yet)
+    for (uint64_t h = (uint64_t)first_chars; h < (uint64_t)L * 2; h <<= 1) {
+        // rows still tied: among all rows after round 0, among the previous round's tied rows afterwards
+        if (n_prev == 0xffffffffu) {
+            hipLaunchKernelGGL(k_sa_mark_active, dim3(grid_of(L)), dim3(kThreads), 0, 0, d_sa, d_rank, L, d_active);
+            bytes = tmp_bytes;
+            SA_TRY(rocprim::select(d_tmp, bytes, rocprim::counting_iterator<uint32_t>(0), d_active, d_rows, d_count,
+                                   (size_t)L));
+        } else {
+            hipLaunchKernelGGL(k_sa_mark_active_rows, dim3(grid_of(n_prev)), dim3(kThreads), 0, 0, d_sa, d_rank, L, d_rows,
+                               n_prev, d_active);
+            bytes = tmp_bytes;
+            SA_TRY(rocprim::select(d_tmp, bytes, d_rows, d_active, d_rows_alt, d_count, (size_t)n_prev));
+            uint32_t *t = d_rows;
+            d_rows = d_rows_alt;
+            d_rows_alt = t;
+        }
+        uint32_t n_active = 0;
+        SA_TRY(hipMemcpy(&n_active, d_count, 4, hipMemcpyDeviceToHost));
+        n_prev = n_active;
+        if (n_active == 0) break;
+        ++rounds;
+        sorted_rows += n_active;
+        const uint32_t hh = (uint32_t)(h < L ? h : L);
+        hipLaunchKernelGGL(k_sa_next_keys, dim3(grid_of(n_active)), dim3(kThreads), 0, 0, d_sa, d_rows, d_rank, n_active, L,
+                           hh, low_bits, d_keys, d_vals);
+        bytes = tmp_bytes;
+        SA_TRY(rocprim::radix_sort_pairs(d_tmp, bytes, d_keys, d_keys_alt, d_vals, d_vals_alt, (size_t)n_active, 0u,
+                                         (unsigned)(low_bits + high_bits)));
+        hipLaunchKernelGGL(k_sa_mark_heads, dim3(grid_of(n_active)), dim3(kThreads), 0, 0, d_keys_alt, d_rows, n_active,
+                           d_head);
+        bytes = tmp_bytes;
+        SA_TRY(rocprim::inclusive_scan(d_tmp, bytes, d_head, d_head, (size_t)n_active, rocprim::maximum<uint32_t>()));
+        hipLaunchKernelGGL(k_sa_assign_ranks, dim3(grid_of(n_active)), dim3(kThreads), 0, 0, d_vals_alt, d_rows, d_head,
+                           n_active, d_rank, d_sa);
+    }
+    SA_TRY(hipGetLastError());
+    out.keys = d_keys;
+    out.keys_alt = d_keys_alt;
+    out.sa = d_sa;
+    out.vals = d_vals;
+    out.vals_alt = d_vals_alt;
+    out.rank = d_rank;
+    out.head = d_head;
+    out.rows = d_rows;
+    out.tmp = d_tmp;
+    out.tmp_bytes = tmp_bytes;
+    return 0;
+}
+
 }  // namespace
 
 void device_release(void *d_ptr) {
@@ -296,10 +410,6 @@ int device_sa_stage(const int16_t *seq, int32_t n, int sample_rate, bool extract
     const uint32_t L = (uint32_t)n;
     DevMem mem;
     int16_t *d_seq = nullptr;
-    uint64_t *d_keys = nullptr, *d_keys_alt = nullptr;
-    uint32_t *d_sa = nullptr, *d_vals = nullptr, *d_vals_alt = nullptr, *d_rank = nullptr, *d_head = nullptr,
-             *d_rows = nullptr, *d_rows_alt = nullptr, *d_count = nullptr;
-    uint8_t *d_active = nullptr;
     int16_t *d_codes = nullptr;
     if (d_text) {
         d_seq = static_cast<int16_t *>(d_text);  // mapped in place below
@@ -309,86 +419,17 @@ int device_sa_stage(const int16_t *seq, int32_t n, int sample_rate, bool extract
     } else {
         SA_TRY(mem.alloc(&d_seq, (size_t)L));
     }
-    SA_TRY(mem.alloc(&d_keys, (size_t)L));
-    SA_TRY(mem.alloc(&d_keys_alt, (size_t)L));
-    SA_TRY(mem.alloc(&d_sa, (size_t)L));
-    SA_TRY(mem.alloc(&d_vals, (size_t)L));
-    SA_TRY(mem.alloc(&d_vals_alt, (size_t)L));
-    SA_TRY(mem.alloc(&d_rank, (size_t)L));
-    SA_TRY(mem.alloc(&d_head, (size_t)L));
-    SA_TRY(mem.alloc(&d_rows, (size_t)L));
-    SA_TRY(mem.alloc(&d_rows_alt, (size_t)L));
-    SA_TRY(mem.alloc(&d_active, (size_t)L));
-    SA_TRY(mem.alloc(&d_count, 1));
-    if (!d_text) SA_TRY(hipMemcpy(d_seq, seq, (size_t)L * 2, hipMemcpyHostToDevice));
-
-    // one temporary buffer for all rocPRIM calls (sizes queried for the full length)
-    const int low_bits = ceil_log2((uint64_t)L + 1), high_bits = ceil_log2((uint64_t)L);
-    size_t tmp_sort = 0, tmp_scan = 0, tmp_select = 0;
-    SA_TRY(rocprim::radix_sort_pairs(nullptr, tmp_sort, d_keys, d_keys_alt, d_vals, d_vals_alt, (size_t)L, 0u, 64u));
-    SA_TRY(rocprim::inclusive_scan(nullptr, tmp_scan, d_head, d_head, (size_t)L, rocprim::maximum<uint32_t>()));
-    SA_TRY(rocprim::select(nullptr, tmp_select, rocprim::counting_iterator<uint32_t>(0), d_active, d_rows, d_count,
-                           (size_t)L));
-    size_t tmp_select_rows = 0;
-    SA_TRY(rocprim::select(nullptr, tmp_select_rows, d_rows, d_active, d_rows_alt, d_count, (size_t)L));
-    size_t tmp_bytes = tmp_sort > tmp_scan ? tmp_sort : tmp_scan;
-    if (tmp_select > tmp_bytes) tmp_bytes = tmp_select;
-    if (tmp_select_rows > tmp_bytes) tmp_bytes = tmp_select_rows;
-    uint8_t *d_tmp = nullptr;
-    SA_TRY(mem.alloc(&d_tmp, tmp_bytes));
-
-    // round 0
-    const int code_bits = alphabet > 0 ? (ceil_log2((uint64_t)alphabet) > 0 ? ceil_log2((uint64_t)alphabet) : 1) : 16;
-    const int first_chars = 64 / code_bits > 16 ? 16 : 64 / code_bits;
-    hipLaunchKernelGGL(k_sa_first_keys, dim3(grid_of(L)), dim3(kThreads), 0, 0, d_seq, L, first_chars, code_bits, d_keys, d_vals);
-    size_t bytes = tmp_bytes;
-    SA_TRY(rocprim::radix_sort_pairs(d_tmp, bytes, d_keys, d_keys_alt, d_vals, d_sa, (size_t)L, 0u,
-                                     (unsigned)(first_chars * code_bits)));
-    hipLaunchKernelGGL(k_sa_mark_heads, dim3(grid_of(L)), dim3(kThreads), 0, 0, d_keys_alt, (const uint32_t *)nullptr, L,
-                       d_head);
-    bytes = tmp_bytes;
-    SA_TRY(rocprim::inclusive_scan(d_tmp, bytes, d_head, d_head, (size_t)L, rocprim::maximum<uint32_t>()));
-    hipLaunchKernelGGL(k_sa_assign_ranks, dim3(grid_of(L)), dim3(kThreads), 0, 0, d_sa, (const uint32_t *)nullptr, d_head,
-                       L, d_rank, d_sa);
-
+    Doubling dbl;
     int rounds = 0;
     uint64_t sorted_rows = L;
-    uint32_t n_prev = 0xffffffffu;  // tied rows of the previous round (none yet)
-    for (uint64_t h = (uint64_t)first_chars; h < (uint64_t)L * 2; h <<= 1) {
-        // rows still tied: among all rows after round 0, among the previous round's tied rows afterwards
-        if (n_prev == 0xffffffffu) {
-            hipLaunchKernelGGL(k_sa_mark_active, dim3(grid_of(L)), dim3(kThreads), 0, 0, d_sa, d_rank, L, d_active);
-            bytes = tmp_bytes;
-            SA_TRY(rocprim::select(d_tmp, bytes, rocprim::counting_iterator<uint32_t>(0), d_active, d_rows, d_count,
-                                   (size_t)L));
-        } else {
-            hipLaunchKernelGGL(k_sa_mark_active_rows, dim3(grid_of(n_prev)), dim3(kThreads), 0, 0, d_sa, d_rank, L, d_rows,
-                               n_prev, d_active);
-            bytes = tmp_bytes;
-            SA_TRY(rocprim::select(d_tmp, bytes, d_rows, d_active, d_rows_alt, d_count, (size_t)n_prev));
-            uint32_t *t = d_rows;
-            d_rows = d_rows_alt;
-            d_rows_alt = t;
-        }
-        uint32_t n_active = 0;
-        SA_TRY(hipMemcpy(&n_active, d_count, 4, hipMemcpyDeviceToHost));
-        n_prev = n_active;
-        if (n_active == 0) break;
-        ++rounds;
-        sorted_rows += n_active;
-        const uint32_t hh = (uint32_t)(h < L ? h : L);
-        hipLaunchKernelGGL(k_sa_next_keys, dim3(grid_of(n_active)), dim3(kThreads), 0, 0, d_sa, d_rows, d_rank, n_active, L,
-                           hh, low_bits, d_keys, d_vals);
-        bytes = tmp_bytes;
-        SA_TRY(rocprim::radix_sort_pairs(d_tmp, bytes, d_keys, d_keys_alt, d_vals, d_vals_alt, (size_t)n_active, 0u,
-                                         (unsigned)(low_bits + high_bits)));
-        hipLaunchKernelGGL(k_sa_mark_heads, dim3(grid_of(n_active)), dim3(kThreads), 0, 0, d_keys_alt, d_rows, n_active,
-                           d_head);
-        bytes = tmp_bytes;
-        SA_TRY(rocprim::inclusive_scan(d_tmp, bytes, d_head, d_head, (size_t)n_active, rocprim::maximum<uint32_t>()));
-        hipLaunchKernelGGL(k_sa_assign_ranks, dim3(grid_of(n_active)), dim3(kThreads), 0, 0, d_vals_alt, d_rows, d_head,
-                           n_active, d_rank, d_sa);
-    }
+    int rc = sort_suffixes(mem, d_text ? nullptr : seq, d_seq, L, alphabet, dbl, rounds, sorted_rows, err);
+    if (rc) return rc;
+    uint64_t *d_keys = dbl.keys, *d_keys_alt = dbl.keys_alt;
+    uint32_t *d_sa = dbl.sa, *d_vals = dbl.vals, *d_vals_alt = dbl.vals_alt, *d_rank = dbl.rank, *d_head = dbl.head,
+             *d_rows = dbl.rows;
+    uint8_t *d_tmp = dbl.tmp;
+    const size_t tmp_bytes = dbl.tmp_bytes;
+    size_t bytes = tmp_bytes;
     SA_TRY(hipGetLastError());
 
     // FM:329-394 from the suffix array
@@ -472,6 +513,45 @@ int device_sa_stage(const int16_t *seq, int32_t n, int sample_rate, bool extract
         stats->rows_sorted = sorted_rows;
         stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
         stats->wavelet_seconds = out.wavelet_done ? wt_seconds : 0;
+    }
+    return 0;
+}
+
+// The suffix array alone (SuffixArray.construct, BurrowsWheelerTransform): the doubling above over `seq` (L codes below
+// `alphabet`, code 0 at L-1 only), and nothing derived from it.  The array stays in HBM: *d_sa (L entries) is the
+// caller's, freed with device_release.
+int device_suffix_array(const int16_t *seq, int32_t L, int alphabet, int device, uint32_t **d_sa, SaStageStats *stats,
+                        std::string &err) {
+    *d_sa = nullptr;
+    if (L <= 0 || !seq) {
+        err = "bad arguments";
+        return -1;
+    }
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        err = "no HIP device visible";
+        return -5;
+    }
+    if (device < 0 || device >= n_dev) {
+        err = "device ordinal out of range";
+        return -1;
+    }
+    SA_TRY(hipSetDevice(device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    DevMem mem;
+    int16_t *d_seq = nullptr;
+    SA_TRY(mem.alloc(&d_seq, (size_t)L));
+    Doubling dbl;
+    int rounds = 0;
+    uint64_t sorted_rows = (uint64_t)L;
+    const int rc = sort_suffixes(mem, seq, d_seq, (uint32_t)L, alphabet, dbl, rounds, sorted_rows, err);
+    if (rc) return rc;
+    SA_TRY(hipDeviceSynchronize());
+    *d_sa = static_cast<uint32_t *>(mem.detach(dbl.sa));
+    if (stats) {
+        stats->rounds = rounds;
+        stats->rows_sorted = sorted_rows;
+        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     }
     return 0;
 }

@@ -276,46 +276,53 @@ bool key_order_is_modelled(const FmModel &m) {
     return !tree;
 }
 
+// SER:89-100: the payload of a stream in ObjectOutputStream framing (false: `buf` is a raw stream)
+bool unframe_stream(const uint8_t *buf, size_t len, std::vector<uint8_t> &plain, bool &corrupt_tail) {
+    corrupt_tail = false;
+    if (!(len >= 4 && buf[0] == 0xAC && buf[1] == 0xED && buf[2] == 0x00 && buf[3] == 0x05)) return false;
+    plain.reserve(len);
+    // ObjectInputStream's block-data reader (java.io.ObjectInputStream.BlockDataInputStream.readBlockHeader / refill), which
+    // works LAZILY — a header is only looked at when FmIndex.read asks for bytes the earlier records did not hold:
+    // payloads of TC_BLOCKDATA 0x77 <u8 len> and TC_BLOCKDATALONG 0x7A <i32 len> records are one byte sequence (a
+    // primitive may straddle records; empty records are legal); TC_RESET 0x79 may stand between records; any other tag
+    // ends the block data (EOFException for a reader that wants more); a negative long length is a
+    // StreamCorruptedException for a reader that gets that far.  So: gather what is well-formed, parse, and let the
+    // parser's "truncated" become "malformed" when the payload ended at a corrupt header.
+    size_t pos = 4;
+    while (pos < len) {
+        size_t bl;
+        if (buf[pos] == 0x79) {
+            ++pos;
+            continue;
+        }
+        if (buf[pos] == 0x77) {
+            if (pos + 2 > len) break;
+            bl = buf[pos + 1];
+            pos += 2;
+        } else if (buf[pos] == 0x7A) {
+            if (pos + 5 > len) break;
+            if (buf[pos + 1] & 0x80) {
+                corrupt_tail = true;
+                break;
+            }
+            bl = ((size_t)buf[pos + 1] << 24) | ((size_t)buf[pos + 2] << 16) | ((size_t)buf[pos + 3] << 8) | buf[pos + 4];
+            pos += 5;
+        } else {
+            corrupt_tail = buf[pos] < 0x70 || buf[pos] > 0x7E;  // not a type code at all (TC_BASE .. TC_MAX)
+            break;
+        }
+        if (bl > len - pos) bl = len - pos;  // a record cut short by the end of the buffer holds what it holds
+        plain.insert(plain.end(), buf + pos, buf + pos + bl);
+        pos += bl;
+    }
+    return true;
+}
+
 // FM:983-1025.  Returns 0, or 1 truncated / 2 version / 3 malformed.
 int parse_model(const uint8_t *buf, size_t len, FmModel &m, std::string &err) {
     std::vector<uint8_t> plain;
     bool corrupt_tail = false;
-    if (len >= 4 && buf[0] == 0xAC && buf[1] == 0xED && buf[2] == 0x00 && buf[3] == 0x05) {  // SER:89-100
-        plain.reserve(len);
-        // ObjectInputStream's block-data reader (java.io.ObjectInputStream.BlockDataInputStream.readBlockHeader / refill), which
-        // works LAZILY — a header is only looked at when FmIndex.read asks for bytes the earlier records did not hold:
-        // payloads of TC_BLOCKDATA 0x77 <u8 len> and TC_BLOCKDATALONG 0x7A <i32 len> records are one byte sequence (a
-        // primitive may straddle records; empty records are legal); TC_RESET 0x79 may stand between records; any other tag
-        // ends the block data (EOFException for a reader that wants more); a negative long length is a
-        // StreamCorruptedException for a reader that gets that far.  So: gather what is well-formed, parse, and let the
-        // parser's "truncated" become "malformed" when the payload ended at a corrupt header.
-        size_t pos = 4;
-        while (pos < len) {
-            size_t bl;
-            if (buf[pos] == 0x79) {
-                ++pos;
-                continue;
-            }
-            if (buf[pos] == 0x77) {
-                if (pos + 2 > len) break;
-                bl = buf[pos + 1];
-                pos += 2;
-            } else if (buf[pos] == 0x7A) {
-                if (pos + 5 > len) break;
-                if (buf[pos + 1] & 0x80) {
-                    corrupt_tail = true;
-                    break;
-                }
-                bl = ((size_t)buf[pos + 1] << 24) | ((size_t)buf[pos + 2] << 16) | ((size_t)buf[pos + 3] << 8) | buf[pos + 4];
-                pos += 5;
-            } else {
-                corrupt_tail = buf[pos] < 0x70 || buf[pos] > 0x7E;  // not a type code at all (TC_BASE .. TC_MAX)
-                break;
-            }
-            if (bl > len - pos) bl = len - pos;  // a record cut short by the end of the buffer holds what it holds
-            plain.insert(plain.end(), buf + pos, buf + pos + bl);
-            pos += bl;
-        }
+    if (unframe_stream(buf, len, plain, corrupt_tail)) {
         buf = plain.data();
         len = plain.size();
     }
@@ -355,6 +362,29 @@ int parse_model(const uint8_t *buf, size_t len, FmModel &m, std::string &err) {
     return 0;
 }
 
+// SER:67-79: `raw` in ObjectOutputStream framing — magic, then block-data records of at most 1024 bytes
+void frame_stream(const std::vector<uint8_t> &raw, std::vector<uint8_t> &out) {
+    out.clear();
+    out.reserve(raw.size() + raw.size() / 200 + 16);
+    const uint8_t magic[4] = {0xAC, 0xED, 0x00, 0x05};
+    out.insert(out.end(), magic, magic + 4);
+    for (size_t pos = 0; pos < raw.size();) {
+        size_t bl = std::min<size_t>(1024, raw.size() - pos);
+        if (bl <= 255) {
+            out.push_back(0x77);
+            out.push_back((uint8_t)bl);
+        } else {
+            out.push_back(0x7A);
+            out.push_back((uint8_t)(bl >> 24));
+            out.push_back((uint8_t)(bl >> 16));
+            out.push_back((uint8_t)(bl >> 8));
+            out.push_back((uint8_t)bl);
+        }
+        out.insert(out.end(), raw.begin() + (long)pos, raw.begin() + (long)(pos + bl));
+        pos += bl;
+    }
+}
+
 // FM:948-975 (+ SER:67-79 framing)
 void emit_model(const FmModel &m, bool framed, std::vector<uint8_t> &out) {
     std::vector<uint8_t> raw;
@@ -382,25 +412,7 @@ void emit_model(const FmModel &m, bool framed, std::vector<uint8_t> &out) {
         out.swap(raw);
         return;
     }
-    out.clear();
-    out.reserve(raw.size() + raw.size() / 200 + 16);
-    const uint8_t magic[4] = {0xAC, 0xED, 0x00, 0x05};
-    out.insert(out.end(), magic, magic + 4);
-    for (size_t pos = 0; pos < raw.size();) {
-        size_t bl = std::min<size_t>(1024, raw.size() - pos);
-        if (bl <= 255) {
-            out.push_back(0x77);
-            out.push_back((uint8_t)bl);
-        } else {
-            out.push_back(0x7A);
-            out.push_back((uint8_t)(bl >> 24));
-            out.push_back((uint8_t)(bl >> 16));
-            out.push_back((uint8_t)(bl >> 8));
-            out.push_back((uint8_t)bl);
-        }
-        out.insert(out.end(), raw.begin() + (long)pos, raw.begin() + (long)(pos + bl));
-        pos += bl;
-    }
+    frame_stream(raw, out);
 }
 
 // structural checks on a parsed stream before it is flattened and any kernel may walk the image (a kernel fault can take

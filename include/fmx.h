@@ -102,6 +102,21 @@ int fmx_suffix_table_info(const fmx_index *idx, int32_t *chars, int64_t *bytes);
  * "window_cells_mb" (default 65,536) caps it in absolute terms beside the quarter-of-free-memory rule of "window_cells" = 2;
  * fmx_resident_bytes says what an index took.  *bytes = its size (0: none). */
 int fmx_window_cells_info(const fmx_index *idx, int64_t *bytes);
+/* The row table of a resident FM-index (option "locate_rows", read when an index becomes resident: 0, the default, never;
+ * 1 = for every index made resident afterwards whose text is shorter than 2^31 characters, where the table fits "window_cells_mb"
+ * and a quarter of the device's free memory — the directory's two rules; any other value: FMX_E_ARG).  One 32-bit word per BWT
+ * row beside the image (4 bytes per text character: the bytes of index4j's own sampleRate = 1 form, FM:343-344): WHAT locate()
+ * RETURNS for a hit at that row (FM:538-542), written once per residency by the walk locate() itself runs for that row, over the
+ * window directory where the index has one.  A pattern's hits are then end - start ADJACENT words: locate() — every entry point
+ * that locates: fmx_locate_batch{,_dev}, fmx_locate_extract_batch, fmx_locate_lines_batch, the segment sets, the *_multi forms —
+ * is the range search plus one gather, no LF-step.  Bit 31 of a word ("replay") marks the rows whose answer a word cannot carry
+ * (the walk raised a status, or took a number of LF-steps other than value % sampleRate — a walk derailed by quirk Q1 may): those
+ * hits are walked as without a table.  Positions, found counts, statuses and LF-step counts do not depend on having one.
+ * The fill costs wt_size x sampleRate / 2 LF-steps per residency; a table that does not fit, or whose fill fails, is simply not
+ * there (the index walks; not an error).  Never serialized.  RRR-only, wavelet-only and SuffixArray handles never get one.
+ * *bytes = its size as allocated (0: none), *replay_rows = rows marked "replay" (each pointer nullable).
+ * FMX_E_ARG for a null or SuffixArray handle. */
+int fmx_locate_rows_info(const fmx_index *idx, int64_t *bytes, int64_t *replay_rows);
 /* What a resident handle holds in its device's memory, in bytes (each pointer nullable): the image, the suffix table (with its
  * order-1 statistics), the window directory.  All 0 for a handle that is not resident.  (index4j's own figure for comparison is
  * the serialized size, FmIndexSerializedSizeBenchmark.java:57: 0.44-0.47 bytes per text byte.) */
@@ -449,7 +464,8 @@ int fmx_device_count(void);
  * Applied when an index is flattened or becomes resident afterwards: "suffix_table_mb" / "suffix_table_chars" (budget
  * and depth of the suffix table, 0 = none), "sb_cache_limit" (superblocks whose headers are staged in LDS), "map_by_symbol" / "map_fast" / "inv_fast"
  * (layout of the image: tests force the reference's own routes with them), "window_cells" (the window directory of
- * fmx_window_cells_info: 0 none, 1 always, 2 where it fits a quarter of the device's free memory).  Applied by
+ * fmx_window_cells_info: 0 none, 1 always, 2 where it fits a quarter of the device's free memory), "locate_rows" (the row table of
+ * fmx_locate_rows_info: 0 none — the default —, 1 where it fits; "rows_order" = 1: a locate over it keeps the walk-order stage in front; default 0, the caller's order: measured faster).  Applied by
  * fmx_build_on_device: "wavelet_on_device" = 0 encodes the wavelet tree on the host.
  * Results are identical for every setting. */
 /* Image form (fmx_set_option("image_compact", 0 | 1), applies to images flattened afterwards: fmx_to_device / fmx_blob of an index

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../fmx.h"
@@ -86,6 +87,13 @@ public:
 
     void toDevice(int device) { detail::check(fmx_to_device(h_, device), "fmx_to_device"); }
     fmx_index *handle() const { return h_; }
+    // {bytes, replay rows} of the resident index's row table (fmx_locate_rows_info; {0, 0}: none).  An index made resident after
+    // fmx_set_option("locate_rows", 1) keeps what locate() returns for every BWT row and gathers its hits instead of walking.
+    std::pair<int64_t, int64_t> locateRowsInfo() const {
+        int64_t bytes = 0, replay = 0;
+        detail::check(fmx_locate_rows_info(h_, &bytes, &replay), "fmx_locate_rows_info");
+        return {bytes, replay};
+    }
 
     // FmIndex.write(ObjectOutput) FM:948-975; framed = through Serialization.writeToByteArray SER:67-79
     std::vector<uint8_t> write(bool framed = true) const {

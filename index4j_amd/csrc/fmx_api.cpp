@@ -37,6 +37,7 @@
     int launch_win_build(const fmx::DevIndex &, int, uint32_t, fmx::Quad *, uint32_t *, hipStream_t);                   \
     int launch_win_other(const fmx::DevIndex &, int, uint32_t, fmx::Quad *, const uint32_t *, uint16_t *, uint32_t *, int, uint64_t *, uint32_t, hipStream_t); \
     int launch_win_flat(const fmx::DevIndex &, int, uint32_t, uint32_t *, uint32_t *, uint64_t *, uint32_t, hipStream_t);           \
+    int launch_rows_fill(const fmx::DevIndex &, int, uint32_t, uint32_t *, uint32_t *, hipStream_t);                    \
     int launch_count_plan(const fmx::DevIndex &, int, const uint16_t *, const int32_t *, int32_t, void *, size_t, bool, fmx::CountPlan *, \
                           hipStream_t);                                                                                 \
     int launch_count(const fmx::DevIndex &, int, const uint16_t *, const int32_t *, const fmx::CountPlan *, bool, int32_t, int32_t *, \
@@ -86,6 +87,7 @@ FMX_DISPATCH_FN(launch_suffix_order1)
 FMX_DISPATCH_FN(launch_win_build)
 FMX_DISPATCH_FN(launch_win_other)
 FMX_DISPATCH_FN(launch_win_flat)
+FMX_DISPATCH_FN(launch_rows_fill)
 FMX_DISPATCH_FN(launch_count_plan)
 FMX_DISPATCH_FN(launch_count)
 FMX_DISPATCH_FN(count_workspace_bytes)
@@ -121,6 +123,9 @@ struct fmx_index {
     void *d_win_other = nullptr;        // DevIndex.win_other: ... and the entries of the positions no class holds
     size_t win_bytes = 0;               // both together
     uint32_t win_unclean = 0;           // entries that carry a status or `suspect` (statistics)
+    void *d_rows = nullptr;             // DevIndex.rows: the row table (owned likewise; option locate_rows)
+    size_t rows_bytes = 0;              // ... as allocated
+    uint32_t rows_replay = 0;           // ... rows whose word says "walk this hit" (fmx::kRowReplay)
     size_t suffix_table_bytes = 0;
     uint32_t suffix_table_strings = 0;  // strings (of 2 .. suffix_chars codes) the table holds
     uint32_t suffix_table_deepest = 0;  // ... of which strings of suffix_chars codes: what a batch's patterns spread over after the lookup
@@ -171,6 +176,10 @@ std::atomic<int> g_suffix_table_image_fraction{8};  // option "suffix_table_imag
 // holds many indexes lowers it, or the quarter rule shrinks what is free geometrically)
 std::atomic<int> g_window_cells{2};
 std::atomic<int> g_window_cells_mb{65536};
+// option "locate_rows": indexes made resident afterwards grow a ROW TABLE (fmx_device.hpp DevIndex.rows: 4 bytes per text character
+// beside the image; locate() then gathers its hits instead of walking to them) — 0 (default) = never, 1 = where the text is shorter
+// than 2^31 characters and the table fits the directory's two rules: "window_cells_mb" and a quarter of the device's free memory
+std::atomic<int> g_locate_rows{0};
 // option "window_entry_bytes": the directory's entries — 0 = four bytes (the row; the symbol by a search over cumulativeCounts) where
 // those fit LDS (fmx::kWinSymbolSearchMax), six bytes otherwise; 4 / 6 = that form whatever the alphabet (tests, A/B)
 std::atomic<int> g_window_entry_bytes{0};
@@ -268,6 +277,7 @@ void make_dev_index(fmx_index *idx) {
     d.c_lds = nullptr;
     d.c_lut = nullptr;
     d.c_lut_shift = 0;
+    d.rows = nullptr;
     d.sb_cache = nullptr;
     d.sb_cache_limit = g_sb_cache_limit;
     d.wt_size = (uint32_t)h.wt_size;
@@ -290,6 +300,7 @@ int publish_dev_index(fmx_index *idx) {
     copy.win_flat = 0;
     copy.c_lds = nullptr;
     copy.c_lut = nullptr;
+    copy.rows = nullptr;
     HIP_TRY(hipMemcpy(idx->d_self, &copy, sizeof(copy), hipMemcpyHostToDevice));
     idx->dev.self = copy.self;
     return FMX_OK;
@@ -852,6 +863,11 @@ int fmx_set_option(const char *name, int value) {
         g_window_entry_bytes = value;
         return FMX_OK;
     }
+    if (name && !strcmp(name, "locate_rows")) {  // row table of indexes made resident from now on: 0 never, 1 where it fits
+        if (value != 0 && value != 1) return fail(FMX_E_ARG, "bad value");
+        g_locate_rows = value;
+        return FMX_OK;
+    }
     if (name && !strcmp(name, "window_cells_mb")) {  // absolute budget of one index's window directory under "window_cells" = 2
         if (value < 0) return fail(FMX_E_ARG, "bad value");
         g_window_cells_mb = value;
@@ -1010,9 +1026,11 @@ static void release_device_state(fmx_index *idx) {
     if (idx->d_self) (void)hipFree(idx->d_self);
     if (idx->d_win) (void)hipFree(idx->d_win);
     if (idx->d_win_other) (void)hipFree(idx->d_win_other);
-    idx->d_blob = idx->d_suffix_table = idx->d_suffix_order1 = idx->d_self = idx->d_win = idx->d_win_other = nullptr;
+    if (idx->d_rows) (void)hipFree(idx->d_rows);
+    idx->d_blob = idx->d_suffix_table = idx->d_suffix_order1 = idx->d_self = idx->d_win = idx->d_win_other = idx->d_rows = nullptr;
     idx->d_len = 0;
-    idx->win_bytes = idx->suffix_table_bytes = 0;
+    idx->win_bytes = idx->suffix_table_bytes = idx->rows_bytes = 0;
+    idx->rows_replay = 0;
     idx->owns_device = false;
     idx->dev = fmx::DevIndex();
     for (auto &kv : idx->side) {
@@ -1184,6 +1202,57 @@ static void build_window_cells(fmx_index *idx) {
         idx->dev.win_full = entry4 ? reinterpret_cast<const uint64_t *>(e8 + entry_bytes + 16) : nullptr;
         return;
     }
+}
+
+// The row table of a resident FM-index (fmx_device.hpp DevIndex.rows; option locate_rows): one word per BWT row, filled on the
+// device by the very walk locate() runs for a hit at that row (k_rows_fill) — over the window directory grown just before, or
+// the tree.  Never from the text or a suffix sort: the words are what the REFERENCE returns, quirks included, and an index
+// loaded from a stream has no text.  Not having one (the option is off, it does not fit, the fill fails) is never an error:
+// locate() then walks.
+static void build_locate_rows(fmx_index *idx) {
+    if (idx->d_rows) (void)hipFree(idx->d_rows);
+    idx->d_rows = nullptr;
+    idx->rows_bytes = 0;
+    idx->rows_replay = 0;
+    idx->dev.rows = nullptr;
+    if (g_locate_rows.load() != 1 || idx->rrr_only || idx->wavelet_only || idx->hdr.kind != 0 || idx->hdr.wt_size <= 0 ||
+        (uint64_t)idx->hdr.wt_size >= 0x80000000ull || !idx->dev.self)
+        return;
+    const size_t bytes = ((size_t)idx->hdr.wt_size * 4 + 63) & ~(size_t)63;
+    size_t free_b = 0, total_b = 0;
+    if (bytes > ((size_t)g_window_cells_mb.load() << 20) || hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4) {
+        (void)hipGetLastError();
+        return;
+    }
+    void *d_rows = nullptr;
+    uint32_t replay = 0;
+    if (hipMalloc(&d_rows, bytes + 64) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    uint8_t *r8 = static_cast<uint8_t *>(d_rows);  // (behind the table: the fill's count of replay rows)
+    if (hipMemset(r8 + bytes, 0, 64) != hipSuccess ||
+        k_launch_rows_fill(idx, idx->dev, idx->n_cu, (uint32_t)idx->hdr.wt_size, static_cast<uint32_t *>(d_rows),
+                           reinterpret_cast<uint32_t *>(r8 + bytes), nullptr) != 0 ||
+        hipMemcpy(&replay, r8 + bytes, sizeof replay, hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d_rows);
+        return;
+    }
+    idx->d_rows = d_rows;
+    idx->rows_bytes = bytes;
+    idx->rows_replay = replay;
+    idx->dev.rows = static_cast<const uint32_t *>(d_rows);
+}
+
+int fmx_locate_rows_info(const fmx_index *idx, int64_t *bytes, int64_t *replay_rows) {
+    return guarded([&]() -> int {
+    if (!idx || idx->sa) return fail(FMX_E_ARG, "not an FM-index handle");
+    const bool have = idx->d_blob != nullptr && idx->d_rows != nullptr;
+    if (bytes) *bytes = have ? (int64_t)idx->rows_bytes : 0;
+    if (replay_rows) *replay_rows = have ? (int64_t)idx->rows_replay : 0;
+    return FMX_OK;
+    });
 }
 
 int fmx_window_cells_info(const fmx_index *idx, int64_t *bytes) {
@@ -1414,6 +1483,7 @@ int fmx_to_device(fmx_index *idx, int device) {
     if (int rc2 = publish_dev_index(idx)) return rc2;
     build_window_cells(idx);
     build_suffix_table(idx);
+    build_locate_rows(idx);
     return FMX_OK;
     });
 }
@@ -1450,6 +1520,7 @@ int fmx_attach_device_blob(void *device_blob, size_t len, int device, fmx_index 
     if (int rc2 = publish_dev_index(idx.get())) return rc2;
     build_window_cells(idx.get());
     build_suffix_table(idx.get());
+    build_locate_rows(idx.get());
     *out = idx.release();
     return FMX_OK;
     });
@@ -1532,6 +1603,7 @@ int fmx_replicate(const fmx_index *src_c, const int32_t *devices, int32_t n_devi
         }
         build_window_cells(idx.get());
         build_suffix_table(idx.get());
+        build_locate_rows(idx.get());
         made[(size_t)i] = std::move(idx);
     };
     {

@@ -104,6 +104,10 @@ struct DevIndex {
     int32_t c_lut_shift;        // row >> c_lut_shift = the row's bucket
     // this index's DevIndex as the API layer keeps it in HBM (no LDS cache, no launch option applied): what a cold route reads
     const DevIndex *self;
+    // Row table (nullptr: none; option locate_rows, grown beside a resident image after the window directory — "fm_row_*" below):
+    // one 32-bit word per BWT row, WHAT locate() RETURNS for a hit at that row (FM:538-542) — a pattern's hits are end - start
+    // adjacent words, no LF-step — or kRowReplay where a word cannot carry the answer (that hit is walked, as without a table)
+    const uint32_t *rows;
 };
 // width of one alphabet code in a plan record's word and in a suffix-table key: 8 bits while the alphabet fits, 12 for alphabets
 // of up to 4,096 codes (five codes per 64-bit word, keys of five characters), else 16
@@ -1951,6 +1955,64 @@ FMX_HD int32_t fm_locate_finish_win(const DevIndex &ix, const uint16_t *inv, con
         if (r < 0) r = 0;
     }
     return fm_packed_get(ix.suffix_words, r, ix.bw_suffixes) + w.distance;  // FM:538-542
+}
+
+// THE ROW TABLE (DevIndex.rows).  Word r = what fm_locate_hit returns for the hit at BWT row r (the reference's answer, quirks
+// included: a walk that Q1 derails and that ends cleanly has a value like any other), bit 31 clear.  The LF-steps of that hit are
+// not stored: a walk that met no quirk took `value % sampleRate` of them (every sampleRate-th text position is sampled).  A row
+// whose walk ended in a status, or took another number of steps (a derailed walk may), or whose value does not fit 31 bits, gets
+// kRowReplay instead, and whoever reads it runs fm_locate_hit for that hit.
+constexpr uint32_t kRowReplay = 0x80000000u;
+// what k_rows_fill stores for row r: the walk k_locate_walk runs for a hit there (kWin: over the directory the index has, or the tree)
+template <int kWin = kWinAsk>
+FMX_HD uint32_t fm_row_word(const DevIndex &ix, const uint16_t *inv, uint32_t r) {
+    int status = ST_OK;
+    int32_t distance;
+    const int32_t at = fm_locate_hit<kWin>(ix, inv, (int32_t)r, 0, distance, status);  // (hit 0 of a range that starts at r: j = r + 1)
+    if (status != ST_OK || at < 0 || ix.sample_rate <= 0 || distance != at % ix.sample_rate) return kRowReplay;
+    return (uint32_t)at;
+}
+// FM:544-546 and the Java AIOOBE beyond `locations`: how many hits of [start, end) a call stores (`wanted`: how many it asks for).
+// limit = maxMatches less what earlier segments of a set took (<= 0 with taken: nothing left; <= 0 without: no limit)
+FMX_HD int32_t fm_locate_share(int32_t start, int32_t end, int32_t limit, bool limited, int32_t loc_cap, int32_t &wanted) {
+    int32_t hits = start < end ? end - start : 0;
+    if (limited && limit <= 0) hits = 0;
+    wanted = (limit > 0 && hits > limit) ? limit : hits;
+    return wanted < loc_cap ? wanted : loc_cap;
+}
+// One hit through the table: row start + k's word where the table has one, else (kRowReplay, or a row outside the table: a count
+// phase over a damaged image can hand back any range) the walk.  The table is never indexed with an unchecked row.
+template <int kWin = kWinAsk>
+FMX_HD int32_t fm_rows_hit(const DevIndex &ix, const uint16_t *inv, int32_t start, int32_t k, int32_t &distance, int &status) {
+    const int64_t row = (int64_t)start + k;
+    if (row >= 0 && row < (int64_t)ix.wt_size) {
+        const uint32_t w = ix.rows[row];
+        if (!(w & kRowReplay)) {
+            distance = (int32_t)(w % (uint32_t)ix.sample_rate);  // (fm_row_word: a clean word's walk took exactly these steps)
+            return (int32_t)w;
+        }
+    }
+    return fm_locate_hit<kWin>(ix, inv, start, k, distance, status);
+}
+// A lane's share of one pattern's hits (k_locate_rows): hits k0, k0 + step, ... below `located` into the pattern's row — `out`
+// (int32) or, for a segment set, `set_out` (int64 text positions moved by set_base).  Returns the LF-steps those hits stand for;
+// statuses are or-ed into `status`.  Adjacent lanes (k0, k0 + 1, ...) read adjacent words and write adjacent slots.
+template <int kWin = kWinAsk>
+FMX_HD int32_t fm_rows_gather(const DevIndex &ix, const uint16_t *inv, int32_t start, int32_t located, int32_t k0, int32_t step,
+                              int32_t *out, int64_t *set_out, int64_t set_base, int &status) {
+    int32_t steps = 0;
+    for (int32_t k = k0; k < located; k += step) {
+        int32_t distance = 0;
+        int st = ST_OK;  // (per hit: fm_locate_hit finishes a walk by the status it ended with)
+        const int32_t at = fm_rows_hit<kWin>(ix, inv, start, k, distance, st);
+        status |= st;
+        if (set_out)
+            set_out[k] = set_base + at;
+        else
+            out[k] = at;
+        steps += distance;
+    }
+    return steps;
 }
 
 // up to four characters of one aligned 8-byte group of a destination row (mask: which of them): one store when all four are there

@@ -2,6 +2,7 @@
 //
 //   k_count            FmIndex.count            FM:455-474   two lanes per pattern (start / end of the SA interval)
 //   k_locate_walk      FmIndex.locate           FM:526-548   one lane per (pattern, hit): LF-walk to a sampled row
+//   k_locate_rows      ... over a row table     FM:526-548   a group of lanes per pattern: the hits gathered, no LF-step (option locate_rows)
 //   k_extract          FmIndex.extract          FM:564-608   one lane per query
 //   k_extract_boundary extractUntilBoundary{,Left,Right} FM:640-922  one lane per query
 //
@@ -1169,6 +1170,84 @@ FMX_WALK_KERNEL(kBlock) void k_locate_walk(DevIndex ix_global, const int32_t *__
     }
 }
 
+// THE ROW TABLE (fmx_device.hpp DevIndex.rows; option locate_rows).
+// k_rows_fill: a lane per BWT row runs the walk k_locate_walk runs for a hit there — over the window directory where the index has
+// one (kWin), over the tree otherwise — and stores fm_row_word's answer.  *replay counts the rows that got kRowReplay.
+template <int kWin>
+FMX_WALK_KERNEL(256) void k_rows_fill(DevIndex ix_global, uint32_t n_rows, uint32_t *__restrict__ rows, uint32_t *__restrict__ replay) {
+    FMX_FM_INV(ix_global);
+    FMX_WITH_SB_CACHE(ix_global, ix);
+    uint32_t mine = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (uint64_t)gridDim.x * 256) {
+        const uint32_t w = fm_row_word<kWin>(ix, s_inv, (uint32_t)r);
+        rows[r] = w;
+        mine += w >> 31;
+    }
+    if (mine) atomicAdd(replay, mine);
+}
+// k_locate_rows: k_locate_walk's arguments and stores, the hits GATHERED from the row table: a pattern's hits are end - start
+// adjacent words.  A group of 2^lanes_log2 lanes per pattern (the launcher sizes it to the slot count: 16 lanes read <= 16 hits
+// as one sector and write one; a whole wave strides over the range where the slots are many), lane g takes hits g, g + lanes, ...
+// A word that says kRowReplay, or a row outside the table, is walked by its lane (fm_rows_hit).  The groups are aligned inside a
+// wave, so a group's lanes leave the loop together and the LF-step sum is folded over the group before ONE lane adds it.
+template <int kBlock>
+__global__ __launch_bounds__(kBlock) void k_locate_rows(DevIndex ix, const int32_t *__restrict__ range, int32_t n, int32_t max_matches,
+                                                        int32_t *__restrict__ locs, int32_t loc_cap, int32_t lanes_log2,
+                                                        int32_t *__restrict__ found, int32_t *__restrict__ lf_steps,
+                                                        int32_t *__restrict__ status_out, const int32_t *__restrict__ taken,
+                                                        const PlanRec *__restrict__ order, int64_t *__restrict__ set_locs,
+                                                        int64_t set_base) {
+    const int32_t lanes = 1 << lanes_log2;
+    const int64_t total = (int64_t)n << lanes_log2;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
+        const int64_t rec = t >> lanes_log2;
+        const int32_t g = (int32_t)(t & (lanes - 1));
+        int32_t p = (int32_t)rec;
+        int32_t start, end;
+        if (order) {  // (the batch's records {start, end, pattern} by the first row of their ranges: launch_locate_walk)
+            const Quad r = ld_quad(order + rec);
+            start = (int32_t)r.x;
+            end = (int32_t)r.y;
+            p = (int32_t)r.z;
+        } else {
+            start = range[2 * p];
+            end = range[2 * p + 1];
+        }
+        const int32_t before = taken ? taken[p] : 0;  // segment sets: hits that came from earlier segments
+        int32_t wanted;
+        const int32_t located = fm_locate_share(start, end, taken ? max_matches - before : max_matches, taken != nullptr, loc_cap, wanted);
+        if (g == 0) {
+            found[p] = located;
+            if (wanted > loc_cap && status_out) atomicOr(&status_out[p], ST_JAVA_AIOOBE);
+        }
+        int status = ST_OK;
+        // (the value-of-offset table of a compact image where it lies, not staged: only a replayed hit reads it)
+        int32_t steps = fm_rows_gather<kWinAsk>(ix, ix.inv_global, start, located, g, lanes, locs + (int64_t)p * loc_cap,
+                                                set_locs ? set_locs + (int64_t)p * loc_cap + before : nullptr, set_base, status);
+        if (lf_steps) {
+            for (int32_t o = lanes >> 1; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
+            if (g == 0 && steps) atomicAdd(&lf_steps[p], steps);
+        }
+        if (status && status_out) atomicOr(&status_out[p], status);
+    }
+}
+
+// the row table of a resident index (k_rows_fill): walked over the window directory the index has by now, or the tree
+int launch_rows_fill(const DevIndex &ix, int n_cu, uint32_t n_rows, uint32_t *rows, uint32_t *replay, hipStream_t st) {
+    if (n_rows == 0) return 0;
+    const dim3 grid(win_blocks(n_cu, n_rows));
+    DevIndex walk = ix;
+    walk.rows = nullptr;
+    if (ix.win && ix.win_flat)
+        hipLaunchKernelGGL(k_rows_fill<kWinFlat>, grid, dim3(256), 0, st, walk, n_rows, rows, replay);
+    else if (ix.win)
+        hipLaunchKernelGGL(k_rows_fill<kWinAlways>, grid, dim3(256), 0, st, walk, n_rows, rows, replay);
+    else
+        hipLaunchKernelGGL(k_rows_fill<kWinNever>, grid, dim3(256), 0, st, walk, n_rows, rows, replay);
+    return (int)hipGetLastError();
+}
+
 // k_locate_walk over an index with a window directory, with the walks still under way PACKED into fewer waves twice on their
 // way (after sample_rate / 2 and sample_rate * 3 / 4 steps).  The kernel is bound by VALU issue, and a wave walks until the longest
 // of its 64 walks meets a sampled row — sample_rate - 1 steps where the average walk takes half of that: half of the wave-steps ran
@@ -2305,6 +2384,11 @@ static std::atomic<int> g_walk_order_min{32768};
 static std::atomic<int> g_boundary_order_min{32768};
 static std::atomic<int> g_walk_fine{1};  // the window-local fine order on top of the buckets (k_plan_fine; 0: A/B)
 static std::atomic<int> g_sort_bits{28};    // full key width: floor(sort_bits / bits-per-code) trailing characters
+// option "rows_order": 1 = locate over a row table (k_locate_rows) still takes large batches by the first row of their ranges (the
+// walk-order stage in front, as the walks do); 0 (default, by measurement: profiles/r08_locate_rows.json) = in the caller's order —
+// a gather reads one or two sectors per pattern whatever the order, and the three short kernels in front cost more than the
+// locality they buy: configs[2] 0.062 -> 0.044 ms, series locate(1) 0.85 -> 0.77, locate(100) 0.47 -> 0.45
+static std::atomic<int> g_rows_order{0};
 
 int set_option(const char *name, int value) {
     if (!strcmp(name, "block")) {
@@ -2434,6 +2518,11 @@ int set_option(const char *name, int value) {
     if (!strcmp(name, "walk_order_min")) {
         if (value < 0) return -1;
         g_walk_order_min = value;
+        return 0;
+    }
+    if (!strcmp(name, "rows_order")) {
+        if (value != 0 && value != 1) return -1;
+        g_rows_order = value;
         return 0;
     }
     if (!strcmp(name, "sort_bits")) {
@@ -2767,7 +2856,8 @@ int launch_locate_walk(const DevIndex &ix, int n_cu, const int32_t *range, int32
     if (slots < 1) slots = 1;
     const PlanRec *order = nullptr;
     const uint32_t *order_idle = nullptr;
-    const size_t need = walk_workspace_bytes(ix, n);
+    // (a row table: the hits are gathered, not walked — in the caller's order unless option "rows_order" asks for the walk order)
+    const size_t need = (ix.rows && !g_rows_order.load()) ? 0 : walk_workspace_bytes(ix, n);
     if (workspace && need != 0 && workspace_bytes >= need && loc_cap > 0) {
         uint8_t *wsb = static_cast<uint8_t *>(workspace);
         uint32_t *ghist = reinterpret_cast<uint32_t *>(wsb);
@@ -2793,6 +2883,13 @@ int launch_locate_walk(const DevIndex &ix, int n_cu, const int32_t *range, int32
             hipLaunchKernelGGL(k_plan_fine, dim3((n + kFineWindow - 1) / kFineWindow), dim3(kFineThreads), 0, st, ordered, n);
         order = ordered;
         order_idle = ticket + 1;
+    }
+    if (ix.rows) {  // a row table: k_locate_rows, a group of lanes per pattern sized to the slot count (a wave at most)
+        int lanes_log2 = 0;
+        while (lanes_log2 < 6 && (1 << lanes_log2) < slots) ++lanes_log2;
+        FMX_DISPATCH(k_locate_rows, (int64_t)n << lanes_log2, ix, range, n, max_matches, locs, loc_cap, lanes_log2, found, lf, status, taken,
+                     order, set_locs, set_base);
+        return (int)hipGetLastError();
     }
     const int64_t tickets = (int64_t)n * (slots < kWalkLanes ? slots : kWalkLanes);
     // a window directory and many hits per pattern: the ticket-queue form (k_locate_walk_q).  Measured (round 6, profiles/r06_experiments.txt

@@ -196,6 +196,14 @@ class FmIndex:
         check(lib.fmx_window_cells_info(self._h, C.byref(nbytes)), "fmx_window_cells_info")
         return nbytes.value
 
+    def locate_rows_info(self):
+        """(bytes, replay_rows) of the resident index's row table (0, 0: none) — fmx_locate_rows_info.  An index made resident
+        while option "locate_rows" is 1 keeps what locate() returns for every BWT row (4 bytes per text character) and gathers
+        its hits instead of walking to them; replay_rows = rows that are walked all the same"""
+        nbytes, replay = C.c_int64(0), C.c_int64(0)
+        check(lib.fmx_locate_rows_info(self._h, C.byref(nbytes), C.byref(replay)), "fmx_locate_rows_info")
+        return nbytes.value, replay.value
+
     def suffix_table_info(self):
         """(characters, bytes) of the resident index's suffix table (0, 0: none) — fmx_suffix_table_info"""
         chars, nbytes = C.c_int32(0), C.c_int64(0)

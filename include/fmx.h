@@ -452,21 +452,19 @@ const char *fmx_last_error(void);
  * returns it to the driver. */
 void fmx_release_scratch(void);
 int fmx_device_count(void);
-/* launch tunables: "block" = threads per workgroup (512 | 1024), "groups_per_cu" = grid cap per CU,
- * "sort_min" = smallest batch that is processed in suffix-sorted order (0 = never), "sort_bits" = sort key width,
- * "boundary_accel" = 0 forces the literal +4-chunk right walk of extractUntilBoundary, "boundary_group" = lanes
- * per extractUntilBoundary query (0 | 2 | 4 | 8 | 16), "coarse_bits" / "plan_fine" = bins and fine pass of the plan
- * stage, "plan_sa_key" / "plan_sa_min" / "plan_min_per_string" / "walk_order_min" / "walk_fine" / "boundary_order_min" = which batches are planned
- * and by what (fmx_count_batch_is_planned), "suffix_table" = 0: launches ignore the index's suffix table, "lf_steps_executed_only" = 1: the LF-step
- * output of count() leaves out the rank evaluations the suffix table answered (bench.py's executed-work figure; the
- * default reports the reference's count), "boundary_first_fill" = 0: a lane of extractUntilBoundary walks its two
- * sample intervals one after the other instead of interleaved (A/B; 2 = default).
- * Applied when an index is flattened or becomes resident afterwards: "suffix_table_mb" / "suffix_table_chars" (budget
- * and depth of the suffix table, 0 = none), "sb_cache_limit" (superblocks whose headers are staged in LDS), "map_by_symbol" / "map_fast" / "inv_fast"
- * (layout of the image: tests force the reference's own routes with them), "window_cells" (the window directory of
- * fmx_window_cells_info: 0 none, 1 always, 2 where it fits a quarter of the device's free memory), "locate_rows" (the row table of
- * fmx_locate_rows_info: 0 none — the default —, 1 where it fits; "rows_order" = 1: a locate over it keeps the walk-order stage in front; default 0, the caller's order: measured faster).  Applied by
- * fmx_build_on_device: "wavelet_on_device" = 0 encodes the wavelet tree on the host.
+/* Runtime options (process-wide; FMX_E_ARG for an unknown name or a value the option does not take, which then keeps what it had).
+ * The complete list — every name with its default, the values it takes and what it does — is the table in
+ * index4j_amd/csrc/fmx_options.cpp; tests/test_option_ranges.py pins it.  The groups:
+ * launch tunables, read by every launch: workgroup size and grid cap ("block" = 512 | 1024, "groups_per_cu"), which batches are
+ * planned and by what (the "sort_*", "plan_*", "walk_*" and "boundary_*" options; fmx_count_batch_is_planned), and A/B switches
+ * that force a plainer route ("suffix_table" = 0: launches ignore the index's suffix table, "boundary_accel" = 0: the literal
+ * +4-chunk right walk of extractUntilBoundary).  "lf_steps_executed_only" = 1: the LF-step output of count() leaves out the rank
+ * evaluations the suffix table answered (bench.py's executed-work figure; the default reports the reference's count).
+ * Applied when an index is flattened or becomes resident AFTERWARDS (an index that already is keeps what it has): budget and
+ * depth of the suffix table, the LDS cache of superblock headers, the layout of the image (tests force the reference's own routes
+ * with it), the window directory of fmx_window_cells_info, the row table of fmx_locate_rows_info, a suffix array's fence table.
+ * Applied by fmx_build_on_device: "wavelet_on_device" = 0 encodes the wavelet tree on the host.
+ * The "host_*" and "segments_*" options choose how the host-buffer and segment-set entry points stage their copies and streams.
  * Results are identical for every setting. */
 /* Image form (fmx_set_option("image_compact", 0 | 1), applies to images flattened afterwards: fmx_to_device / fmx_blob of an index
  * that has none yet).  0 (default): the bit vectors of the wavelet tree and the sampled-row bitmap are EXPANDED into 16-byte cells

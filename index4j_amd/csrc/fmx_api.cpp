@@ -5,6 +5,7 @@
 #include "fmx_device.hpp"
 #include "fmx_build_stage.hpp"
 #include "fmx_model.hpp"
+#include "fmx_options.hpp"
 #include "fmx_plan.hpp"
 #include "fmx_sa_index.hpp"
 
@@ -29,49 +30,12 @@
 #include <vector>
 
 // fmx_kernels.hip is compiled twice: namespace fmx serves expanded images, fmxc compact ones (BlobHeader.compact)
-#define FMX_KERNEL_API                                                                                                  \
-    int launch_suffix_level1(const fmx::DevIndex &, fmx::SuffixSlot *, uint32_t *, uint32_t, hipStream_t);              \
-    int launch_suffix_expand(const fmx::DevIndex &, int, const fmx::SuffixSlot *, uint32_t, int, int, fmx::SuffixSlot *, uint32_t *, uint32_t, hipStream_t); \
-    int launch_suffix_insert(const fmx::DevIndex &, const fmx::SuffixSlot *, uint32_t, int, fmx::SuffixSlot *, hipStream_t); \
-    int launch_suffix_order1(const fmx::DevIndex &, float *, hipStream_t);                                              \
-    int launch_win_build(const fmx::DevIndex &, int, uint32_t, fmx::Quad *, uint32_t *, hipStream_t);                   \
-    int launch_win_other(const fmx::DevIndex &, int, uint32_t, fmx::Quad *, const uint32_t *, uint16_t *, uint32_t *, int, uint64_t *, uint32_t, hipStream_t); \
-    int launch_win_flat(const fmx::DevIndex &, int, uint32_t, uint32_t *, uint32_t *, uint64_t *, uint32_t, hipStream_t);           \
-    int launch_rows_fill(const fmx::DevIndex &, int, uint32_t, uint32_t *, uint32_t *, hipStream_t);                    \
-    int launch_count_plan(const fmx::DevIndex &, int, const uint16_t *, const int32_t *, int32_t, void *, size_t, bool, fmx::CountPlan *, \
-                          hipStream_t);                                                                                 \
-    int launch_count(const fmx::DevIndex &, int, const uint16_t *, const int32_t *, const fmx::CountPlan *, bool, int32_t, int32_t *, \
-                     int32_t *, int32_t *, int32_t *, hipStream_t);                                                     \
-    size_t count_workspace_bytes(const fmx::DevIndex &, int32_t n);                                                     \
-    int launch_locate_walk(const fmx::DevIndex &, int, const int32_t *, int32_t, int32_t, int32_t *, int32_t, int32_t *, \
-                           int32_t *, int32_t *, const int32_t *, void *, size_t, bool, hipStream_t, int64_t *, int64_t); \
-    int launch_segment_commit(int32_t *, int32_t *, const int32_t *, const int32_t *, int32_t, int32_t, int, hipStream_t); \
-    size_t walk_workspace_bytes(const fmx::DevIndex &, int32_t n);                                                      \
-    int launch_extract(const fmx::DevIndex &, int, const int32_t *, const int32_t *, int64_t, uint16_t *, int32_t, int32_t, \
-                       int32_t *, int32_t *, int32_t *, const int32_t *, int32_t, int32_t, void *, size_t, bool, hipStream_t); \
-    int launch_extract_boundary(const fmx::DevIndex &, int, const int32_t *, int64_t, uint16_t, int, uint16_t *, int32_t, \
-                                int32_t, int32_t *, int32_t *, int32_t *, int32_t *, void *, size_t, const int32_t *, int32_t, \
-                                void *, size_t, bool, hipStream_t);                                                     \
-    size_t boundary_workspace_bytes(const fmx::DevIndex &, int64_t n, int n_cu);                                        \
-    size_t boundary_order_bytes(const fmx::DevIndex &, int64_t n);                                                      \
-    int launch_rrr_rank_ones(const fmx::DevIndex &, int, const int32_t *, int32_t, int32_t *, hipStream_t);             \
-    int launch_rrr_access(const fmx::DevIndex &, int, const int32_t *, int32_t, uint8_t *, int32_t *, hipStream_t);     \
-    int launch_segment_add_counts(int64_t *, int64_t *, int32_t *, const int32_t *, const int32_t *, const int32_t *, int32_t, \
-                                  int, hipStream_t);                                                                    \
-    int launch_segment_append_hits(int64_t *, int32_t *, int32_t *, const int32_t *, const int32_t *, const int32_t *, int32_t, \
-                                   int32_t, int64_t, int, hipStream_t);                                                 \
-    int launch_fill_offsets(int32_t *, int32_t, int32_t, int32_t, hipStream_t);                                         \
-    int launch_wt_rank(const fmx::DevIndex &, int, const int64_t *, const int32_t *, int32_t, int64_t *, int32_t *, hipStream_t); \
-    int launch_wt_inverse_select(const fmx::DevIndex &, int, const int64_t *, int32_t, int64_t *, int32_t *, hipStream_t); \
-    int set_option(const char *, int);                                                                                  \
-
 namespace fmx {
-FMX_KERNEL_API
+#include "fmx_kernel_api.hpp"
 }  // namespace fmx
 namespace fmxc {
-FMX_KERNEL_API
+#include "fmx_kernel_api.hpp"
 }  // namespace fmxc
-#undef FMX_KERNEL_API
 struct fmx_index;
 static bool image_is_compact(const fmx_index *idx);
 // k_<launcher>(idx, args...): the launcher of the namespace that serves this index's image
@@ -156,46 +120,9 @@ static bool image_is_compact(const fmx_index *idx) { return idx->hdr.compact != 
 namespace {
 
 thread_local std::string g_err;
-std::atomic<int> g_wavelet_on_device{1};  // option "wavelet_on_device": 0 = fmx_build_on_device encodes the wavelet tree on the host
-std::atomic<int> g_suffix_table_mb{256};  // option "suffix_table_mb": budget of the suffix table of indexes made resident afterwards (0 = none)
-std::atomic<int> g_suffix_table_chars{8};  // option "suffix_table_chars": its depth (characters; the size limit and the key width may cut it)
-// The plan stage (suffix order of a batch) pays while MANY patterns share the table string they start from — their first
-// steps then read the same lines.  Option "plan_min_per_string": a batch is planned only if it holds at least this many
-// patterns per string of the table's deepest level (0 = every batch of sort_min patterns or more is planned).  Measured
-// (tools/depth_sort_probe.py, tools/nosort_probe.py): 1 M patterns over 26 K strings (depth 4): planned 0.168 ms, caller's
-// order 0.179; over 227 K strings (depth 5): 0.150 / 0.141; 65,536 patterns over 227 K: 0.045 / 0.023.
-std::atomic<int> g_plan_min_per_string{16};
-std::atomic<int> g_plan_sa_min{786432};   // option "plan_sa_min" (plan_pays)
-std::atomic<int> g_plan_sa_key_api{2};     // mirror of the kernels' option "plan_sa_key"
-std::atomic<int> g_code_bits_12_api{1};   // mirror of the kernels' option "code_bits_12": the key width of suffix tables grown from now on
-std::atomic<int> g_suffix_table_in_use{1};  // mirror of the kernels' A/B option "suffix_table": launches told to ignore the table plan as if there were none
-std::atomic<int> g_suffix_table_image_fraction{8};  // option "suffix_table_image_fraction": the table stays below image / this (0 = only the budget counts)
-// option "window_cells": indexes made resident afterwards grow a window directory (fmx_device.hpp "window directory": 64 bytes per
-// 112 text characters + 8 per position no class holds, beside the image) — 0 = none, 1 = always, 2 (default) = where it fits a
-// quarter of the device's free memory AND the absolute budget "window_cells_mb" (per index; default 65,536 MiB: a process that
-// holds many indexes lowers it, or the quarter rule shrinks what is free geometrically)
-std::atomic<int> g_window_cells{2};
-std::atomic<int> g_window_cells_mb{65536};
-// option "locate_rows": indexes made resident afterwards grow a ROW TABLE (fmx_device.hpp DevIndex.rows: 4 bytes per text character
-// beside the image; locate() then gathers its hits instead of walking to them) — 0 (default) = never, 1 = where the text is shorter
-// than 2^31 characters and the table fits the directory's two rules: "window_cells_mb" and a quarter of the device's free memory
-std::atomic<int> g_locate_rows{0};
-// option "window_entry_bytes": the directory's entries — 0 = four bytes (the row; the symbol by a search over cumulativeCounts) where
-// those fit LDS (fmx::kWinSymbolSearchMax), six bytes otherwise; 4 / 6 = that form whatever the alphabet (tests, A/B)
-std::atomic<int> g_window_entry_bytes{0};
-// option "window_flat_fraction": under window_cells = 2 the directory takes its FLAT form (4 bytes per text byte, every step of a walk
-// one sector) where that costs at most 1 / this of the device's memory (default 128); 0 = never by itself (window_cells = 3 asks by name)
-std::atomic<int> g_window_flat_fraction{128};
-// host-buffer count(): batches of at least this many patterns go through the pipeline (smaller ones: one copy in, kernels, one copy out)
-std::atomic<int> g_host_small_max{2048};  // option "host_small_max": host-array calls of at most this many patterns / queries go through one mapped pinned block (0: off)
-std::atomic<int> g_host_pipeline_min{131072};
-std::atomic<int> g_host_mapped{1};  // option "host_mapped": every array of a host-buffer count registered -> one launch over the mapped arrays, no copies
-std::atomic<int> g_host_direct_stores{1};  // option "host_direct_stores": the pipeline's kernels store results straight into registered arrays
-std::atomic<int> g_host_pipeline_chunk{262144};  // patterns per stage of that pipeline
 // what fmx_host_register pinned: start -> bytes (mapped_range trusts nothing else)
 std::mutex g_registered_mutex;
 std::map<uintptr_t, size_t> g_registered;
-std::atomic<int> g_sb_cache_limit{320};  // option "sb_cache_limit": applies to indexes made resident afterwards (tests: 0 = no LDS cache)
 int fail(int code, const std::string &msg) {
     g_err = msg;
     // a failed runtime call also stays behind as the thread's "last error": taken off with the report, or the NEXT call's
@@ -265,7 +192,7 @@ void make_dev_index(fmx_index *idx) {
     d.map_by_symbol = h.map_by_symbol;
     d.suffix_table = nullptr;
     d.suffix_chars = 0;
-    d.suffix_key_bits = fmx::fmx_code_bits_for(h.wt_sigma, g_code_bits_12_api.load() != 0);
+    d.suffix_key_bits = fmx::fmx_code_bits_for(h.wt_sigma, fmx::options().code_bits_12.load() != 0);
     d.suffix_shift = 0;
     d.suffix_mask = 0;
     d.suffix_order1 = nullptr;
@@ -279,7 +206,7 @@ void make_dev_index(fmx_index *idx) {
     d.c_lut_shift = 0;
     d.rows = nullptr;
     d.sb_cache = nullptr;
-    d.sb_cache_limit = g_sb_cache_limit;
+    d.sb_cache_limit = fmx::options().sb_cache_limit;
     d.wt_size = (uint32_t)h.wt_size;
     d.self = nullptr;
 }
@@ -316,9 +243,6 @@ int require_device(const fmx_index *idx, bool rrr_handle = false) {
 }
 
 constexpr int kWsPlan = 0, kWsBoundary = 1, kWsWalk = 2, kWsSegRange = 3, kWsSegCounts = 4;  // (kWsWalk: the walk order of locate, a plan-like head; kWsSegRange: a segment set's second {found, status, range} buffers)
-std::atomic<int> g_segments_direct{1};   // option "segments_direct": 0 = every segment's hits staged and appended (A/B)
-std::atomic<int> g_segments_overlap{1};  // option "segments_overlap": 0 = a segment set's kernels all on the caller's stream (A/B)
-std::atomic<int> g_segments_overlap_min{262144};  // option "segments_overlap_min": ... and only for batches at least this large
 
 // the side stream of `stream` with at least n_events events (nullptr: could not be made — the caller stays on one stream)
 fmx_index::SideLane *side_lane(const fmx_index *idx, void *stream, size_t n_events) {
@@ -579,11 +503,6 @@ CopyPool &copy_pool() {
     static CopyPool *pool = new CopyPool();  // leaked on purpose: its threads outlive every static destructor
     return *pool;
 }
-// option "host_stage_threads": host threads that stage a pageable array into pinned memory (0 / 1 = the runtime's own staging, the
-// default BY MEASUREMENT: with the result copies gone — below — a 1 M-pattern call takes 0.58 ms with the runtime's staging and
-// 0.70-0.73 with 3-6 threads of this pool: the runtime's copy is not what the call was waiting for; profiles/r06_experiments.txt 4)
-std::atomic<int> g_host_stage_threads{0};
-
 // Three streams per (host thread, device) for the pipelined host-buffer entry points.  Created on first use and never
 // destroyed (a thread_local destructor would run while the HIP runtime may already be shutting down).
 constexpr int kPipeStreams = 3;  // copies in, kernels, copies out
@@ -777,140 +696,10 @@ void fmx_release_scratch(void) {
 
 int fmx_set_option(const char *name, int value) {
     return guarded([&]() -> int {
-    if (name && !strcmp(name, "sb_cache_limit")) {
-        if (value < 0 || value > 320) return fail(FMX_E_ARG, "bad value");
-        g_sb_cache_limit = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "map_by_symbol")) {  // layout of the mapping tables of images flattened from now on
-        if (value < -1 || value > 1) return fail(FMX_E_ARG, "bad value");
-        fmx::set_map_by_symbol(value);
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "map_fast")) {  // 0: images flattened from now on keep every mapping entry on the reference's route
-        fmx::set_map_fast(value != 0);
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "suffix_table_mb")) {  // budget for the suffix table of indexes made resident from now on
-        if (value < 0 || value > (1 << 16)) return fail(FMX_E_ARG, "bad value");
-        g_suffix_table_mb = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "host_mapped")) {
-        g_host_mapped = value != 0;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "host_direct_stores")) {
-        g_host_direct_stores = value != 0;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "host_pipeline_min")) {  // host-buffer count(): batches at least this large are pipelined (0 = never)
-        if (value < 0) return fail(FMX_E_ARG, "bad value");
-        g_host_pipeline_min = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "host_small_max")) {  // batches of at most this many patterns go through one mapped pinned block (0: off)
-        if (value < 0) return fail(FMX_E_ARG, "bad value");
-        g_host_small_max = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "host_stage_threads")) {  // host threads staging a pageable array into pinned memory (0 / 1: the runtime's own staging)
-        if (value < 0 || value > 64) return fail(FMX_E_ARG, "bad value");
-        g_host_stage_threads = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "host_pipeline_chunk")) {
-        if (value < 65536) return fail(FMX_E_ARG, "bad value");
-        g_host_pipeline_chunk = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "suffix_table_chars")) {  // depth of the suffix table of indexes made resident from now on
-        if (value < 0 || value > 8) return fail(FMX_E_ARG, "bad value");
-        g_suffix_table_chars = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "plan_sa_min")) {
-        if (value < 0) return fail(FMX_E_ARG, "bad value");
-        g_plan_sa_min = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "plan_min_per_string")) {
-        if (value < 0) return fail(FMX_E_ARG, "bad value");
-        g_plan_min_per_string = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "suffix_table_image_fraction")) {  // the table stays below image bytes / value (0: only the budget counts)
-        if (value < 0) return fail(FMX_E_ARG, "bad value");
-        g_suffix_table_image_fraction = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "wavelet_on_device")) {
-        g_wavelet_on_device = value != 0;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "window_cells")) {  // window directory of indexes made resident from now on: 0 none, 1 always, 2 if it fits, 3 the flat form
-        if (value < 0 || value > 3) return fail(FMX_E_ARG, "bad value");
-        g_window_cells = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "window_flat_fraction")) {  // the flat form by itself up to 1 / value of the device's memory (0: never)
-        if (value < 0) return fail(FMX_E_ARG, "bad value");
-        g_window_flat_fraction = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "window_entry_bytes")) {  // entries of the window directories grown from now on: 0 by the alphabet, 4, 6
-        if (value != 0 && value != 4 && value != 6) return fail(FMX_E_ARG, "bad value");
-        g_window_entry_bytes = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "locate_rows")) {  // row table of indexes made resident from now on: 0 never, 1 where it fits
-        if (value != 0 && value != 1) return fail(FMX_E_ARG, "bad value");
-        g_locate_rows = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "window_cells_mb")) {  // absolute budget of one index's window directory under "window_cells" = 2
-        if (value < 0) return fail(FMX_E_ARG, "bad value");
-        g_window_cells_mb = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "segments_overlap_min")) {  // smallest batch whose segment searches run beside the walks (side stream)
-        if (value < 0) return fail(FMX_E_ARG, "bad value");
-        g_segments_overlap_min = value;
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "cells_split_blocks")) {  // tests: chunked decoding of short vectors too (same image)
-        fmx::set_split_blocks(value);
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "inv_fast")) {  // 0: images flattened from now on walk inverseSelect the reference's way
-        fmx::set_inv_fast(value != 0);
-        return FMX_OK;
-    }
-    if (name && !strcmp(name, "image_compact")) {  // images flattened from now on keep their bit vectors compressed (fmx.h)
-        fmx::set_image_compact(value);
-        return FMX_OK;
-    }
-    if (!name) return fail(FMX_E_ARG, "unknown option or bad value");
-    if (!strcmp(name, "suffix_table")) g_suffix_table_in_use = value != 0;
-    if (!strcmp(name, "plan_sa_key") && value >= 0 && value <= 2) g_plan_sa_key_api = value;
-    if (!strcmp(name, "code_bits_12")) g_code_bits_12_api = value != 0;
-    if (!strcmp(name, "segments_direct")) {
-        g_segments_direct = value != 0;
-        return FMX_OK;
-    }
-    if (!strcmp(name, "segments_overlap")) {
-        g_segments_overlap = value != 0;
-        return FMX_OK;
-    }
-    {  // options of the suffix-array kernels (which also follow "block" and "groups_per_cu")
-        const int rc = fmx::sa_set_option(name, value);
-        if (rc < 0) return fail(FMX_E_ARG, "bad value");
-        if (rc == 0) return FMX_OK;
-    }
-    {  // launch options go to both kernel sets
-        const int a = fmx::set_option(name, value), b = fmxc::set_option(name, value);
-        if (a || b) return fail(FMX_E_ARG, "unknown option or bad value");
-    }
+    if (!name) return fail(FMX_E_ARG, "null option name");
+    const fmx::OptionRow *row = fmx::find_option(name);  // fmx_options.cpp: the table of every option
+    if (!row) return fail(FMX_E_ARG, std::string("unknown option \"") + name + "\"");
+    if (!row->set(value)) return fail(FMX_E_ARG, std::string("option \"") + name + "\" does not take the value " + std::to_string(value));
     return FMX_OK;
     });
 }
@@ -945,7 +734,7 @@ int fmx_build_on_device(const uint16_t *text, int32_t n, int32_t sample_rate, in
     std::string err;
     fmx::SaStageStats stats;
     int rc = fmx::build_model(text, n, sample_rate, enable_extract != 0, idx->model, err, device, &stats,
-                              g_wavelet_on_device != 0);
+                              fmx::options().wavelet_on_device != 0);
     if (rc == -2) return fail(FMX_E_ALPHABET, err);
     if (rc == -5) return fail(FMX_E_NO_DEVICE, err);
     if (rc == -6) return fail(FMX_E_HIP, err);
@@ -1076,7 +865,7 @@ static void build_window_cells(fmx_index *idx) {
     idx->dev.win_full = nullptr;
     idx->dev.win_entry4 = 0;
     idx->dev.win_flat = 0;
-    const int mode = g_window_cells.load();
+    const int mode = fmx::options().window_cells.load();
     if (mode == 0 || idx->rrr_only || idx->wavelet_only || idx->hdr.kind != 0 || idx->hdr.wt_size <= 0 || !idx->dev.self) return;
     // THE FLAT FORM (fmx_device.hpp win_step): one 32-bit word per position instead of cells and entries — 4 bytes per text
     // byte, every step of a walk ONE sector (locate 18-24 % faster, extract 10 %).  Asked for by name (window_cells = 3), or
@@ -1086,13 +875,13 @@ static void build_window_cells(fmx_index *idx) {
     bool flat = mode == 3;
     // (by itself only for alphabets whose cumulativeCounts fit LDS: the flat form's words are rows, and a kernel that wants the symbol
     // searches for it — over 8 KB of LDS, not over a table of up to 32,768 entries in memory)
-    if (mode == 2 && g_window_flat_fraction.load() > 0 && (uint64_t)idx->hdr.wt_size <= 0x3fffffffull &&
+    if (mode == 2 && fmx::options().window_flat_fraction.load() > 0 && (uint64_t)idx->hdr.wt_size <= 0x3fffffffull &&
         idx->hdr.n_c <= fmx::kWinSymbolSearchMax) {
         size_t free_b = 0, total_b = 0;
         const size_t need = (size_t)idx->hdr.wt_size * 4 + ((size_t)4096 + (size_t)idx->hdr.wt_size / 512) * 8 + 64;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            flat = need <= total_b / (size_t)g_window_flat_fraction.load() && need <= free_b / 4 &&
-                   need <= ((size_t)g_window_cells_mb.load() << 20);
+            flat = need <= total_b / (size_t)fmx::options().window_flat_fraction.load() && need <= free_b / 4 &&
+                   need <= ((size_t)fmx::options().window_cells_mb.load() << 20);
         else
             (void)hipGetLastError();
     }
@@ -1131,7 +920,7 @@ static void build_window_cells(fmx_index *idx) {
     if (mode == 2) {  // cells + (at worst) an entry per position must fit a quarter of what is free, and the absolute budget
         size_t free_b = 0, total_b = 0;
         const size_t worst = bytes + (size_t)idx->hdr.wt_size * fmx::kWinEntryWords * sizeof(uint16_t);
-        if (worst > ((size_t)g_window_cells_mb.load() << 20) || hipMemGetInfo(&free_b, &total_b) != hipSuccess || worst > free_b / 4) {
+        if (worst > ((size_t)fmx::options().window_cells_mb.load() << 20) || hipMemGetInfo(&free_b, &total_b) != hipSuccess || worst > free_b / 4) {
             (void)hipGetLastError();
             return;
         }
@@ -1167,7 +956,7 @@ static void build_window_cells(fmx_index *idx) {
     // did not fit (no directory in that form then), how many of the four-byte form's slots are taken; then those slots (eight
     // bytes each: the few answers that are more than a row).  A four-byte directory that runs out of slots is made again with
     // six-byte entries.
-    const int want = g_window_entry_bytes.load();
+    const int want = fmx::options().window_entry_bytes.load();
     bool entry4 = want == 4 || (want == 0 && idx->hdr.n_c <= fmx::kWinSymbolSearchMax);
     for (;;) {
         const size_t per_entry = entry4 ? 4 : fmx::kWinEntryWords * sizeof(uint16_t);
@@ -1215,12 +1004,12 @@ static void build_locate_rows(fmx_index *idx) {
     idx->rows_bytes = 0;
     idx->rows_replay = 0;
     idx->dev.rows = nullptr;
-    if (g_locate_rows.load() != 1 || idx->rrr_only || idx->wavelet_only || idx->hdr.kind != 0 || idx->hdr.wt_size <= 0 ||
+    if (fmx::options().locate_rows.load() != 1 || idx->rrr_only || idx->wavelet_only || idx->hdr.kind != 0 || idx->hdr.wt_size <= 0 ||
         (uint64_t)idx->hdr.wt_size >= 0x80000000ull || !idx->dev.self)
         return;
     const size_t bytes = ((size_t)idx->hdr.wt_size * 4 + 63) & ~(size_t)63;
     size_t free_b = 0, total_b = 0;
-    if (bytes > ((size_t)g_window_cells_mb.load() << 20) || hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4) {
+    if (bytes > ((size_t)fmx::options().window_cells_mb.load() << 20) || hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4) {
         (void)hipGetLastError();
         return;
     }
@@ -1301,17 +1090,17 @@ static void build_suffix_table(fmx_index *idx) {
     idx->dev.suffix_table = nullptr;
     idx->dev.suffix_order1 = nullptr;
     idx->dev.suffix_chars = 0;
-    idx->dev.suffix_key_bits = fmx::fmx_code_bits_for(idx->hdr.wt_sigma, g_code_bits_12_api.load() != 0);
+    idx->dev.suffix_key_bits = fmx::fmx_code_bits_for(idx->hdr.wt_sigma, fmx::options().code_bits_12.load() != 0);
     idx->dev.suffix_shift = 0;
     idx->dev.suffix_mask = 0;
     if (idx->rrr_only || idx->wavelet_only || idx->hdr.kind != 0) return;
-    const uint64_t budget = (uint64_t)g_suffix_table_mb.load() << 20;
+    const uint64_t budget = (uint64_t)fmx::options().suffix_table_mb.load() << 20;
     const int key_bits = idx->dev.suffix_key_bits;
-    int max_chars = g_suffix_table_chars.load();
+    int max_chars = fmx::options().suffix_table_chars.load();
     if (max_chars > 64 / key_bits) max_chars = 64 / key_bits;
     if (budget == 0 || max_chars < 2 || idx->hdr.wt_sigma < 2) return;
     uint64_t limit = budget;
-    if (const int frac = g_suffix_table_image_fraction.load(); frac > 0)
+    if (const int frac = fmx::options().suffix_table_image_fraction.load(); frac > 0)
         limit = std::min<uint64_t>(limit, std::max<uint64_t>(idx->d_len / (uint64_t)frac, 64 << 10));
     // slots for a set of strings: a power of two, half full at most — or, where only that keeps the table inside its limit, 0.7
     auto slots_for = [&](uint64_t strings) {
@@ -1669,10 +1458,10 @@ void *fmx_device_blob(const fmx_index *idx, size_t *len) {
 //    string they start from — at least "plan_min_per_string" (16) patterns per string of the table's deepest level; always
 //    without a table.
 static bool plan_pays(const fmx_index *idx, int32_t n) {
-    const bool table = idx->dev.suffix_table && idx->suffix_table_deepest != 0 && g_suffix_table_in_use.load();
+    const bool table = idx->dev.suffix_table && idx->suffix_table_deepest != 0 && fmx::options().suffix_table.load();
     if (!table) return true;
-    if (g_plan_sa_key_api.load() != 0) return n >= g_plan_sa_min.load();
-    const int per_string = g_plan_min_per_string.load();
+    if (fmx::options().plan_sa_key.load() != 0) return n >= fmx::options().plan_sa_min.load();
+    const int per_string = fmx::options().plan_min_per_string.load();
     if (per_string <= 0) return true;
     return (uint64_t)n >= (uint64_t)per_string * idx->suffix_table_deepest;
 }
@@ -2050,7 +1839,7 @@ static int locate_segments_impl(const fmx_index *const *segs, int32_t n_segs, co
     // patterns: only for batches that large, and only for the per-stream form (a host call's own stream lives for one call).
     int32_t *set_found[2] = {seg_found, nullptr}, *set_status[2] = {seg_status, nullptr}, *set_range[2] = {range, nullptr};
     fmx_index::SideLane *lane = nullptr;
-    if (g_segments_overlap && !scratch.per_call && n_segs > 1 && n >= g_segments_overlap_min.load()) {
+    if (fmx::options().segments_overlap && !scratch.per_call && n_segs > 1 && n >= fmx::options().segments_overlap_min.load()) {
         void *second = nullptr;
         rc = scratch.get(kWsSegRange, (size_t)n * 4 * sizeof(int32_t), &second);
         if (rc) return rc;
@@ -2124,7 +1913,7 @@ static int locate_segments_impl(const fmx_index *const *segs, int32_t n_segs, co
         // taken from earlier segments shrink this segment's limit
         // (the hits go straight into the set's rows behind those already taken, and a commit of a few bytes per pattern replaces
         // the append of every hit; option "segments_direct" = 0 keeps the staged form)
-        const bool direct = g_segments_direct.load() != 0;
+        const bool direct = fmx::options().segments_direct.load() != 0;
         e = k_launch_locate_walk(segs[s], segs[s]->dev, segs[s]->n_cu, set_range[b], n, max_matches, seg_locs, max_matches,
                                  set_found[b], nullptr, set_status[b], s ? d_found : nullptr, ws, ws_bytes, !scratch.per_call, st,
                                  direct ? d_locs : nullptr, direct ? seg_base[s] : 0);
@@ -2396,7 +2185,7 @@ static int count_batch_pipelined(const fmx_index *idx, const uint16_t *pat, cons
     if (rc) return rc;
     // equal chunks (a schedule of halving sizes — a small last chunk, so that little is left that overlaps nothing — was
     // slower: the first chunk's kernels then start after half of the transfer; profiles/r03_experiments.txt)
-    const int32_t chunk = std::max<int32_t>(kPipeChunkMin, g_host_pipeline_chunk.load());
+    const int32_t chunk = std::max<int32_t>(kPipeChunkMin, fmx::options().host_pipeline_chunk.load());
     std::vector<int32_t> bounds(1, 0);
     while (bounds.back() < n) bounds.push_back((int32_t)std::min<int64_t>(n, (int64_t)bounds.back() + chunk));
     const int32_t n_chunks = (int32_t)bounds.size() - 1;
@@ -2427,7 +2216,7 @@ static int count_batch_pipelined(const fmx_index *idx, const uint16_t *pat, cons
     // are registered arrays of the caller or that staging, mapped either way)
     int32_t *m_cnt = nullptr, *m_lf = nullptr, *m_st = nullptr;
     bool stores_out = false;
-    if (g_host_direct_stores.load()) {
+    if (fmx::options().host_direct_stores.load()) {
         // (a caller's array must lie inside one range registered through fmx_host_register: mapped_range; the library's own pinned
         // staging is mapped by construction — round 5's stricter mapped_range had silently sent it back to result COPIES, eight
         // device-to-host copies of 1 MB at 148 us each per 1 M-pattern call: 1.2 of the call's 1.75 ms, round 6)
@@ -2562,7 +2351,7 @@ static int count_batch_pipelined(const fmx_index *idx, const uint16_t *pat, cons
     std::atomic<bool> feed_stop{false};
     std::thread feeder;
     JoinOnExit join_feeder{feeder, feed_stop};
-    const int stage_threads = g_host_stage_threads.load();
+    const int stage_threads = fmx::options().host_stage_threads.load();
     const bool staged_in = !in_pinned && stage_threads >= 2 && total_chars > pat_off[0] &&
                            h_pat.alloc((size_t)(total_chars - pat_off[0]) * 2) == hipSuccess;
     if (!staged_in) (void)hipGetLastError();
@@ -2765,9 +2554,9 @@ int fmx_count_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pa
     if (n == 0) return FMX_OK;
     HIP_TRY(hipSetDevice(idx->device));
     {
-        const int pipe_min = g_host_pipeline_min;
+        const int pipe_min = fmx::options().host_pipeline_min;
         if (pipe_min > 0 && n >= pipe_min) {
-            if (g_host_mapped.load()) {
+            if (fmx::options().host_mapped.load()) {
                 const int r = count_batch_mapped(idx, pat, pat_off, n, counts, lf_steps, status);
                 if (r != -1) return r;
             }
@@ -2777,7 +2566,7 @@ int fmx_count_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pa
     rc = check_offsets(pat_off, n);
     if (rc) return rc;
     const size_t chars = (size_t)(pat_off[n] > 0 ? pat_off[n] : 0);
-    if (n <= g_host_small_max.load() && chars - (size_t)first_char(pat_off) <= kHostSmallChars) {
+    if (n <= fmx::options().host_small_max.load() && chars - (size_t)first_char(pat_off) <= kHostSmallChars) {
         const int r = count_batch_small(idx, pat, pat_off, n, counts, lf_steps, status);
         if (r != -1) return r;
     }
@@ -2822,7 +2611,7 @@ int fmx_locate_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *p
     // a small call (a Java caller's locate(char[], ...) is a batch of one): characters, offsets and the in / out `locations` rows in
     // ONE mapped pinned block the kernels read and write where it lies; found / LF-steps / statuses — updated with atomics — stay
     // in HBM and come down by three asynchronous copies into the block; one wait (count_batch_small has the story)
-    if (n <= g_host_small_max.load() && chars - first_char(pat_off) <= kHostSmallChars && loc_bytes <= kHostSmallBytes) {
+    if (n <= fmx::options().host_small_max.load() && chars - first_char(pat_off) <= kHostSmallChars && loc_bytes <= kHostSmallBytes) {
         const size_t first = first_char(pat_off), own = chars - first;
         SmallBlock blk;
         if (blk.init(SmallBlock::up(own * 2 + 8) + SmallBlock::up(((size_t)n + 1) * 4) + SmallBlock::up(loc_bytes) + 3 * SmallBlock::up((size_t)n * 4)) ==
@@ -2872,7 +2661,7 @@ int fmx_locate_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *p
     // stores the hits straight into the caller's rows — only the slots it fills travel, and they travel once (the array is in /
     // out, FM:504: unmapped it goes up and comes down whole) — and k_count reads the characters where they are.
     // found / LF-steps / statuses stay in HBM: the kernels update them with atomics.
-    const bool mapped_ok = g_host_mapped.load() != 0;
+    const bool mapped_ok = fmx::options().host_mapped.load() != 0;
     void *m_locs = mapped_ok ? mapped_range(locs, loc_bytes) : nullptr;
     void *m_pat = mapped_ok ? mapped_range(pat, chars * 2) : nullptr;
     const bool locs_mapped = m_locs != nullptr, pat_mapped = m_pat != nullptr;
@@ -2932,7 +2721,7 @@ static int locate_pipeline_host(const fmx_index *idx, const uint16_t *pat, const
     const size_t dst_bytes = slots * (size_t)row_len * 2;
     // a small call: characters, offsets, the in / out rows and per-hit arrays in ONE mapped pinned block (count_batch_small has the
     // story); found / LF-steps / statuses — updated with atomics — stay in HBM and come down by asynchronous copies into the block
-    if (n <= g_host_small_max.load() && chars - first_char(pat_off) <= kHostSmallChars && dst_bytes + slots * 16 <= kHostSmallBytes) {
+    if (n <= fmx::options().host_small_max.load() && chars - first_char(pat_off) <= kHostSmallChars && dst_bytes + slots * 16 <= kHostSmallBytes) {
         const size_t first = first_char(pat_off), own = chars - first;
         SmallBlock blk;
         if (blk.init(SmallBlock::up(own * 2 + 8) + SmallBlock::up(((size_t)n + 1) * 4) + 4 * SmallBlock::up(slots * 4) + SmallBlock::up(dst_bytes) +
@@ -3147,7 +2936,7 @@ int fmx_extract_batch(const fmx_index *idx, const int32_t *start, const int32_t 
     if (n == 0) return FMX_OK;
     HIP_TRY(hipSetDevice(idx->device));
     const size_t dst_bytes = (size_t)n * (size_t)dst_len * 2;
-    if (n <= g_host_small_max.load() && dst_bytes <= kHostSmallBytes) {  // a small call: one mapped pinned block (count_batch_small)
+    if (n <= fmx::options().host_small_max.load() && dst_bytes <= kHostSmallBytes) {  // a small call: one mapped pinned block (count_batch_small)
         SmallBlock blk;
         if (blk.init(5 * SmallBlock::up((size_t)n * 4) + SmallBlock::up(dst_bytes)) == FMX_OK) {
             int32_t *da, *db, *dlen, *dlf, *dst_;
@@ -3200,7 +2989,7 @@ int fmx_extract_boundary_batch(const fmx_index *idx, const int32_t *from, int32_
     if (n == 0) return FMX_OK;
     HIP_TRY(hipSetDevice(idx->device));
     const size_t dst_bytes = (size_t)n * (size_t)dst_len * 2;
-    if (n <= g_host_small_max.load() && dst_bytes <= kHostSmallBytes) {  // a small call: one mapped pinned block (count_batch_small)
+    if (n <= fmx::options().host_small_max.load() && dst_bytes <= kHostSmallBytes) {  // a small call: one mapped pinned block (count_batch_small)
         SmallBlock blk;
         if (blk.init(5 * SmallBlock::up((size_t)n * 4) + SmallBlock::up(dst_bytes)) == FMX_OK) {
             int32_t *da, *dlen, *dlf, *dst_, *daux;

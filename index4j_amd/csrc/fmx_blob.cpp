@@ -345,6 +345,8 @@ int flatten_rrr_only(const RrrModel &r, std::vector<uint8_t> &blob, std::string 
     return 0;
 }
 
+// The image layer's options keep their state here, behind set_* functions: this file is also compiled into host-only test builds
+// that have no option table.  Their rows in fmx_options.cpp call these setters and repeat these defaults.
 // blocks above which a bit vector is decoded in chunks (tests lower it: the image must not depend on it)
 void set_split_blocks(int64_t blocks) { g_split_blocks = blocks < 64 ? 64 : blocks; }
 // -1 = by alphabet size; 0 / 1 force the row layout of the mapping tables (tests exercise both)

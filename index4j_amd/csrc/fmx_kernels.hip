@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fmx_device.hpp"
+#include "fmx_options.hpp"
 #include "fmx_plan.hpp"
 
 // This file is compiled twice (Makefile): as it stands for expanded images (kernels and launchers in namespace fmx), and
@@ -40,7 +41,7 @@
 
 namespace FMX_KNS {
 using namespace fmx;
-static std::atomic<int> g_code_bits_12{1};  // option "code_bits_12" (plan_code_bits)
+#include "fmx_kernel_api.hpp"  // the launchers below, as fmx_api.cpp sees them
 
 // Workgroup size is a template parameter (512 / 1024 threads).  Only the stand-alone RrrVector kernels stage the
 // 32 KiB value-of-offset table in LDS.
@@ -95,7 +96,7 @@ __device__ __forceinline__ void stage_inverse_table(uint16_t *s_inv, const uint1
 // 12 bits for alphabets of 257 .. 4,096 codes (round 6): FIVE codes per word instead of four and a suffix table one character
 // deeper (60-bit keys) — the shape of the data set the reference's published numbers are quoted on (> 1,000 symbols,
 // README.md:291-292).  fmx_code_bits_for (fmx_device.hpp) is the one rule; option "code_bits_12" = 0 gives 16 bits there (A/B).
-inline int plan_code_bits(int32_t sigma) { return fmx_code_bits_for(sigma, g_code_bits_12.load() != 0); }
+inline int plan_code_bits(int32_t sigma) { return fmx_code_bits_for(sigma, options().code_bits_12.load() != 0); }
 
 // The header quad and the bit-vector view quad of every superblock (32 bytes each) are staged in LDS when the
 // index has at most kSbCacheMax superblocks (335 M symbols): the first stage of every rank / inverseSelect then
@@ -150,7 +151,6 @@ __device__ __forceinline__ void stage_c_lds(int32_t *s_c, uint16_t *s_lut, DevIn
 constexpr int kTileThreads = FMX_TILE_THREADS;
 constexpr int kTileItems = FMX_TILE_ITEMS;          // patterns per thread
 constexpr int kTile = kTileThreads * kTileItems;    // patterns per workgroup of the plan kernels
-constexpr int kCoarseBitsMax = 14;                  // 16,384 LDS bins (64 KiB)
 
 // The (up to) 8 trailing characters of a pattern.  Patterns of >= 8 characters: the 16 bytes [beg + m - 8, beg + m) are
 // fetched as four or five ALIGNED dwords (every dword holds at least one byte of the pattern, so nothing outside
@@ -2327,215 +2327,10 @@ __global__ __launch_bounds__(256) void k_segment_commit(int32_t *__restrict__ fo
 
 // ---- launchers (called from fmx_api.cpp) -----------------------------------------------------
 
-// tunables (fmx_set_option): workgroup size and how many workgroups per CU the grid is capped at.  Atomics: a
-// launch on one host thread may read them while another thread sets one (results are identical for every
-// setting, so a launch that sees a mix of old and new values is still correct).
-static std::atomic<int> g_block{512};
-static std::atomic<int> g_groups_per_cu{16};
-static std::atomic<int> g_walk_queue{8};  // option "walk_queue": locate over a window directory hands its tickets out per wave, this many per lane and run (0: the packed form)
-static std::atomic<int> g_walk_queue_min_slots{32};  // option "walk_queue_min_slots": ... for calls with at least this many hit slots per pattern
-static std::atomic<int> g_walk_burst{0};  // option "walk_burst": LF-steps between two hand-outs (0 = sample_rate / 4, at least 2)
-static std::atomic<int> g_walk_pack{1};  // option "walk_pack": locate over a window directory packs the walks still under way into fewer waves (0: A/B)
-static std::atomic<int> g_boundary_accel{1};  // 0 = literal right walk of extractUntilBoundary (A/B and fallback)
-static std::atomic<int> g_boundary_group{4};  // lanes per query of extractUntilBoundary (0 = one lane per query)
-// first fill of extractUntilBoundary's two text windows: 0 = G intervals on each side, a lane walks one after the other;
-// 2 = the same with a lane's two walks interleaved (fm_lf_step2)
-static std::atomic<int> g_boundary_first_fill{2};
-// option "boundary_narrow" (default OFF, by measurement — round 6, profiles/r06_experiments.txt 2): the narrow first round walks 37.8 M
-// LF-steps where the wide form walks 50.9 M on configs[3] and takes 0.855 ms against 0.808: every pass costs a wave's lifetime (64
-// dependent steps of one or two HBM round trips: ~0.35 ms whatever the batch), and the second pass pays it again for a quarter of the queries
-static std::atomic<int> g_boundary_narrow{0};
-static std::atomic<int> g_boundary_narrow_min{4096};   // option "boundary_narrow_min": ... for batches at least this large
-static std::atomic<int> g_regroup_by_length{1};  // k_count: workgroups with mixed pattern lengths hand their records out again by length (0: A/B)
-static std::atomic<int> g_steps_executed_only{0};  // 1 = d_lf_steps of count() leave out what the suffix table answered
-static std::atomic<int> g_suffix_table_use{1};  // 0 = k_count ignores the index's suffix table (A/B)
-static std::atomic<int> g_lds_pad_kb{0};   // experiment knob: extra dynamic LDS per workgroup (lowers occupancy)
-static std::atomic<int> g_sort_min{16384};  // batches at least this large are processed in suffix-sorted order (0 = never)
-// bins of the bucket pass = 2^coarse_bits (<= 14: they live in LDS).  Measured on configs[1] (tools/tune_coarse.py):
-// 14 bits: plan 0.091 ms, step 0.304 ms; 12 bits: 0.075 / 0.286 ms; 10 bits: 0.071 / 0.286 ms; 8 bits: 0.069 / 0.294 ms
-static std::atomic<int> g_coarse_bits{12};
-static std::atomic<int> g_plan_fine{1};  // 0 = skip the window-local fine order (A/B)
-// 0 = order by the trailing characters' codes even where a suffix table exists; 1 = by the SA row the table answers; 2 = by an
-// estimate of that row from the table's two-character strings (SortShape.sa_key)
-static std::atomic<int> g_plan_sa_key{2};
-// planned k_count: a batch of one length runs on half the grid (decided on the device from the plan's flag; 0: A/B).
-// Tried first (round 5): tiles taken from a counter on a grid of 8 workgroups per CU — the barrier that hands a tile to a
-// workgroup's eight waves ties them together: headline 0.138 -> 0.151 ms, series count +3 %.  Dropped.
-static std::atomic<int> g_count_halve_uniform{1};
-// option "count_lean": planned batches over expanded images run k_count_lean + k_count's list mode instead of k_count.  Default
-// OFF, by measurement (round 6, profiles/r06_experiments.txt 1): the lean kernel issues 20 % fewer vector instructions (26.0 M against
-// 32.5 M per headline launch, no spill at all) and takes the SAME time (89.0 against 90.9 us; + 4.6 us for the list pass that finds
-// its list empty) — k_count is not bound by instruction issue.  Kept as the A/B that showed it.
-static std::atomic<int> g_count_lean{0};
-// option "boundary_rounds": extractUntilBoundary (both ways, the group of four) fetches the four sample intervals next to `from`
-// first and the four further out only for the groups whose line does not end inside those (fmx_device.hpp window_fill_round)
-static std::atomic<int> g_boundary_rounds{1};
-// 1 = the plan stage of a batch of at most one tile per CU is ONE launch (k_plan_fused); 0 (default) = k_plan_codes +
-// k_plan_scatter.  Measured (round 5, configs[1]): step 0.1365 -> 0.1339 ms (-2 %), with two batches in flight 0.109 -> 0.117
-// (+7 %: workgroups waiting at the barrier hold their CUs) — not worth a spinning kernel by default.
-static std::atomic<int> g_plan_fused{0};
-static std::atomic<int> g_plan_spin_limit{4096};  // polls of k_plan_fused's barrier before a workgroup aborts the order (~1 us each)
-// locate: batches at least this large walk their hits by the first row of the patterns' SA ranges (0 = always in the caller's
-// order).  Measured on configs[1]'s index, <= 16 hits per pattern (tools/locate_order_probe.py): 16,384 patterns +8 % (the two
-// or three short kernels in front), 32,768 -5 %, 100,000 -24 %, 1,048,576 -43 %.
-static std::atomic<int> g_walk_order_min{32768};
-// extractUntilBoundary: batches at least this large take their queries by text position (0 = always the caller's order):
-// 100,000 hit locations of configs[3] (40,024 distinct) 1.93 -> 1.74 ms sorted on the host (tools/boundary_order_probe.py)
-static std::atomic<int> g_boundary_order_min{32768};
-static std::atomic<int> g_walk_fine{1};  // the window-local fine order on top of the buckets (k_plan_fine; 0: A/B)
-static std::atomic<int> g_sort_bits{28};    // full key width: floor(sort_bits / bits-per-code) trailing characters
-// option "rows_order": 1 = locate over a row table (k_locate_rows) still takes large batches by the first row of their ranges (the
-// walk-order stage in front, as the walks do); 0 (default, by measurement: profiles/r08_locate_rows.json) = in the caller's order —
-// a gather reads one or two sectors per pattern whatever the order, and the three short kernels in front cost more than the
-// locality they buy: configs[2] 0.062 -> 0.044 ms, series locate(1) 0.85 -> 0.77, locate(100) 0.47 -> 0.45
-static std::atomic<int> g_rows_order{0};
-
-int set_option(const char *name, int value) {
-    if (!strcmp(name, "block")) {
-        if (value != 512 && value != 1024) return -1;
-        g_block = value;
-        return 0;
-    }
-    if (!strcmp(name, "walk_pack")) {  // 0: k_locate_walk; 1 / 2: two packings; 3: three
-        if (value < 0 || value > 3) return -1;
-        g_walk_pack = value;
-        return 0;
-    }
-    if (!strcmp(name, "walk_queue")) {
-        if (value < 0 || value > 64) return -1;
-        g_walk_queue = value;
-        return 0;
-    }
-    if (!strcmp(name, "walk_queue_min_slots")) {
-        if (value < 0) return -1;
-        g_walk_queue_min_slots = value;
-        return 0;
-    }
-    if (!strcmp(name, "walk_burst")) {
-        if (value < 0 || value > 1024) return -1;
-        g_walk_burst = value;
-        return 0;
-    }
-    if (!strcmp(name, "groups_per_cu")) {
-        if (value < 1 || value > 64) return -1;
-        g_groups_per_cu = value;
-        return 0;
-    }
-    if (!strcmp(name, "boundary_accel")) {
-        g_boundary_accel = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "boundary_group")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return -1;
-        g_boundary_group = value;
-        return 0;
-    }
-    if (!strcmp(name, "regroup_by_length")) {
-        g_regroup_by_length = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "lf_steps_executed_only")) {
-        g_steps_executed_only = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "boundary_first_fill")) {
-        if (value != 0 && value != 2) return -1;  // (1, half-width windows, was measured slower in round 3 and is gone)
-        g_boundary_first_fill = value;
-        return 0;
-    }
-    if (!strcmp(name, "boundary_narrow")) {
-        g_boundary_narrow = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "boundary_narrow_min")) {
-        if (value < 0) return -1;
-        g_boundary_narrow_min = value;
-        return 0;
-    }
-    if (!strcmp(name, "suffix_table")) {
-        g_suffix_table_use = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "coarse_bits")) {
-        if (value < 4 || value > kCoarseBitsMax - 1) return -1;  // k_plan_scatter keeps two arrays of 2^bits words in LDS
-        g_coarse_bits = value;
-        return 0;
-    }
-    if (!strcmp(name, "plan_sa_key")) {
-        if (value < 0 || value > 2) return -1;
-        g_plan_sa_key = value;
-        return 0;
-    }
-    if (!strcmp(name, "count_halve_uniform")) {
-        g_count_halve_uniform = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "code_bits_12")) {
-        g_code_bits_12 = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "boundary_rounds")) {
-        g_boundary_rounds = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "count_lean")) {
-        g_count_lean = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "plan_fused")) {
-        g_plan_fused = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "plan_spin_limit")) {
-        if (value < 0) return -1;
-        g_plan_spin_limit = value;
-        return 0;
-    }
-    if (!strcmp(name, "plan_fine")) {
-        if (value < 0 || value > 2) return -1;
-        g_plan_fine = value;
-        return 0;
-    }
-    if (!strcmp(name, "lds_pad_kb")) {
-        if (value < 0 || value > 96) return -1;
-        g_lds_pad_kb = value;
-        return 0;
-    }
-    if (!strcmp(name, "sort_min")) {
-        if (value < 0) return -1;
-        g_sort_min = value;
-        return 0;
-    }
-    if (!strcmp(name, "walk_fine")) {
-        g_walk_fine = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "boundary_order_min")) {
-        if (value < 0) return -1;
-        g_boundary_order_min = value;
-        return 0;
-    }
-    if (!strcmp(name, "walk_order_min")) {
-        if (value < 0) return -1;
-        g_walk_order_min = value;
-        return 0;
-    }
-    if (!strcmp(name, "rows_order")) {
-        if (value != 0 && value != 1) return -1;
-        g_rows_order = value;
-        return 0;
-    }
-    if (!strcmp(name, "sort_bits")) {
-        if (value < 1 || value > 32) return -1;
-        g_sort_bits = value;
-        return 0;
-    }
-    return -1;
-}
-
+// tunables: fmx_options.hpp (one reading of an option per decision)
 static int grid_for(int64_t lanes, int block, int n_cu) {
     int64_t blocks = (lanes + block - 1) / block;
-    const int64_t cap = (int64_t)n_cu * g_groups_per_cu;  // a few rounds of workgroups per CU, grid-stride the rest
+    const int64_t cap = (int64_t)n_cu * options().groups_per_cu;  // a few rounds of workgroups per CU, grid-stride the rest
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     return (int)blocks;
@@ -2543,20 +2338,20 @@ static int grid_for(int64_t lanes, int block, int n_cu) {
 
 #define FMX_DISPATCH(KERNEL, LANES, ...)                                                                     \
     do {                                                                                                     \
-        const int blk__ = g_block;                                                                           \
+        const int blk__ = options().block;                                                                   \
         const dim3 grid__(grid_for((LANES), blk__, n_cu));                                                   \
         if (blk__ == 1024)                                                                                   \
-            hipLaunchKernelGGL(KERNEL<1024>, grid__, dim3(1024), (size_t)g_lds_pad_kb * 1024, st, __VA_ARGS__);                        \
+            hipLaunchKernelGGL(KERNEL<1024>, grid__, dim3(1024), (size_t)options().lds_pad_kb * 1024, st, __VA_ARGS__); \
         else                                                                                                 \
-            hipLaunchKernelGGL(KERNEL<512>, grid__, dim3(512), (size_t)g_lds_pad_kb * 1024, st, __VA_ARGS__);                          \
+            hipLaunchKernelGGL(KERNEL<512>, grid__, dim3(512), (size_t)options().lds_pad_kb * 1024, st, __VA_ARGS__); \
     } while (0)
 
 // ... of a kernel that only runs over a window directory, instantiated per form of it (fmx_device.hpp: kFormCells / kFormFlat)
 #define FMX_DISPATCH_FORM(KERNEL, IX, LANES, ...)                                                                      \
     do {                                                                                                               \
-        const int blk__ = g_block;                                                                                     \
+        const int blk__ = options().block;                                                                             \
         const dim3 grid__(grid_for((LANES), blk__, n_cu));                                                             \
-        const size_t lds__ = (size_t)g_lds_pad_kb * 1024;                                                              \
+        const size_t lds__ = (size_t)options().lds_pad_kb * 1024;                                                      \
         if ((IX).win_flat) {                                                                                           \
             if (blk__ == 1024)                                                                                         \
                 hipLaunchKernelGGL((KERNEL<1024, kFormFlat>), grid__, dim3(1024), lds__, st, __VA_ARGS__);            \
@@ -2574,9 +2369,9 @@ static int grid_for(int64_t lanes, int block, int n_cu) {
 // kWinFlat / kWinNever)
 #define FMX_DISPATCH_WIN(KERNEL, IX, LANES, ...)                                                                       \
     do {                                                                                                               \
-        const int blk__ = g_block;                                                                                     \
+        const int blk__ = options().block;                                                                             \
         const dim3 grid__(grid_for((LANES), blk__, n_cu));                                                             \
-        const size_t lds__ = (size_t)g_lds_pad_kb * 1024;                                                              \
+        const size_t lds__ = (size_t)options().lds_pad_kb * 1024;                                                      \
         if ((IX).win && (IX).win_flat) {                                                                               \
             if (blk__ == 1024)                                                                                         \
                 hipLaunchKernelGGL((KERNEL<1024, kWinFlat>), grid__, dim3(1024), lds__, st, __VA_ARGS__);             \
@@ -2599,14 +2394,14 @@ static SortShape sort_shape(const DevIndex &ix) {
     SortShape sh;
     sh.bits = 1;
     while ((1 << sh.bits) < ix.wt_sigma && sh.bits < 15) ++sh.bits;
-    const int sort_bits = g_sort_bits, coarse_bits = g_coarse_bits;
+    const int sort_bits = options().sort_bits, coarse_bits = options().coarse_bits;
     sh.chars = sort_bits / sh.bits;
     if (sh.chars < 1) sh.chars = 1;
     if (sh.chars > 64 / plan_code_bits(ix.wt_sigma)) sh.chars = 64 / plan_code_bits(ix.wt_sigma);
     sh.total_bits = sh.chars * sh.bits;
     sh.sa_key = 0;
-    if (g_plan_sa_key && ix.suffix_table && g_suffix_table_use) {  // order by SA row (SortShape.sa_key)
-        sh.sa_key = g_plan_sa_key;
+    if (options().plan_sa_key && ix.suffix_table && options().suffix_table) {  // order by SA row (SortShape.sa_key)
+        sh.sa_key = options().plan_sa_key;
         sh.total_bits = 1;
         while (sh.total_bits < 32 && (1ll << sh.total_bits) <= (long long)ix.length) ++sh.total_bits;
     }
@@ -2618,7 +2413,7 @@ static SortShape sort_shape(const DevIndex &ix) {
 // [n] (16 B) | records in processing order [n] (16 B)
 // bytes of scratch needed to order a batch of n patterns (0 = the batch is not sorted)
 size_t count_workspace_bytes(const DevIndex &ix, int32_t n) {
-    const int sort_min = g_sort_min;
+    const int sort_min = options().sort_min;
     if (sort_min <= 0 || n < sort_min) return 0;
     return kPlanHeadBytes + (size_t)n * 2 * sizeof(PlanRec) + 64;
 }
@@ -2654,10 +2449,10 @@ int launch_count_plan(const DevIndex &ix, int n_cu, const uint16_t *pat, const i
     const size_t lds_codes = o1 ? order1_lds_bytes(bins, ix.wt_sigma) : (size_t)bins * 4;
     // ONE launch (k_plan_fused) while every tile can be resident at once — a tile per CU at most — and no fine pass follows (its
     // window order needs the bucket order complete); else k_plan_codes + k_plan_scatter
-    const bool fine_pass = g_plan_fine == 2 || (g_plan_fine == 1 && !sh.sa_key);
-    if (g_plan_fused && !fine_pass && n_cu > 0 && tiles <= n_cu) {
+    const bool fine_pass = options().plan_fine == 2 || (options().plan_fine == 1 && !sh.sa_key);
+    if (options().plan_fused && !fine_pass && n_cu > 0 && tiles <= n_cu) {
         const size_t lds_fused = std::max(lds_codes, (size_t)bins * 8);
-        const uint32_t spin_limit = (uint32_t)g_plan_spin_limit.load();
+        const uint32_t spin_limit = (uint32_t)options().plan_spin_limit.load();
         if (code_bits == 8)
             hipLaunchKernelGGL(k_plan_fused<8>, dim3(tiles), dim3(kTileThreads), lds_fused, st, ix, pat, off, n, sh, ordered, ghist, ticket,
                                ticket + 2, epoch, spin_limit);
@@ -2683,7 +2478,7 @@ int launch_count_plan(const DevIndex &ix, int n_cu, const uint16_t *pat, const i
                        sh.total_bits - sh.coarse_bits, ghist, cursor, ticket, ordered);
     }
     // (the fine pass: for the code key; with the SA-row key 4,096 buckets already are what a full sort gives within 5 %: option 2 forces it)
-    if (g_plan_fine == 2 || (g_plan_fine == 1 && !sh.sa_key))
+    if (options().plan_fine == 2 || (options().plan_fine == 1 && !sh.sa_key))
         hipLaunchKernelGGL(k_plan_fine, dim3((n + kFineWindow - 1) / kFineWindow), dim3(kFineThreads), 0, st, ordered, n);
     plan->recs = ordered;
     // (the records by pattern are dead once the order is made: their place serves k_count_lean's redo list; its two counters sit
@@ -2714,15 +2509,15 @@ int launch_count(const DevIndex &ix, int n_cu, const uint16_t *pat, const int32_
     const bool translate = recs && plan_is_foreign && pl.code_bits == 8 && plan_code_bits(ix.wt_sigma) == 8;
     const int mode = !recs ? 0 : (!plan_is_foreign ? 1 : (translate ? 2 : 3));
     DevIndex ix_launch = ix;
-    if (!g_suffix_table_use) ix_launch.suffix_table = nullptr;  // (A/B: the same index without its table)
+    if (!options().suffix_table) ix_launch.suffix_table = nullptr;  // (A/B: the same index without its table)
     // code width: the plan's in modes 1 / 2 (its record words), this index's own where the kernel makes the chunks itself
     const int bits = (mode == 1 || mode == 2) ? pl.code_bits : plan_code_bits(ix.wt_sigma);
 #define FMX_COUNT_LAUNCH(BLOCK, MODE, BITS)                                                                           \
-    hipLaunchKernelGGL((k_count<BLOCK, MODE, BITS>), grid__, dim3(BLOCK), (size_t)g_lds_pad_kb * 1024, st, ix_launch, pat, \
-                       off, recs, n, counts, lf, status, range, pl.look_up, pl.sigma, (int)g_steps_executed_only, (int)g_regroup_by_length, recs ? pl.mixed : nullptr, pl.epoch, (int)g_count_halve_uniform, (const int32_t *)nullptr, (uint32_t *)nullptr)
+    hipLaunchKernelGGL((k_count<BLOCK, MODE, BITS>), grid__, dim3(BLOCK), (size_t)options().lds_pad_kb * 1024, st, ix_launch, pat, \
+                       off, recs, n, counts, lf, status, range, pl.look_up, pl.sigma, (int)options().lf_steps_executed_only, (int)options().regroup_by_length, recs ? pl.mixed : nullptr, pl.epoch, (int)options().count_halve_uniform, (const int32_t *)nullptr, (uint32_t *)nullptr)
 #define FMX_COUNT_MODE(MODE)                                                                                       \
     do {                                                                                                           \
-        const int blk__ = g_block;                                                                                 \
+        const int blk__ = options().block;                                                                         \
         const dim3 grid__(grid_for(2 * (int64_t)n, blk__, n_cu));                                                  \
         if (blk__ == 1024 && bits == 8)                                                                            \
             FMX_COUNT_LAUNCH(1024, MODE, 8);                                                                       \
@@ -2745,7 +2540,7 @@ int launch_count(const DevIndex &ix, int n_cu, const uint16_t *pat, const int32_
 #endif
 #if !FMX_COMPACT
     // a planned batch over an expanded image whose superblock headers fit LDS: the lean kernel (option "count_lean" = 0: A/B)
-    if (mode == 1 && g_count_lean && pl.redo_list && pl.redo_count && ix.n_sb <= kSbCacheMax && ix.n_sb <= ix.sb_cache_limit &&
+    if (mode == 1 && options().count_lean && pl.redo_list && pl.redo_count && ix.n_sb <= kSbCacheMax && ix.n_sb <= ix.sb_cache_limit &&
         (!ix_launch.suffix_table || pl.code_bits == ix.suffix_key_bits)) {
         CountLeanArgs a;
         a.hot.base = ix.base;
@@ -2769,16 +2564,16 @@ int launch_count(const DevIndex &ix, int n_cu, const uint16_t *pat, const int32_
         a.tile.suffix_chars = ix.suffix_chars;
         a.tile.suffix_shift = ix.suffix_shift;
         a.tile.suffix_mask = ix.suffix_mask;
-        a.tile.steps_mode = (int)g_steps_executed_only;
+        a.tile.steps_mode = (int)options().lf_steps_executed_only;
         a.tile.mixed = 0;
         a.sbd = ix.sbd;
         a.plan_mixed = pl.mixed;
         a.plan_epoch = pl.epoch;
-        a.regroup = (int)g_regroup_by_length;
-        a.halve_uniform = (int)g_count_halve_uniform;
-        const int blk = g_block;
+        a.regroup = (int)options().regroup_by_length;
+        a.halve_uniform = (int)options().count_halve_uniform;
+        const int blk = options().block;
         const dim3 grid(grid_for(2 * (int64_t)n, blk, n_cu));
-        const size_t lds = (size_t)g_lds_pad_kb * 1024;
+        const size_t lds = (size_t)options().lds_pad_kb * 1024;
 #define FMX_LEAN_LAUNCH(BLOCK, BITS, BYSYM) hipLaunchKernelGGL((k_count_lean<BLOCK, BITS, BYSYM>), grid, dim3(BLOCK), lds, st, a)
 #define FMX_LEAN_SHAPE(BLOCK)                                    \
     do {                                                         \
@@ -2807,7 +2602,7 @@ int launch_count(const DevIndex &ix, int n_cu, const uint16_t *pat, const int32_
         const dim3 redo_grid(n_cu > 0 ? (unsigned)n_cu : 256u);
 #define FMX_REDO_LAUNCH(BLOCK, BITS)                                                                                              \
     hipLaunchKernelGGL((k_count<BLOCK, 4, BITS>), redo_grid, dim3(BLOCK), lds, st, ix_launch, pat, off, (const PlanRec *)nullptr, n, \
-                       counts, lf, status, range, (const int32_t *)nullptr, 0, (int)g_steps_executed_only, 0, (const uint32_t *)nullptr, \
+                       counts, lf, status, range, (const int32_t *)nullptr, 0, (int)options().lf_steps_executed_only, 0, (const uint32_t *)nullptr, \
                        0u, 0, (const int32_t *)pl.redo_list, pl.redo_count)
         if (blk == 1024 && own_bits == 8)
             FMX_REDO_LAUNCH(1024, 8);
@@ -2841,7 +2636,7 @@ int launch_count(const DevIndex &ix, int n_cu, const uint16_t *pat, const int32_
 // bytes of scratch for the walk order of a batch of n patterns (0 = the batch is walked in the caller's order):
 // head (as a plan's, kPlanHeadBytes, zero between uses) | records in walk order [n]
 size_t walk_workspace_bytes(const DevIndex &ix, int32_t n) {
-    const int walk_min = g_walk_order_min;
+    const int walk_min = options().walk_order_min;
     if (walk_min <= 0 || n < walk_min) return 0;
     return kPlanHeadBytes + (size_t)n * sizeof(PlanRec) + 64;
 }
@@ -2857,7 +2652,7 @@ int launch_locate_walk(const DevIndex &ix, int n_cu, const int32_t *range, int32
     const PlanRec *order = nullptr;
     const uint32_t *order_idle = nullptr;
     // (a row table: the hits are gathered, not walked — in the caller's order unless option "rows_order" asks for the walk order)
-    const size_t need = (ix.rows && !g_rows_order.load()) ? 0 : walk_workspace_bytes(ix, n);
+    const size_t need = (ix.rows && !options().rows_order.load()) ? 0 : walk_workspace_bytes(ix, n);
     if (workspace && need != 0 && workspace_bytes >= need && loc_cap > 0) {
         uint8_t *wsb = static_cast<uint8_t *>(workspace);
         uint32_t *ghist = reinterpret_cast<uint32_t *>(wsb);
@@ -2870,7 +2665,7 @@ int launch_locate_walk(const DevIndex &ix, int n_cu, const int32_t *range, int32
         }
         int total_bits = 1;
         while (total_bits < 32 && (1ll << total_bits) <= (long long)ix.length) ++total_bits;
-        const int coarse_bits = total_bits < g_coarse_bits ? total_bits : (int)g_coarse_bits;
+        const int coarse_bits = total_bits < options().coarse_bits ? total_bits : (int)options().coarse_bits;
         const int bins = (1 << coarse_bits) + 1, below = total_bits - coarse_bits;  // (+ the bin of patterns with nothing to locate)
         const int tiles = (n + kTile - 1) / kTile;
         hipLaunchKernelGGL(k_walk_hist, dim3(tiles), dim3(kTileThreads), (size_t)bins * 4, st, range, n, bins, below, taken,
@@ -2879,7 +2674,7 @@ int launch_locate_walk(const DevIndex &ix, int n_cu, const int32_t *range, int32
         hipLaunchKernelGGL(k_plan_scatter<true>, dim3(tiles), dim3(kTileThreads), (size_t)bins * 8, st, nullptr, range, taken,
                            max_matches, n, bins, below, ghist, cursor, ticket, ordered);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
-        if (g_walk_fine)
+        if (options().walk_fine)
             hipLaunchKernelGGL(k_plan_fine, dim3((n + kFineWindow - 1) / kFineWindow), dim3(kFineThreads), 0, st, ordered, n);
         order = ordered;
         order_idle = ticket + 1;
@@ -2895,19 +2690,19 @@ int launch_locate_walk(const DevIndex &ix, int n_cu, const int32_t *range, int32
     // a window directory and many hits per pattern: the ticket-queue form (k_locate_walk_q).  Measured (round 6, profiles/r06_experiments.txt
     // 3): locate(100) of the reference-shaped series 2.47 -> 2.14-2.26 ms; with <= 16 hits per pattern the hand-out's record loads cost
     // more than the idle lanes they save (configs[2] 0.247 -> 0.34 ms, locate(1) 1.09 -> 1.14): those keep the packed form below
-    if (ix.win && g_walk_queue.load() && ix.sample_rate >= 4 && slots >= g_walk_queue_min_slots.load()) {
+    if (ix.win && options().walk_queue.load() && ix.sample_rate >= 4 && slots >= options().walk_queue_min_slots.load()) {
         const int64_t waves = (tickets + 63) / 64;  // a lane per ticket would need this many waves: give each wave `per` lanes' worth
-        int32_t per = g_walk_queue.load();          // tickets per lane and run (option "walk_queue": 0 = off)
+        int32_t per = options().walk_queue.load();          // tickets per lane and run (option "walk_queue": 0 = off)
         const int32_t chunk = 64 * per;
-        int32_t burst = g_walk_burst.load();
+        int32_t burst = options().walk_burst.load();
         if (burst <= 0) burst = ix.sample_rate / 4 > 2 ? ix.sample_rate / 4 : 2;
         (void)waves;
         FMX_DISPATCH_FORM(k_locate_walk_q, ix, (tickets + per - 1) / per, ix, range, n, max_matches, locs, loc_cap, slots, found, lf, status, taken, order,
                      order_idle, set_locs, set_base, chunk, burst);
         return (int)hipGetLastError();
     }
-    if (ix.win && g_walk_pack.load() && ix.sample_rate >= 8) {  // a window directory: the packed form (k_locate_walk_c)
-        const int packings = g_walk_pack.load() >= 3 ? 3 : 2;
+    if (ix.win && options().walk_pack.load() && ix.sample_rate >= 8) {  // a window directory: the packed form (k_locate_walk_c)
+        const int packings = options().walk_pack.load() >= 3 ? 3 : 2;
         FMX_DISPATCH_FORM(k_locate_walk_c, ix, tickets, ix, range, n, max_matches, locs, loc_cap, slots, found, lf, status, taken, order, order_idle,
                      set_locs, set_base, packings);
         return (int)hipGetLastError();
@@ -2981,7 +2776,7 @@ int launch_rrr_access(const DevIndex &ix, int n_cu, const int32_t *pos, int32_t 
 
 // bytes of scratch for taking n extractUntilBoundary queries by text position (0 = the caller's order): head | records [n]
 size_t boundary_order_bytes(const DevIndex &ix, int64_t n) {
-    const int order_min = g_boundary_order_min;
+    const int order_min = options().boundary_order_min;
     if (order_min <= 0 || n < order_min || n > INT32_MAX) return 0;
     return kPlanHeadBytes + (size_t)n * sizeof(PlanRec) + 64;
 }
@@ -2999,7 +2794,7 @@ static int launch_position_order(const DevIndex &ix, const int32_t *positions, i
     }
     int total_bits = 1;
     while (total_bits < 32 && (1ll << total_bits) <= (long long)ix.length) ++total_bits;
-    const int coarse_bits = total_bits < g_coarse_bits ? total_bits : (int)g_coarse_bits;
+    const int coarse_bits = total_bits < options().coarse_bits ? total_bits : (int)options().coarse_bits;
     const int bins = (1 << coarse_bits) + 1, below = total_bits - coarse_bits;
     const int tiles = (n + kTile - 1) / kTile;
     hipLaunchKernelGGL(k_walk_hist, dim3(tiles), dim3(kTileThreads), (size_t)bins * 4, st, nullptr, n, bins, below, nullptr, 0, ghist,
@@ -3038,9 +2833,9 @@ struct BoundaryShape {
 };
 static BoundaryShape boundary_shape() {
     BoundaryShape b;
-    b.block = g_block;
-    b.accel = g_boundary_accel;
-    b.group = b.accel ? (int)g_boundary_group : 0;  // 0 = one lane, literal/serial forms
+    b.block = options().block;
+    b.accel = options().boundary_accel;
+    b.group = b.accel ? (int)options().boundary_group : 0;  // 0 = one lane, literal/serial forms
     return b;
 }
 static size_t boundary_bytes_for_grid(const DevIndex &ix, int blocks, const BoundaryShape &b) {
@@ -3087,17 +2882,17 @@ int launch_extract_boundary(const DevIndex &ix, int n_cu, const int32_t *from, i
                             ? static_cast<uint16_t *>(workspace)
                             : nullptr;
     const int G = scratch ? shape.group : 0;
-    const int pair_walks = g_boundary_first_fill != 0;
+    const int pair_walks = options().boundary_first_fill != 0;
     const dim3 grid(scratch ? blocks_accel : grid_for(n, blk, n_cu));
     // the group kernel's redo list lives behind the windows; its count is cleared in front of every launch
     int32_t *redo = (scratch && G > 0) ? reinterpret_cast<int32_t *>(static_cast<uint8_t *>(workspace) + ((windows_bytes + 15) & ~(size_t)15)) : nullptr;
-    // The NARROW first round (option "boundary_narrow", default 0: off, see g_boundary_narrow; the default group of 4, sample rates the marked replay serves,
+    // The NARROW first round (option "boundary_narrow", default 0: off, see its note in fmx_options.cpp; the default group of 4, sample rates the marked replay serves,
     // batches of "boundary_narrow_min" queries or more): the walks are what this costs (one sector per LF-step, at the chip's
     // random-sector rate) and the wide form fetches 8 sample intervals per query where a line needs 3.1 — so every query first
     // gets the two intervals on each side of `from` (G = 2, a lane's two walks interleaved: HALF the LF-steps), and only a query
     // whose line does not end inside them (about one in seven of configs[3]) takes the wide form, off a list, in a launch behind.
     int32_t *todo = nullptr;
-    if (redo && G == 4 && pair_walks && g_boundary_narrow && ix.sample_rate <= 64 && n >= g_boundary_narrow_min &&
+    if (redo && G == 4 && pair_walks && options().boundary_narrow && ix.sample_rate <= 64 && n >= options().boundary_narrow_min &&
         workspace_bytes >= windows_bytes + 2 * boundary_redo_bytes(n) + 16) {
         todo = redo;
         redo = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(todo) + ((boundary_redo_bytes(n) + 15) & ~(size_t)15));
@@ -3135,7 +2930,7 @@ int launch_extract_boundary(const DevIndex &ix, int n_cu, const int32_t *from, i
 // 0.660, and keep the one that looks at ix.win itself: tools/boundary_probe.py, round 6)
 #define FMX_LAUNCH_GROUP_MODE(BLK, GG, MODE)                                                                             \
     do {                                                                                                                \
-        if (GG == 4 && MODE == 0 && g_boundary_rounds && pair_walks && !todo)                                            \
+        if (GG == 4 && MODE == 0 && options().boundary_rounds && pair_walks && !todo)                                   \
             hipLaunchKernelGGL((k_extract_boundary_group<BLK, ((GG == 4 && MODE == 0) ? 4 : 1), 0, kWinAsk, false,       \
                                                          (GG == 4 && MODE == 0)>),                                      \
                                grid, dim3(BLK), 0, st, ix, from, n, boundary, dst, dst_len, offset, out_len, lf, status, aux, scratch, \

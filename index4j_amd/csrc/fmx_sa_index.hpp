@@ -69,7 +69,6 @@ SaIndex *sa_of(const fmx_index *idx);
 int api_fail(int code, const std::string &msg);
 
 // fmx_sa_query.hip
-int sa_set_option(const char *name, int value);  // 0 taken, -1 bad value, 1 not an option of these kernels
 int sa_fence_settings(int32_t n, int32_t *n_fences, int32_t *shift, int32_t *chars);  // from the options; -1: too big for LDS
 int launch_sa_fences(const SaView &v, uint16_t *keys, uint8_t *lens, void *stream);
 // per pattern: counts[i] = right - left (nullable), left[i] and found[i] = min(count, max_matches) (both nullable)

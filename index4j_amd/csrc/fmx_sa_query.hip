@@ -10,25 +10,19 @@
 // `found`, so that neighbouring lanes read neighbouring entries.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <cstring>
-
 #include <rocprim/device/device_scan.hpp>
 
+#include "fmx_options.hpp"
 #include "fmx_sa_index.hpp"
 
 namespace fmx {
 namespace {
 
-std::atomic<int> g_sa_block{512};           // option "block" (shared with the FM kernels)
-std::atomic<int> g_sa_groups_per_cu{16};    // option "groups_per_cu" (likewise)
-std::atomic<int> g_sa_fences{4096};         // option "sa_fences": most fences (a power of two; 0 = no fence table)
-std::atomic<int> g_sa_fence_chars{8};       // option "sa_fence_chars": K
 constexpr size_t kFenceLdsMax = 64 * 1024;  // fence keys staged per workgroup
 
 int grid_for(int64_t lanes, int block, int n_cu) {
     int64_t blocks = (lanes + block - 1) / block;
-    const int64_t cap = (int64_t)n_cu * g_sa_groups_per_cu;  // a few rounds of workgroups per CU, grid-stride the rest
+    const int64_t cap = (int64_t)n_cu * options().groups_per_cu;  // a few rounds of workgroups per CU, grid-stride the rest
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     return (int)blocks;
@@ -95,30 +89,8 @@ __global__ void k_bwt_gather(const int32_t *__restrict__ sa, const uint16_t *__r
 
 }  // namespace
 
-int sa_set_option(const char *name, int value) {
-    if (!strcmp(name, "block")) {  // validated (and answered) by the FM kernels' set_option as well
-        if (value == 512 || value == 1024) g_sa_block = value;
-        return 1;
-    }
-    if (!strcmp(name, "groups_per_cu")) {
-        if (value >= 1 && value <= 64) g_sa_groups_per_cu = value;
-        return 1;
-    }
-    if (!strcmp(name, "sa_fences")) {  // applies to suffix arrays made resident afterwards
-        if (value < 0 || value > 32768 || (value & (value - 1))) return -1;
-        g_sa_fences = value;
-        return 0;
-    }
-    if (!strcmp(name, "sa_fence_chars")) {
-        if (value < 1 || value > 16) return -1;
-        g_sa_fence_chars = value;
-        return 0;
-    }
-    return 1;
-}
-
 int sa_fence_settings(int32_t n, int32_t *n_fences, int32_t *shift, int32_t *chars) {
-    const int32_t most = g_sa_fences, k = g_sa_fence_chars;
+    const int32_t most = options().sa_fences, k = options().sa_fence_chars;
     int32_t s = 0;
     while (most > 0 && (((int64_t)n + (1ll << s) - 1) >> s) > most) ++s;
     *n_fences = most > 0 ? (int32_t)(((int64_t)n + (1ll << s) - 1) >> s) : 0;
@@ -138,7 +110,7 @@ int launch_sa_search(const SaView &v, const uint16_t *keys, int n_cu, const uint
                      int32_t n, int32_t max_matches, int32_t *counts, int32_t *left, int32_t *found, void *stream) {
     if (n <= 0) return 0;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int blk = g_sa_block;
+    const int blk = options().block;
     const dim3 grid(grid_for(n, blk, n_cu));
     const size_t lds = ((size_t)v.n_fences * v.fence_chars * 2 + 15) / 16 * 16;
     if (blk == 1024)
@@ -166,7 +138,7 @@ int launch_sa_locate_copy(const SaView &v, int n_cu, const int32_t *left, const 
     size_t tmp_bytes = scratch_bytes - ((size_t)n * 4 + 255) / 256 * 256;
     hipError_t e = rocprim::inclusive_scan(tmp, tmp_bytes, found, incl, (size_t)n, rocprim::plus<int32_t>(), st);
     if (e != hipSuccess) return (int)e;
-    const int blk = g_sa_block;
+    const int blk = options().block;
     const dim3 grid(grid_for((int64_t)n * max_matches, blk, n_cu));
     if (blk == 1024)
         hipLaunchKernelGGL(k_sa_locate_copy<1024>, grid, dim3(1024), 0, st, v.sa, left, found, incl, n, max_matches, locs);

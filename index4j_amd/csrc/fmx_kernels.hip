@@ -1680,9 +1680,13 @@ FMX_KERNEL(kBlock) void k_rrr_access(DevIndex ix, const int32_t *__restrict__ po
 //   2. k_plan_scatter: every workgroup scans the histogram itself (no scan kernel), reserves its share of each
 //      bin with one atomic and writes the pattern indices in bucket order; the last workgroup to finish zeroes
 //      the histogram and the cursors for the next plan on this stream (no memset launch);
-//   3. the fine order where it matters — which 32 patterns share a wave — is made inside k_count: a counting
-//      sort of each workgroup's 256 records on 10 key bits, in LDS.
-// Two short kernels (round 1: memset + four kernels with a tile-local radix sort, 76 us at 1 M patterns).
+//   3. k_plan_fine: the fine order where it matters — which patterns share a wave —, in place: every window of 1,024
+//      consecutive records of the bucket order is ranked by the records' fine bins (bits 22..31 of PlanRec.m as
+//      k_plan_codes left them: 10 key bits ending 8 below the coarse bits) with a counting sort in LDS, and those
+//      bits are cleared.  A record never leaves its window.  Runs for the code key, and for an SA-row key only
+//      under plan_fine = 2.
+// Two or three short kernels (round 1: memset + four kernels with a tile-local radix sort, 76 us at 1 M patterns).
+// tests/test_gpu_plan_order.py reads the records back and pins this contract against tests/plan_model.py.
 
 // (dynamic LDS of k_plan_codes with the order-1 table staged behind the histogram: order1_lds_bytes / kPlanCodesLdsMax in
 // fmx_device.hpp — the launcher, the kernel and the table's builder decide alike)
@@ -1737,8 +1741,11 @@ __device__ __forceinline__ Quad plan_record(const DevIndex &ix, const PlanTables
         // strings alone (a few hundred slots: cache-resident) — the row range of the suffix's first two characters,
         // narrowed character by character by the share the next character has after its predecessor (an order-1 chain:
         // row ~ s(xy) + |xy| * (F(z|y) + P(z|y) * (F(u|z) + ...)), F / P = where the two-character string yz starts inside
-        // y's rows and how much of them it takes).  The estimate is monotone in the suffix's lexicographic order, which
-        // is all the bucket pass needs; results never depend on it.
+        // y's rows and how much of them it takes).  The estimate is monotone in the suffix's lexicographic order (up to
+        // float32 rounding), which is all the bucket pass needs; results never depend on it.  One exception: a suffix
+        // whose FIRST character is absent from the alphabet has no rows of its own — the table cannot answer it and
+        // k_count starts from the last character —, so its key is the last character's first row, C[last], as if the
+        // suffix were that one character; a suffix with an absent character further in stays at the rows reached so far.
         key = 0;
         constexpr uint32_t cmask = (1u << kCodeBits) - 1u;
         const int32_t c_last = (int32_t)(word & cmask);

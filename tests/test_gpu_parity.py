@@ -987,8 +987,8 @@ def test_the_plan_stage_as_one_launch_gives_the_same_answers_also_when_its_barri
                     assert (found == want[1]).all() and (st2 == want[2]).all() and (locs[live] == want[0][live]).all()
             fm.close()
     finally:
-        L.fmx_set_option(b"plan_fused", 1)
-        L.fmx_set_option(b"plan_spin_limit", 4096)
+        L.fmx_set_option(b"plan_fused", ia._lib.ENV_OPTIONS.get("plan_fused", 0))  # (the library's default: two kernels)
+        L.fmx_set_option(b"plan_spin_limit", ia._lib.ENV_OPTIONS.get("plan_spin_limit", 4096))
 
 
 def test_api_edge_cases():

@@ -191,6 +191,19 @@ int fmx_locate_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *p
                      int32_t max_matches, int32_t *locs, int32_t loc_cap, int32_t *found, int32_t *lf_steps,
                      int32_t *status);
 
+/* int locate(char[] pattern, int[] locations) FM:487-489, "all occurrences" (FM:487-552), batched and PACKED — the host form of
+ * fmx_locate_all_ranges_dev + fmx_locate_all_fill_dev (below: the layout, max_matches, what lf_steps / status hold).
+ * host buffers, synchronous: hit_off = n + 1 int64 (out); *locs = hit_off[n] ints owned by the library until
+ * fmx_free_buffer((uint8_t *)*locs) (NULL when there are no hits); lf_steps / status nullable, n ints.
+ * The hits of pattern i are (*locs)[hit_off[i] .. hit_off[i + 1]), in the order locate() stores them.  Device scratch is bounded:
+ * the hits come down in windows of 2^24.  n == 0: FMX_OK, hit_off[0] = 0, *locs = NULL.  FMX_E_NOMEM if the result cannot be
+ * allocated (nothing is left behind; *locs = NULL on every failure); FMX_E_ARG for null or negative arguments, pattern offsets
+ * that start below 0 or decrease, and a SuffixArray, RrrVector or stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that
+ * is not resident.  When every pattern has a few hits at most, fmx_locate_batch with a small loc_cap is the faster form (it
+ * orders the walks; README). */
+int fmx_locate_all_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t max_matches,
+                         int64_t *hit_off, int32_t **locs, int32_t *lf_steps, int32_t *status);
+
 /* int extract(int start, int stop, char[] destination, int offset) FM:564-608.  dst is n rows of
  * dst_len chars (row i = the `destination` array of query i, in/out); out_len[i] = return value. */
 int fmx_extract_batch(const fmx_index *idx, const int32_t *start, const int32_t *stop, int32_t n, uint16_t *dst,
@@ -241,6 +254,32 @@ int fmx_batch_policy(const fmx_index *idx, int kind, int64_t n);
 int fmx_locate_batch_dev(const fmx_index *idx, const uint16_t *d_pat, const int32_t *d_pat_off, int32_t n,
                          int32_t max_matches, int32_t *d_locs, int32_t loc_cap, int32_t *d_found,
                          int32_t *d_lf_steps, int32_t *d_status, int32_t *d_range_ws /* 2*n ints */, void *stream);
+/* int locate(char[] pattern, int[] locations) FM:487-489 — "all occurrences", the loop of FM:526-548 without a limit (FM:487-552)
+ * — for a batch, PACKED: one offsets array of n + 1 entries and one array of positions, so that a batch that mixes patterns of
+ * one hit with a pattern of millions takes the memory of its hits (fmx_locate_batch's rows would take n x the largest count), and
+ * lanes are handed to HITS, not to patterns: a single pattern with 10^6 hits is spread over the whole device.  Two stages, so
+ * that a device caller can allocate d_locs between them:
+ * stage 1: the range search of FM:506-523 for the batch, and the packed layout of its hits.
+ * d_hit_off[i] = number of hits of patterns 0 .. i-1 (int64; d_hit_off[0] = 0, d_hit_off[n] = all hits of the batch), where
+ * pattern i has min(count, max_matches) hits for max_matches > 0 and count hits otherwise (FM:544-546: -1 and 0 never stop).
+ * d_lf_steps / d_status (nullable) as fmx_locate_batch_dev's range pass leaves them (an empty pattern: FMX_ST_JAVA_AIOOBE, no hits).
+ * d_range_ws = 2*n ints, handed unchanged to stage 2.  Asynchronous on `stream`; nothing is synchronised.
+ * n == 0: d_hit_off[0] = 0 (an asynchronous memset).  FMX_E_ARG for null or negative arguments and for a SuffixArray, RrrVector
+ * or stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident.  Scratch per (index, stream), like the other
+ * device forms.  v1: the patterns are taken in the caller's order after the count plan (no walk-order stage), one index, one
+ * device (no segment sets, no *_multi form). */
+int fmx_locate_all_ranges_dev(const fmx_index *idx, const uint16_t *d_pat, const int32_t *d_pat_off, int32_t n,
+                              int32_t max_matches, int64_t *d_hit_off, int32_t *d_lf_steps, int32_t *d_status,
+                              int32_t *d_range_ws, void *stream);
+/* stage 2: hits [first_hit, first_hit + n_hits) of the packed order, cut at d_hit_off[n]: d_locs[t - first_hit] = what the reference's
+ * locate() stores for hit t - d_hit_off[p] of its pattern p (SA rows start+1.. in order, FM:527-547).  Entries of d_locs for hits
+ * beyond d_hit_off[n] keep the caller's values.  Walk LF-steps are ADDED to d_lf_steps[p], walk statuses OR-ed into d_status[p]
+ * (both nullable): windows that tile the hits once give fmx_locate_batch's totals.  d_lf_steps stays int32 per pattern, like
+ * fmx_locate_batch's: a pattern whose walks pass 2^31 steps wraps, there as here.  The kernel reads d_hit_off[n] itself (the
+ * grid is sized from n_hits): no host synchronisation; d_locs must hold min(n_hits, d_hit_off[n] - first_hit) ints. */
+int fmx_locate_all_fill_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_off, const int32_t *d_range_ws,
+                            int64_t first_hit, int64_t n_hits, int32_t *d_locs, int32_t *d_lf_steps, int32_t *d_status,
+                            void *stream);
 int fmx_extract_batch_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n,
                           uint16_t *d_dst, int32_t dst_len, int32_t offset, int32_t *d_out_len,
                           int32_t *d_lf_steps, int32_t *d_status, void *stream);

@@ -139,6 +139,38 @@ public:
         for (int s : status) detail::raise_for_status(s);
         return found;
     }
+    // every hit of every pattern, packed (fmx_locate_all_batch; FM:487-552): the hits of pattern i are
+    // locations[offsets[i] .. offsets[i + 1]), in the order locate() stores them; maxMatches > 0 cuts each pattern's hits there
+    struct Hits {
+        std::vector<int64_t> offsets;
+        std::vector<int32_t> locations;
+    };
+    Hits locateAllBatch(const std::vector<std::u16string> &patterns, int maxMatches = -1) const {
+        std::vector<uint16_t> chars;
+        std::vector<int32_t> off;
+        pack(patterns, chars, off);
+        const int32_t n = (int32_t)patterns.size();
+        Hits hits;
+        hits.offsets.assign((size_t)n + 1, 0);
+        std::vector<int32_t> status(patterns.size());
+        int32_t *buf = nullptr;
+        detail::check(fmx_locate_all_batch(h_, chars.data(), off.data(), n, maxMatches, hits.offsets.data(), &buf, nullptr,
+                                           status.data()),
+                      "fmx_locate_all_batch");
+        try {
+            if (buf) hits.locations.assign(buf, buf + hits.offsets[(size_t)n]);
+        } catch (...) {
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+            throw;
+        }
+        fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+        for (int s : status) detail::raise_for_status(s);
+        return hits;
+    }
+    std::vector<int32_t> locateAll(const std::u16string &pattern) const {  // FM:487-489, the array made here
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        return locateAllBatch({pattern}, -1).locations;
+    }
 
     // locate, then extract(loc, min(getInputLength(), loc + extractLength), row, 0) per hit, both on the device:
     // the composite the reference times in locateAndExtractBenchmark (FmIndexThroughputBenchmark.java:231-249).

@@ -19,6 +19,7 @@
 #include <condition_variable>
 #include <deque>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -57,6 +58,7 @@ FMX_DISPATCH_FN(launch_count)
 FMX_DISPATCH_FN(count_workspace_bytes)
 FMX_DISPATCH_FN(launch_locate_walk)
 FMX_DISPATCH_FN(walk_workspace_bytes)
+FMX_DISPATCH_FN(launch_locate_all)
 FMX_DISPATCH_FN(launch_extract)
 FMX_DISPATCH_FN(launch_extract_boundary)
 FMX_DISPATCH_FN(boundary_workspace_bytes)
@@ -243,6 +245,7 @@ int require_device(const fmx_index *idx, bool rrr_handle = false) {
 }
 
 constexpr int kWsPlan = 0, kWsBoundary = 1, kWsWalk = 2, kWsSegRange = 3, kWsSegCounts = 4;  // (kWsWalk: the walk order of locate, a plan-like head; kWsSegRange: a segment set's second {found, status, range} buffers)
+constexpr int kWsHitCounts = 5, kWsHitWindow = 6;  // fmx_locate_all_*: the hit counts and the scan's scratch; the host form's window of packed hits
 
 // the side stream of `stream` with at least n_events events (nullptr: could not be made — the caller stays on one stream)
 fmx_index::SideLane *side_lane(const fmx_index *idx, void *stream, size_t n_events) {
@@ -1634,6 +1637,63 @@ int fmx_locate_batch_dev(const fmx_index *idx, const uint16_t *d_pat, const int3
     });
 }
 
+// ---- "all occurrences", packed (FM:487-552) ----------------------------------------------------
+// an FM-index handle (not a SuffixArray, RrrVector or stand-alone wavelet tree), resident
+static int require_fm_device(const fmx_index *idx) {
+    const int rc = require_device(idx);
+    if (rc && rc != FMX_E_NO_DEVICE) return rc;
+    if (idx->wavelet_only || (idx->d_blob && idx->hdr.kind != 0)) return fail(FMX_E_ARG, "not an FmIndex handle");
+    return rc;
+}
+
+static int locate_all_ranges_impl(const fmx_index *idx, const uint16_t *d_pat, const int32_t *d_pat_off, int32_t n, int32_t max_matches,
+                                  int64_t *d_hit_off, int32_t *d_lf_steps, int32_t *d_status, int32_t *d_range_ws, Scratch &scratch) {
+    if (!idx || n < 0 || !d_hit_off || (n > 0 && (!d_pat_off || !d_range_ws))) return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(scratch.stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_hit_off, 0, sizeof(int64_t), st));
+        return FMX_OK;
+    }
+    fmx::CountPlan plan;
+    rc = plan_order(idx, d_pat, d_pat_off, n, scratch, &plan);
+    if (rc) return rc;
+    // (the range pass wants a `counts` output: the first n ints of d_hit_off take it; the scan below overwrites them afterwards)
+    int e = k_launch_count(idx, idx->dev, idx->n_cu, d_pat, d_pat_off, &plan, false, n, reinterpret_cast<int32_t *>(d_hit_off), d_lf_steps,
+                           d_status, d_range_ws, st);
+    if (e) return fail(FMX_E_HIP, std::string("k_count launch: ") + hipGetErrorString((hipError_t)e));
+    void *ws = nullptr;
+    const size_t ws_bytes = fmx::hit_offsets_scratch_bytes(n);
+    rc = scratch.get(kWsHitCounts, ws_bytes, &ws);
+    if (rc) return rc;
+    e = fmx::launch_hit_offsets(d_range_ws, n, max_matches, d_hit_off, ws, ws_bytes, st);
+    if (e) return fail(FMX_E_HIP, std::string("hit offsets: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+}
+
+int fmx_locate_all_ranges_dev(const fmx_index *idx, const uint16_t *d_pat, const int32_t *d_pat_off, int32_t n, int32_t max_matches,
+                              int64_t *d_hit_off, int32_t *d_lf_steps, int32_t *d_status, int32_t *d_range_ws, void *stream) {
+    return guarded([&]() -> int {
+    Scratch scratch(idx, stream, false);
+    return locate_all_ranges_impl(idx, d_pat, d_pat_off, n, max_matches, d_hit_off, d_lf_steps, d_status, d_range_ws, scratch);
+    });
+}
+
+int fmx_locate_all_fill_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_off, const int32_t *d_range_ws, int64_t first_hit,
+                            int64_t n_hits, int32_t *d_locs, int32_t *d_lf_steps, int32_t *d_status, void *stream) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || first_hit < 0 || n_hits < 0 || !d_hit_off || (n > 0 && !d_range_ws) || (n > 0 && n_hits > 0 && !d_locs))
+        return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_range_ws, d_hit_off, n, first_hit, n_hits, d_locs, d_lf_steps, d_status,
+                                static_cast<hipStream_t>(stream));
+    if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+    });
+}
+
 int fmx_extract_batch_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n,
                           uint16_t *d_dst, int32_t dst_len, int32_t offset, int32_t *d_out_len, int32_t *d_lf_steps,
                           int32_t *d_status, void *stream) {
@@ -2698,6 +2758,81 @@ int fmx_locate_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *p
     if (lf_steps) HIP_TRY(hipMemcpyAsync(lf_steps, d_lf.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return FMX_OK;
+    });
+}
+
+// The host form of "all occurrences": stage 1, ONE 8-byte copy and wait for the batch's total, the result malloc'ed to that size
+// (fmx_free_buffer is free), then stage 2 in windows of kLocateAllWindow hits of device scratch, each copied straight into its
+// place in the result.
+constexpr int64_t kLocateAllWindow = (int64_t)1 << 24;  // 64 MiB of positions
+int fmx_locate_all_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t max_matches,
+                         int64_t *hit_off, int32_t **locs, int32_t *lf_steps, int32_t *status) {
+    return guarded([&]() -> int {
+    if (locs) *locs = nullptr;
+    if (!idx || n < 0 || !hit_off || !locs || (n > 0 && !pat_off)) return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if (n == 0) {
+        hit_off[0] = 0;
+        return FMX_OK;
+    }
+    HIP_TRY(hipSetDevice(idx->device));
+    rc = check_offsets(pat_off, n);
+    if (rc) return rc;
+    const size_t chars = (size_t)(pat_off[n] > 0 ? pat_off[n] : 0), first = first_char(pat_off);
+    if (chars > first && !pat) return fail(FMX_E_ARG, "bad arguments");
+    DevBuf d_pat, d_off, d_hit, d_lf, d_st, d_ws;
+    HIP_TRY(d_pat.alloc(chars * 2 + 8));
+    HIP_TRY(d_off.alloc((size_t)(n + 1) * 4));
+    HIP_TRY(d_hit.alloc((size_t)(n + 1) * 8));
+    if (lf_steps) HIP_TRY(d_lf.alloc((size_t)n * 4));
+    if (status) HIP_TRY(d_st.alloc((size_t)n * 4));
+    HIP_TRY(d_ws.alloc((size_t)n * 8));
+    PipeStreams *ps = nullptr;
+    rc = pipe_streams(idx->device, &ps);
+    if (rc) return rc;
+    hipStream_t st = ps->s[1];
+    Scratch scratch(idx, st, true);
+    struct Result {  // what leaves this function first waits for the stream, THEN the per-call blocks (declared above) return to their
+        hipStream_t s;  // cache; a result that was not handed over is freed
+        int32_t *p = nullptr;
+        ~Result() {
+            (void)hipStreamSynchronize(s);
+            free(p);
+        }
+    } result{st};
+    if (chars > first) HIP_TRY(hipMemcpyAsync(d_pat.as<uint16_t>() + first, pat + first, (chars - first) * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off.p, pat_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
+    int32_t *dlf = lf_steps ? d_lf.as<int32_t>() : nullptr, *dst_ = status ? d_st.as<int32_t>() : nullptr;
+    rc = locate_all_ranges_impl(idx, d_pat.as<uint16_t>(), d_off.as<int32_t>(), n, max_matches, d_hit.as<int64_t>(), dlf, dst_,
+                                d_ws.as<int32_t>(), scratch);
+    if (rc) return rc;
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_hit.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (total > 0) {
+        if ((uint64_t)total > SIZE_MAX / 4) return fail(FMX_E_NOMEM, "the batch's hits do not fit this host's address space");
+        result.p = static_cast<int32_t *>(malloc((size_t)total * 4));
+        if (!result.p) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(total) + " hits");
+        const int64_t window = total < kLocateAllWindow ? total : kLocateAllWindow;
+        void *d_win = nullptr;
+        rc = scratch.get(kWsHitWindow, (size_t)window * 4, &d_win);
+        if (rc) return rc;
+        for (int64_t at = 0; at < total; at += window) {
+            const int64_t hits = total - at < window ? total - at : window;
+            int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_ws.as<int32_t>(), d_hit.as<int64_t>(), n, at, hits,
+                                        static_cast<int32_t *>(d_win), dlf, dst_, st);
+            if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
+            HIP_TRY(hipMemcpyAsync(result.p + at, d_win, (size_t)hits * 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(hit_off, d_hit.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (lf_steps) HIP_TRY(hipMemcpyAsync(lf_steps, d_lf.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *locs = result.p;
+    result.p = nullptr;
     return FMX_OK;
     });
 }

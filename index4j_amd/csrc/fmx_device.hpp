@@ -2015,6 +2015,40 @@ FMX_HD int32_t fm_rows_gather(const DevIndex &ix, const uint16_t *inv, int32_t s
     return steps;
 }
 
+// THE PACKED LAYOUT of "all occurrences" (fmx_locate_all_*; FM:487-552): hit_off[p] = hits of patterns 0 .. p - 1, n + 1 entries,
+// never decreasing.  Hit t of the packed order belongs to the LAST p with hit_off[p] <= t (a pattern without hits has
+// hit_off[p] == hit_off[p + 1]: a run of equal entries ends in the pattern that holds the hit).
+// fm_locate_all_hits: how many hits pattern [start, end) has in that layout (FM:544-546: maxMatches -1 and 0 never stop).
+FMX_HD int64_t fm_locate_all_hits(int32_t start, int32_t end, int32_t max_matches) {
+    const int64_t hits = start < end ? (int64_t)end - start : 0;
+    return (max_matches > 0 && hits > max_matches) ? max_matches : hits;
+}
+// fm_hit_pattern: the last i in [0, count) with off[i] <= t, for off[0] <= t (count >= 1).  `off` is a slice of hit_off — in
+// global memory, or a workgroup's copy of it in LDS; ceil(log2(count)) dependent loads.
+FMX_HD int32_t fm_hit_pattern(const int64_t *off, int32_t count, int64_t t) {
+    int32_t lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (off[mid] <= t)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+// hits of one tile of k_locate_all, and the entries of hit_off a workgroup keeps in LDS for it (16 KiB): a tile whose patterns
+// [p_lo, p_hi] are more than that — thousands of patterns without hits among its own — searches hit_off where it lies, bounded
+// by that slice.  1,024 hits: one or two per lane, and a pattern of 10^6 hits is a thousand tiles.
+constexpr int32_t kLocateAllTile = 1024;
+constexpr int32_t kLocateAllSlice = 2048;
+// One lane's hit t of the tile whose patterns are [p_lo, p_hi]: its pattern and its number inside that pattern.  slice =
+// hit_off[p_lo ..] (LDS copy or hit_off + p_lo itself), slice_count = p_hi - p_lo + 1.
+FMX_HD int32_t fm_locate_all_resolve(const int64_t *slice, int32_t slice_count, int32_t p_lo, int64_t t, int32_t &k) {
+    const int32_t i = fm_hit_pattern(slice, slice_count, t);
+    k = (int32_t)(t - slice[i]);
+    return p_lo + i;
+}
+
 // up to four characters of one aligned 8-byte group of a destination row (mask: which of them): one store when all four are there
 FMX_HD void fm_flush_chars(uint16_t *group_at, uint64_t group, uint32_t mask) {
     if (mask == 0xfu) {

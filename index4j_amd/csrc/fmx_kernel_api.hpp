@@ -31,6 +31,9 @@ size_t walk_workspace_bytes(const fmx::DevIndex &ix, int32_t n);
 int launch_locate_walk(const fmx::DevIndex &ix, int n_cu, const int32_t *range, int32_t n, int32_t max_matches, int32_t *locs,
                        int32_t loc_cap, int32_t *found, int32_t *lf, int32_t *status, const int32_t *taken, void *workspace,
                        size_t workspace_bytes, bool head_is_zero, hipStream_t st, int64_t *set_locs, int64_t set_base);
+// "all occurrences", packed: hits [first_hit, first_hit + n_hits) of the layout hit_off describes (n + 1 entries), cut at hit_off[n]
+int launch_locate_all(const fmx::DevIndex &ix, int n_cu, const int32_t *range, const int64_t *hit_off, int32_t n, int64_t first_hit,
+                      int64_t n_hits, int32_t *locs, int32_t *lf, int32_t *status, hipStream_t st);
 
 // extract, extractUntilBoundary
 int launch_extract(const fmx::DevIndex &ix, int n_cu, const int32_t *start, const int32_t *stop, int64_t n, uint16_t *dst,

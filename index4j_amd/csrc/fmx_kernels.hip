@@ -3,6 +3,7 @@
 //   k_count            FmIndex.count            FM:455-474   two lanes per pattern (start / end of the SA interval)
 //   k_locate_walk      FmIndex.locate           FM:526-548   one lane per (pattern, hit): LF-walk to a sampled row
 //   k_locate_rows      ... over a row table     FM:526-548   a group of lanes per pattern: the hits gathered, no LF-step (option locate_rows)
+//   k_locate_all       ... all occurrences      FM:487-552   lanes handed to the hits of the whole batch, packed over hit_off (fmx_locate_all_*)
 //   k_extract          FmIndex.extract          FM:564-608   one lane per query
 //   k_extract_boundary extractUntilBoundary{,Left,Right} FM:640-922  one lane per query
 //
@@ -1231,6 +1232,83 @@ __global__ __launch_bounds__(kBlock) void k_locate_rows(DevIndex ix, const int32
         }
         if (status && status_out) atomicOr(&status_out[p], status);
     }
+}
+
+// k_locate_all (fmx_locate_all_*; FM:487-552, "all occurrences"): the hits of the WHOLE batch, packed over hit_off (n + 1 entries,
+// fmx_device.hpp), lanes handed to HITS.  A workgroup takes tiles of kLocateAllTile consecutive packed hits of the window
+// [first_hit, first_hit + n_hits), cut at hit_off[n], in a grid-stride loop; lane i of a tile takes hit i (+ kBlock): adjacent
+// lanes, adjacent hits — adjacent SA rows of one pattern, i.e. one sector of row-table words for 16 lanes, or neighbouring walks.
+// The tile's patterns [p_lo, p_hi] are searched once (every lane the same two searches: the loads are broadcasts), their
+// hit_off entries staged in LDS where they fit kLocateAllSlice, and each lane resolves its hit inside that slice.  One hit is
+// fm_locate_hit / fm_rows_hit as k_locate_walk / k_locate_rows run it.  LF-steps are folded over the lanes of a wave that
+// hold the same pattern (they are neighbours) before one atomicAdd; the patterns are taken in the caller's order (no walk
+// order: a heavy pattern's tiles are already sorted by row).
+template <int kBlock, int kWin, bool kRows>
+__device__ __forceinline__ void locate_all_tiles(const DevIndex &ix, const uint16_t *inv, int64_t *s_off, const int32_t *__restrict__ range,
+                                                 const int64_t *__restrict__ hit_off, int32_t n, int64_t first_hit, int64_t n_hits,
+                                                 int32_t *__restrict__ locs, int32_t *__restrict__ lf_steps,
+                                                 int32_t *__restrict__ status_out) {
+    static_assert(kLocateAllTile % kBlock == 0, "every lane of a workgroup runs the same number of rounds per tile");
+    const int64_t total = hit_off[n];
+    if (first_hit >= total) return;
+    const int64_t last = n_hits < total - first_hit ? first_hit + n_hits : total;  // (no first_hit + n_hits beyond 2^63)
+    const int lane = threadIdx.x & 63;
+    for (int64_t tile = first_hit + (int64_t)blockIdx.x * kLocateAllTile; tile < last; tile += (int64_t)gridDim.x * kLocateAllTile) {
+        const int64_t tile_last = (last - tile < kLocateAllTile ? last : tile + kLocateAllTile) - 1;
+        const int32_t p_lo = fm_hit_pattern(hit_off, n, tile);
+        const int32_t p_hi = p_lo + fm_hit_pattern(hit_off + p_lo, n - p_lo, tile_last);
+        const int32_t slice_count = p_hi - p_lo + 1;
+        const bool in_lds = slice_count <= kLocateAllSlice;
+        if (in_lds) {
+            for (int32_t i = threadIdx.x; i < slice_count; i += kBlock) s_off[i] = hit_off[p_lo + i];
+            __syncthreads();
+        }
+        const int64_t *slice = in_lds ? s_off : hit_off + p_lo;
+        for (int32_t i = threadIdx.x; i < kLocateAllTile; i += kBlock) {
+            const int64_t t = tile + i;
+            int32_t p = -1, steps = 0;
+            if (t <= tile_last) {
+                int32_t k, distance = 0;
+                p = fm_locate_all_resolve(slice, slice_count, p_lo, t, k);
+                const int32_t start = range[2 * (int64_t)p];
+                int status = ST_OK;
+                locs[t - first_hit] = kRows ? fm_rows_hit<kWin>(ix, inv, start, k, distance, status)
+                                            : fm_locate_hit<kWin>(ix, inv, start, k, distance, status);
+                steps = distance;
+                if (status && status_out) atomicOr(&status_out[p], status);
+            }
+            if (lf_steps) {  // (wave-uniform; every lane of the wave is here: kLocateAllTile is a multiple of kBlock)
+                // the lanes of a pattern are neighbours: a segmented inclusive sum, then the last lane of each run adds it
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int32_t s_up = __shfl_up(steps, o);
+                    const int32_t p_up = __shfl_up(p, o);
+                    if (lane >= o && p_up == p) steps += s_up;
+                }
+                const int32_t p_next = __shfl_down(p, 1);
+                if (p >= 0 && steps && (lane == 63 || p_next != p)) atomicAdd(&lf_steps[p], steps);
+            }
+        }
+        if (in_lds) __syncthreads();  // (the next tile's slice overwrites this one)
+    }
+}
+template <int kBlock, int kWin>
+FMX_WALK_KERNEL(kBlock) void k_locate_all(DevIndex ix_global, const int32_t *__restrict__ range, const int64_t *__restrict__ hit_off,
+                                          int32_t n, int64_t first_hit, int64_t n_hits, int32_t *__restrict__ locs,
+                                          int32_t *__restrict__ lf_steps, int32_t *__restrict__ status_out) {
+    __shared__ int64_t s_off[kLocateAllSlice];
+    FMX_FM_INV(ix_global);
+    FMX_WITH_SB_CACHE(ix_global, ix);
+    locate_all_tiles<kBlock, kWin, false>(ix, s_inv, s_off, range, hit_off, n, first_hit, n_hits, locs, lf_steps, status_out);
+}
+// ... over a row table: the hits gathered (fm_rows_hit), a replay row walked by its lane.  Like k_locate_rows it stages nothing
+// for the walks (the value-of-offset table of a compact image where it lies: only a replayed hit reads it).
+template <int kBlock>
+__global__ __launch_bounds__(kBlock) void k_locate_all_rows(DevIndex ix, const int32_t *__restrict__ range,
+                                                            const int64_t *__restrict__ hit_off, int32_t n, int64_t first_hit,
+                                                            int64_t n_hits, int32_t *__restrict__ locs, int32_t *__restrict__ lf_steps,
+                                                            int32_t *__restrict__ status_out) {
+    __shared__ int64_t s_off[kLocateAllSlice];
+    locate_all_tiles<kBlock, kWinAsk, true>(ix, ix.inv_global, s_off, range, hit_off, n, first_hit, n_hits, locs, lf_steps, status_out);
 }
 
 // the row table of a resident index (k_rows_fill): walked over the window directory the index has by now, or the tree
@@ -2716,6 +2794,22 @@ int launch_locate_walk(const DevIndex &ix, int n_cu, const int32_t *range, int32
     }
     FMX_DISPATCH_WIN(k_locate_walk, ix, tickets, ix, range, n, max_matches, locs, loc_cap,
                      slots, found, lf, status, taken, order, order_idle, set_locs, set_base);
+    return (int)hipGetLastError();
+}
+
+// k_locate_all over hits [first_hit, first_hit + n_hits) of the packed order (the kernel cuts the window at hit_off[n] itself: the
+// grid is sized from what the host knows, n_hits — a workgroup per tile up to the grid cap, the rest by the grid-stride loop)
+int launch_locate_all(const DevIndex &ix, int n_cu, const int32_t *range, const int64_t *hit_off, int32_t n, int64_t first_hit,
+                      int64_t n_hits, int32_t *locs, int32_t *lf, int32_t *status, hipStream_t st) {
+    if (n <= 0 || n_hits <= 0) return 0;
+    const int64_t most = (int64_t)1 << 48;  // (tiles x lanes stays inside an int64 whatever window the caller names)
+    const int64_t tiles = ((n_hits < most ? n_hits : most) + kLocateAllTile - 1) / kLocateAllTile;
+    const int64_t lanes = tiles * options().block;  // grid_for: a workgroup per `block` lanes
+    if (ix.rows) {
+        FMX_DISPATCH(k_locate_all_rows, lanes, ix, range, hit_off, n, first_hit, n_hits, locs, lf, status);
+        return (int)hipGetLastError();
+    }
+    FMX_DISPATCH_WIN(k_locate_all, ix, lanes, ix, range, hit_off, n, first_hit, n_hits, locs, lf, status);
     return (int)hipGetLastError();
 }
 

@@ -39,4 +39,11 @@ struct CountPlan {
 // head of the plan workspace: histogram, cursors, ticket — all zero between plans (k_plan_scatter restores that)
 constexpr size_t kPlanHeadBytes = 2 * ((size_t)4 << 14) + 256;
 
+// fmx_hit_offsets.hip — the packed layout of fmx_locate_all_*: hit_off[i] = hits of patterns 0 .. i - 1 (n + 1 entries) from the
+// {start, end} ranges of a batch.  It does not depend on the image form, so it is compiled once, outside the two namespaces of
+// fmx_kernels.hip.  scratch: hit_offsets_scratch_bytes(n).  The launcher returns a hipError_t as int; `stream` a hipStream_t.
+size_t hit_offsets_scratch_bytes(int32_t n);
+int launch_hit_offsets(const int32_t *range, int32_t n, int32_t max_matches, int64_t *hit_off, void *scratch, size_t scratch_bytes,
+                       void *stream);
+
 }  // namespace fmx

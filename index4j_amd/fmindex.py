@@ -238,6 +238,25 @@ class FmIndex:
                                    status.ctypes.data), "fmx_locate_batch")
         return (locs, found, status, steps) if want_steps else (locs, found, status)
 
+    def locate_all_batch(self, chars, offsets, max_matches=-1, want_steps=False):
+        """every hit of every pattern, packed (fmx_locate_all_batch; FM:487-552): the hits of pattern i are
+        locs[hit_off[i]:hit_off[i + 1]], in the order locate() stores them.  Returns (locs, hit_off, status[, steps])."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        n = len(offsets) - 1
+        hit_off = np.zeros(n + 1, dtype=np.int64)
+        steps = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        buf = C.c_void_p()
+        check(lib.fmx_locate_all_batch(self._h, chars.ctypes.data, offsets.ctypes.data, n, int(max_matches), hit_off.ctypes.data,
+                                       C.byref(buf), steps.ctypes.data, status.ctypes.data), "fmx_locate_all_batch")
+        total = int(hit_off[n])
+        try:  # the library's buffer is copied into an array of NumPy's own and handed back
+            locs = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_int32)), shape=(total,)).copy() if total else np.zeros(0, np.int32)
+        finally:
+            lib.fmx_free_buffer(buf)
+        return (locs, hit_off, status, steps) if want_steps else (locs, hit_off, status)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -330,6 +349,18 @@ class FmIndex:
         locations[:] = locs[0]
         raise_for_status(status[0])
         return int(found[0])
+
+    def locate_all(self, pattern, offset=0, length=None, maxMatches=-1):  # FM:487-552
+        """all occurrences as an int32 array of the library's making: locate() without the caller's `locations`"""
+        p = as_chars(pattern)
+        if length is None:
+            length = len(p)
+        if length <= 0 or offset < 0 or offset + length > len(p):
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        sub = p[offset:offset + length]
+        locs, hit_off, status = self.locate_all_batch(sub, np.array([0, len(sub)], dtype=np.int32), maxMatches)
+        raise_for_status(status[0])
+        return locs
 
     def extract(self, start, stop, destination, offset=0):  # FM:564-608
         dst = np.ascontiguousarray(destination, dtype=np.uint16).reshape(1, len(destination))

@@ -204,6 +204,26 @@ int fmx_locate_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *p
 int fmx_locate_all_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t max_matches,
                          int64_t *hit_off, int32_t **locs, int32_t *lf_steps, int32_t *status);
 
+/* THE LINES THAT MATCH: which lines hold each pattern, every line once, in text order (grep -n), how many (grep -c), the first
+ * max_lines of them (grep -m) — the host form of fmx_locate_all_ranges_dev + fmx_locate_all_fill_dev (every hit, no limit) +
+ * fmx_lines_of_hits_dev (below: the line table, what a line is).  Needs a line table (fmx_line_table_build).
+ * host buffers, synchronous: line_off = n + 1 int64 (out), the exclusive sum of max_lines > 0 ? min(line_count, max_lines) :
+ * line_count (max_lines -1 and 0: every line); *lines = line_off[n] ints owned by the library until
+ * fmx_free_buffer((uint8_t *)*lines) (NULL when there are none): (*lines)[line_off[i] .. line_off[i + 1]) = the distinct line ids
+ * of pattern i, ascending — with a limit the smallest max_lines of them; line_count[i] (nullable) = ALL distinct lines of pattern
+ * i whatever the limit; occurrences[i] (nullable) = count(); status[i] (nullable) as fmx_locate_all_batch leaves it (an empty
+ * pattern: FMX_ST_JAVA_AIOOBE and no lines).  What comes down from the device is the lines, not the hits: " " occurs 30,094 times
+ * in the 2,000 lines of the reference's log fixture.  Device scratch grows with the batch's hits, no windows in this version —
+ * 32 bytes per hit (positions 4, lines 4, fmx_lines_of_hits_dev's workspace 24) plus the radix sort's temporary storage, about
+ * one more 8-byte key per hit, each block rounded up to a power of two: FMX_E_NOMEM when it, or the result, cannot be allocated (nothing is left behind; *lines = NULL on every
+ * failure).  FMX_E_ARG as fmx_locate_all_batch, for an index without a line table (fmx_last_error names fmx_line_table_build),
+ * and for a batch of more than 2^31 - 1 hits; FMX_E_NO_DEVICE for a handle that is not resident. */
+int fmx_match_lines_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t max_lines,
+                          int64_t *line_off, int32_t **lines, int32_t *line_count, int32_t *occurrences, int32_t *status);
+/* [start[i], stop[i]) of line lines[i], the boundary excluded — what fmx_extract_batch takes; an id outside [0, n_lines) gets
+ * start = stop = -1.  Host buffers, synchronous.  FMX_E_ARG without a line table. */
+int fmx_line_bounds_batch(const fmx_index *idx, const int32_t *lines, int32_t n, int32_t *start, int32_t *stop);
+
 /* int extract(int start, int stop, char[] destination, int offset) FM:564-608.  dst is n rows of
  * dst_len chars (row i = the `destination` array of query i, in/out); out_len[i] = return value. */
 int fmx_extract_batch(const fmx_index *idx, const int32_t *start, const int32_t *stop, int32_t n, uint16_t *dst,
@@ -280,6 +300,48 @@ int fmx_locate_all_ranges_dev(const fmx_index *idx, const uint16_t *d_pat, const
 int fmx_locate_all_fill_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_off, const int32_t *d_range_ws,
                             int64_t first_hit, int64_t n_hits, int32_t *d_locs, int32_t *d_lf_steps, int32_t *d_status,
                             void *stream);
+/* THE LINE TABLE of a resident FM-index — a resident extra like the row table and the window directory, 4 bytes per line, made
+ * on request: T = the positions locate(new char[]{boundary}, locations) returns, sorted ascending, as int32 in the index's
+ * device memory.  It holds what the INDEX answers (quirk Q1 included), not what the text "really" holds, so that everything
+ * below is defined by reference calls plus arithmetic:
+ *   line(p)  = the number of entries of T below p, for any int32 p;
+ *   n_lines  = |T| + 1 if the text is not empty and its last character is not in T, |T| otherwise (the text: what the caller
+ *              handed to the constructor, textLength = getInputLength() - 1 characters);
+ *   line k   = [k == 0 ? 0 : T[k - 1] + 1, k < |T| ? T[k] : textLength) — the boundary itself excluded;
+ *   a hit belongs to the line of its FIRST character, also for a pattern that holds the boundary or is the boundary.
+ * Built on the device: the range search and k_locate_all for the one-character pattern, then a device sort.  Host-synchronous.
+ * A second call with the same boundary does nothing; another boundary replaces the table.  *n_lines (nullable) = n_lines.
+ * The table belongs to the resident state: fmx_free and a new fmx_to_device free it (fmx_line_table_info then reports boundary
+ * -1 and 0 bytes), fmx_replicate does not copy it (a replica builds its own).  It is the ONE mutation of a resident index:
+ * fmx_line_table_build must not run beside queries on the same handle (every other call on a resident handle may).
+ * FMX_E_NO_DEVICE for a handle that is not resident; FMX_E_ARG for a SuffixArray, RrrVector or stand-alone wavelet handle;
+ * FMX_E_NOMEM when the table does not fit the device. */
+int fmx_line_table_build(fmx_index *idx, uint16_t boundary, int64_t *n_lines);
+/* *boundary = the table's boundary character (-1: no table), *n_boundaries = |T|, *bytes = its size as allocated (each nullable) */
+int fmx_line_table_info(const fmx_index *idx, int32_t *boundary, int64_t *n_boundaries, int64_t *bytes);
+/* fmx_line_bounds_batch over device pointers, asynchronous on `stream` */
+int fmx_line_bounds_batch_dev(const fmx_index *idx, const int32_t *d_lines, int32_t n, int32_t *d_start, int32_t *d_stop, void *stream);
+/* PACKED HITS -> PACKED DISTINCT LINES.  Input: exactly what fmx_locate_all_ranges_dev and fmx_locate_all_fill_dev leave —
+ * d_hit_off (n + 1 entries) and d_locs, which holds hits [0, n_hits) of the packed order, n_hits >= d_hit_off[n] (what the caller
+ * read between the stages).  Output: d_line_count[i] (nullable) = the distinct lines of pattern i; d_line_off (n + 1 int64) = the
+ * exclusive sum of max_lines > 0 ? min(line_count, max_lines) : line_count; d_lines[d_line_off[i] .. d_line_off[i + 1]) = the
+ * distinct line ids of pattern i, ascending (with a limit: the smallest max_lines of them).  The caller gives d_lines room for
+ * n_hits ints; entries from d_line_off[n] on keep the caller's values.
+ * Lanes are handed to HITS in every stage (a key per hit, ONE device-wide radix sort of (pattern, line) keys, a scan over the
+ * sorted keys, a compaction): a batch of one pattern that matches everywhere uses the whole device, and the result does not
+ * depend on scheduling (no atomics).  Asynchronous on `stream`; nothing is synchronised and nothing is allocated: the caller
+ * owns d_ws, at least fmx_lines_of_hits_scratch_bytes(n, n_hits) bytes (24 per hit — two key arrays, flags, their scan — plus the
+ * radix sort's temporary storage, about one more 8-byte key per hit; 0 for an empty call).
+ * n == 0 or n_hits == 0: the offsets are zeroed and nothing else is written.  FMX_E_ARG for null or negative arguments, for a
+ * workspace that is too small (nothing is launched), without a line table, and for n_hits > 2^31 - 1 in this version;
+ * FMX_E_NO_DEVICE for a handle that is not resident. */
+size_t fmx_lines_of_hits_scratch_bytes(int32_t n, int64_t n_hits);
+int fmx_lines_of_hits_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits,
+                          int32_t max_lines, int64_t *d_line_off, int32_t *d_lines, int32_t *d_line_count, void *d_ws,
+                          size_t ws_bytes, void *stream);
+/* the grids fmx_lines_of_hits_dev launches for n_hits hits on this index's device: workgroups of the key kernel (a tile of 1,024
+ * hits each, per round) and of the element-wise kernels (256 lanes); what is beyond them is taken by grid-stride loops */
+int fmx_hit_lines_geometry(const fmx_index *idx, int64_t n_hits, int32_t *key_grid, int32_t *flat_grid);
 int fmx_extract_batch_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n,
                           uint16_t *d_dst, int32_t dst_len, int32_t offset, int32_t *d_out_len,
                           int32_t *d_lf_steps, int32_t *d_status, void *stream);

@@ -171,6 +171,46 @@ public:
         if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
         return locateAllBatch({pattern}, -1).locations;
     }
+    // the lines that match (fmx.h "THE LINE TABLE"): buildLineTable once per residency, then matchLines / matchLinesBatch —
+    // the distinct line ids of pattern i are lines[offsets[i] .. offsets[i + 1]), ascending; maxLines > 0 keeps the first of them,
+    // lineCount says how many there are whatever the limit, occurrences is count()
+    int64_t buildLineTable(char16_t boundary = u'\n') {
+        int64_t lines = 0;
+        detail::check(fmx_line_table_build(h_, (uint16_t)boundary, &lines), "fmx_line_table_build");
+        return lines;
+    }
+    struct Lines {
+        std::vector<int64_t> offsets;
+        std::vector<int32_t> lines, lineCount, occurrences;
+    };
+    Lines matchLinesBatch(const std::vector<std::u16string> &patterns, int maxLines = 0) const {
+        std::vector<uint16_t> chars;
+        std::vector<int32_t> off;
+        pack(patterns, chars, off);
+        const int32_t n = (int32_t)patterns.size();
+        Lines out;
+        out.offsets.assign((size_t)n + 1, 0);
+        out.lineCount.assign(patterns.size(), 0);
+        out.occurrences.assign(patterns.size(), 0);
+        std::vector<int32_t> status(patterns.size());
+        int32_t *buf = nullptr;
+        detail::check(fmx_match_lines_batch(h_, chars.data(), off.data(), n, maxLines, out.offsets.data(), &buf, out.lineCount.data(),
+                                            out.occurrences.data(), status.data()),
+                      "fmx_match_lines_batch");
+        try {
+            if (buf) out.lines.assign(buf, buf + out.offsets[(size_t)n]);
+        } catch (...) {
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+            throw;
+        }
+        fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+        for (int s : status) detail::raise_for_status(s);
+        return out;
+    }
+    std::vector<int32_t> matchLines(const std::u16string &pattern, int maxLines = 0) const {
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        return matchLinesBatch({pattern}, maxLines).lines;
+    }
 
     // locate, then extract(loc, min(getInputLength(), loc + extractLength), row, 0) per hit, both on the device:
     // the composite the reference times in locateAndExtractBenchmark (FmIndexThroughputBenchmark.java:231-249).

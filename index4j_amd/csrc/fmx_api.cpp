@@ -92,6 +92,11 @@ struct fmx_index {
     void *d_rows = nullptr;             // DevIndex.rows: the row table (owned likewise; option locate_rows)
     size_t rows_bytes = 0;              // ... as allocated
     uint32_t rows_replay = 0;           // ... rows whose word says "walk this hit" (fmx::kRowReplay)
+    void *d_line_table = nullptr;       // the line table T (fmx_line_table_build; owned likewise): line_count sorted int32 positions
+    size_t line_table_bytes = 0;        // ... as allocated
+    int32_t line_boundary = -1;         // ... its boundary character (-1: no table)
+    int32_t line_count = 0;             // ... |T|
+    int64_t n_lines = 0;                // ... lines of the text (fm_line_total)
     size_t suffix_table_bytes = 0;
     uint32_t suffix_table_strings = 0;  // strings (of 2 .. suffix_chars codes) the table holds
     uint32_t suffix_table_deepest = 0;  // ... of which strings of suffix_chars codes: what a batch's patterns spread over after the lookup
@@ -819,6 +824,12 @@ static void release_device_state(fmx_index *idx) {
     if (idx->d_win) (void)hipFree(idx->d_win);
     if (idx->d_win_other) (void)hipFree(idx->d_win_other);
     if (idx->d_rows) (void)hipFree(idx->d_rows);
+    if (idx->d_line_table) (void)hipFree(idx->d_line_table);
+    idx->d_line_table = nullptr;
+    idx->line_table_bytes = 0;
+    idx->line_boundary = -1;
+    idx->line_count = 0;
+    idx->n_lines = 0;
     idx->d_blob = idx->d_suffix_table = idx->d_suffix_order1 = idx->d_self = idx->d_win = idx->d_win_other = idx->d_rows = nullptr;
     idx->d_len = 0;
     idx->win_bytes = idx->suffix_table_bytes = idx->rows_bytes = 0;
@@ -1647,7 +1658,8 @@ static int require_fm_device(const fmx_index *idx) {
 }
 
 static int locate_all_ranges_impl(const fmx_index *idx, const uint16_t *d_pat, const int32_t *d_pat_off, int32_t n, int32_t max_matches,
-                                  int64_t *d_hit_off, int32_t *d_lf_steps, int32_t *d_status, int32_t *d_range_ws, Scratch &scratch) {
+                                  int64_t *d_hit_off, int32_t *d_lf_steps, int32_t *d_status, int32_t *d_range_ws, Scratch &scratch,
+                                  int32_t *d_counts = nullptr /* n ints: count() of every pattern, for a caller that wants it */) {
     if (!idx || n < 0 || !d_hit_off || (n > 0 && (!d_pat_off || !d_range_ws))) return fail(FMX_E_ARG, "bad arguments");
     int rc = require_fm_device(idx);
     if (rc) return rc;
@@ -1660,8 +1672,8 @@ static int locate_all_ranges_impl(const fmx_index *idx, const uint16_t *d_pat, c
     rc = plan_order(idx, d_pat, d_pat_off, n, scratch, &plan);
     if (rc) return rc;
     // (the range pass wants a `counts` output: the first n ints of d_hit_off take it; the scan below overwrites them afterwards)
-    int e = k_launch_count(idx, idx->dev, idx->n_cu, d_pat, d_pat_off, &plan, false, n, reinterpret_cast<int32_t *>(d_hit_off), d_lf_steps,
-                           d_status, d_range_ws, st);
+    int e = k_launch_count(idx, idx->dev, idx->n_cu, d_pat, d_pat_off, &plan, false, n,
+                           d_counts ? d_counts : reinterpret_cast<int32_t *>(d_hit_off), d_lf_steps, d_status, d_range_ws, st);
     if (e) return fail(FMX_E_HIP, std::string("k_count launch: ") + hipGetErrorString((hipError_t)e));
     void *ws = nullptr;
     const size_t ws_bytes = fmx::hit_offsets_scratch_bytes(n);
@@ -1690,6 +1702,187 @@ int fmx_locate_all_fill_dev(const fmx_index *idx, int32_t n, const int64_t *d_hi
     int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_range_ws, d_hit_off, n, first_hit, n_hits, d_locs, d_lf_steps, d_status,
                                 static_cast<hipStream_t>(stream));
     if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+    });
+}
+
+// ---- lines: the line table of a resident index, packed hits -> packed distinct lines (fmx_hit_lines.hip) ------------------------
+static int require_line_table(const fmx_index *idx) {
+    if (!idx->d_line_table) return fail(FMX_E_ARG, "the index has no line table (call fmx_line_table_build)");
+    return FMX_OK;
+}
+// the text as the caller handed it over: getInputLength() counts the terminator the constructor appends (FM:300-305)
+static int32_t line_text_length(const fmx_index *idx) { return idx->hdr.length > 0 ? (int32_t)idx->hdr.length - 1 : 0; }
+// whatever leaves a host-synchronous call first waits for its stream; declared BEHIND the call's device blocks, so that they
+// return to their cache only afterwards
+struct StreamWait {
+    hipStream_t s;
+    ~StreamWait() { (void)hipStreamSynchronize(s); }
+};
+static int alloc_for_hits(DevBuf &b, size_t bytes) {  // scratch that grows with a batch's hits: running out of it is FMX_E_NOMEM
+    const hipError_t e = b.alloc(bytes);
+    if (e == hipSuccess) return FMX_OK;
+    (void)hipGetLastError();
+    b.p = nullptr;
+    if (e == hipErrorOutOfMemory) return fail(FMX_E_NOMEM, "out of device memory for " + std::to_string(bytes) + " bytes of scratch");
+    return fail(FMX_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+}
+
+int fmx_line_table_build(fmx_index *idx, uint16_t boundary, int64_t *n_lines) {
+    return guarded([&]() -> int {
+    if (!idx) return fail(FMX_E_ARG, "null index");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if (idx->d_line_table && idx->line_boundary == (int32_t)boundary) {  // the table is there
+        if (n_lines) *n_lines = idx->n_lines;
+        return FMX_OK;
+    }
+    HIP_TRY(hipSetDevice(idx->device));
+    PipeStreams *ps = nullptr;
+    rc = pipe_streams(idx->device, &ps);
+    if (rc) return rc;
+    hipStream_t st = ps->s[1];
+    DevBuf d_pat, d_off, d_hit, d_ws, d_locs, d_sort;
+    HIP_TRY(d_pat.alloc(16));
+    HIP_TRY(d_off.alloc(8));
+    HIP_TRY(d_hit.alloc(16));
+    HIP_TRY(d_ws.alloc(8));
+    Scratch scratch(idx, st, true);
+    void *table = nullptr;
+    struct Leave {  // the stream first, then a table that was not handed over
+        hipStream_t s;
+        void **table;
+        ~Leave() {
+            (void)hipStreamSynchronize(s);
+            if (*table) (void)hipFree(*table);
+        }
+    } leave{st, &table};
+    // T = what locate(new char[]{boundary}, locations) returns: the range search and k_locate_all for the one-character pattern
+    const int32_t off_h[2] = {0, 1};
+    H2D(d_pat.p, &boundary, 2);
+    H2D(d_off.p, off_h, 8);
+    rc = locate_all_ranges_impl(idx, d_pat.as<uint16_t>(), d_off.as<int32_t>(), 1, -1, d_hit.as<int64_t>(), nullptr, nullptr,
+                                d_ws.as<int32_t>(), scratch);
+    if (rc) return rc;
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_hit.as<int64_t>() + 1, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (total < 0 || total > 0x7fffffff) return fail(FMX_E_UNSUPPORTED, "more boundaries than an int32 line id holds");
+    const size_t bytes = (((size_t)total * 4 + 63) & ~(size_t)63) + 64;
+    if (hipMalloc(&table, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        table = nullptr;
+        return fail(FMX_E_NOMEM, "out of device memory for a line table of " + std::to_string(total) + " boundaries");
+    }
+    const size_t sort_bytes = fmx::line_table_scratch_bytes((int32_t)total);
+    if ((rc = alloc_for_hits(d_locs, (size_t)total * 4 + 8))) return rc;
+    if ((rc = alloc_for_hits(d_sort, sort_bytes))) return rc;
+    if (total > 0) {
+        int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_ws.as<int32_t>(), d_hit.as<int64_t>(), 1, (int64_t)0, total,
+                                    d_locs.as<int32_t>(), nullptr, nullptr, st);
+        if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
+    }
+    // (the line count lands behind the hits, in a slot of the same block)
+    int64_t *d_lines_total = reinterpret_cast<int64_t *>(static_cast<uint8_t *>(table) + bytes - 64);
+    int e = fmx::launch_line_table(d_locs.as<int32_t>(), (int32_t)total, line_text_length(idx), static_cast<int32_t *>(table), d_lines_total,
+                                   d_sort.p, sort_bytes, st);
+    if (e) return fail(FMX_E_HIP, std::string("line table sort: ") + hipGetErrorString((hipError_t)e));
+    int64_t lines = 0;
+    HIP_TRY(hipMemcpyAsync(&lines, d_lines_total, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (idx->d_line_table) (void)hipFree(idx->d_line_table);  // another boundary's
+    idx->d_line_table = table;
+    table = nullptr;
+    idx->line_table_bytes = bytes;
+    idx->line_boundary = (int32_t)boundary;
+    idx->line_count = (int32_t)total;
+    idx->n_lines = lines;
+    if (n_lines) *n_lines = lines;
+    return FMX_OK;
+    });
+}
+
+int fmx_line_table_info(const fmx_index *idx, int32_t *boundary, int64_t *n_boundaries, int64_t *bytes) {
+    return guarded([&]() -> int {
+    if (!idx || idx->sa) return fail(FMX_E_ARG, "not an FM-index handle");
+    const bool have = idx->d_blob != nullptr && idx->d_line_table != nullptr;
+    if (boundary) *boundary = have ? idx->line_boundary : -1;
+    if (n_boundaries) *n_boundaries = have ? (int64_t)idx->line_count : 0;
+    if (bytes) *bytes = have ? (int64_t)idx->line_table_bytes : 0;
+    return FMX_OK;
+    });
+}
+
+int fmx_line_bounds_batch_dev(const fmx_index *idx, const int32_t *d_lines, int32_t n, int32_t *d_start, int32_t *d_stop, void *stream) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || (n > 0 && (!d_lines || !d_start || !d_stop))) return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if ((rc = require_line_table(idx))) return rc;
+    int e = fmx::launch_line_bounds(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_lines, line_text_length(idx),
+                                    idx->n_cu, d_lines, n, d_start, d_stop, stream);
+    if (e) return fail(FMX_E_HIP, std::string("k_line_bounds launch: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+    });
+}
+
+int fmx_line_bounds_batch(const fmx_index *idx, const int32_t *lines, int32_t n, int32_t *start, int32_t *stop) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || (n > 0 && (!lines || !start || !stop))) return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if ((rc = require_line_table(idx))) return rc;
+    if (n == 0) return FMX_OK;
+    HIP_TRY(hipSetDevice(idx->device));
+    PipeStreams *ps = nullptr;
+    rc = pipe_streams(idx->device, &ps);
+    if (rc) return rc;
+    hipStream_t st = ps->s[1];
+    DevBuf d_in, d_start, d_stop;
+    HIP_TRY(d_in.alloc((size_t)n * 4));
+    HIP_TRY(d_start.alloc((size_t)n * 4));
+    HIP_TRY(d_stop.alloc((size_t)n * 4));
+    StreamWait wait{st};
+    HIP_TRY(hipMemcpyAsync(d_in.p, lines, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    int e = fmx::launch_line_bounds(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_lines, line_text_length(idx),
+                                    idx->n_cu, d_in.as<int32_t>(), n, d_start.as<int32_t>(), d_stop.as<int32_t>(), st);
+    if (e) return fail(FMX_E_HIP, std::string("k_line_bounds launch: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipMemcpyAsync(start, d_start.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(stop, d_stop.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return FMX_OK;
+    });
+}
+
+size_t fmx_lines_of_hits_scratch_bytes(int32_t n, int64_t n_hits) { return fmx::lines_of_hits_scratch_bytes(n, n_hits); }
+
+int fmx_hit_lines_geometry(const fmx_index *idx, int64_t n_hits, int32_t *key_grid, int32_t *flat_grid) {
+    return guarded([&]() -> int {
+    if (!idx || n_hits < 0 || !key_grid || !flat_grid) return fail(FMX_E_ARG, "bad arguments");
+    fmx::hit_lines_geometry(n_hits, idx->n_cu, key_grid, flat_grid);
+    return FMX_OK;
+    });
+}
+
+int fmx_lines_of_hits_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int32_t max_lines,
+                          int64_t *d_line_off, int32_t *d_lines, int32_t *d_line_count, void *d_ws, size_t ws_bytes, void *stream) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || n_hits < 0 || !d_line_off || (n > 0 && !d_hit_off) || (n > 0 && n_hits > 0 && (!d_locs || !d_lines)))
+        return fail(FMX_E_ARG, "bad arguments");
+    if (n_hits > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one call");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if ((rc = require_line_table(idx))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0 || n_hits == 0) {
+        HIP_TRY(hipMemsetAsync(d_line_off, 0, ((size_t)n + 1) * sizeof(int64_t), st));
+        return FMX_OK;
+    }
+    if (!d_ws || ws_bytes < fmx::lines_of_hits_scratch_bytes(n, n_hits))
+        return fail(FMX_E_ARG, "the workspace is smaller than fmx_lines_of_hits_scratch_bytes");
+    int e = fmx::launch_lines_of_hits(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_cu, n, d_hit_off, d_locs, n_hits,
+                                      max_lines, d_line_off, d_lines, d_line_count, d_ws, ws_bytes, stream);
+    if (e) return fail(FMX_E_HIP, std::string("lines of hits: ") + hipGetErrorString((hipError_t)e));
     return FMX_OK;
     });
 }
@@ -2832,6 +3025,93 @@ int fmx_locate_all_batch(const fmx_index *idx, const uint16_t *pat, const int32_
     if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     *locs = result.p;
+    result.p = nullptr;
+    return FMX_OK;
+    });
+}
+
+// The host form of "which lines match": stage 1 and stage 2 of "all occurrences" (every hit, no limit, no windows: the sort wants
+// them all at once), fmx_lines_of_hits_dev's stages, ONE 8-byte copy and wait for the number of lines, the result malloc'ed to
+// that size.  What comes down is the lines, not the hits.
+int fmx_match_lines_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t max_lines,
+                          int64_t *line_off, int32_t **lines, int32_t *line_count, int32_t *occurrences, int32_t *status) {
+    return guarded([&]() -> int {
+    if (lines) *lines = nullptr;
+    if (!idx || n < 0 || !line_off || !lines || (n > 0 && !pat_off)) return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if ((rc = require_line_table(idx))) return rc;
+    if (n == 0) {
+        line_off[0] = 0;
+        return FMX_OK;
+    }
+    HIP_TRY(hipSetDevice(idx->device));
+    rc = check_offsets(pat_off, n);
+    if (rc) return rc;
+    const size_t chars = (size_t)(pat_off[n] > 0 ? pat_off[n] : 0), first = first_char(pat_off);
+    if (chars > first && !pat) return fail(FMX_E_ARG, "bad arguments");
+    DevBuf d_pat, d_off, d_hit, d_cnt, d_st, d_rng, d_loff, d_lcnt, d_locs, d_lines, d_ws;
+    HIP_TRY(d_pat.alloc(chars * 2 + 8));
+    HIP_TRY(d_off.alloc((size_t)(n + 1) * 4));
+    HIP_TRY(d_hit.alloc((size_t)(n + 1) * 8));
+    HIP_TRY(d_loff.alloc((size_t)(n + 1) * 8));
+    HIP_TRY(d_cnt.alloc((size_t)n * 4));
+    HIP_TRY(d_lcnt.alloc((size_t)n * 4));
+    if (status) HIP_TRY(d_st.alloc((size_t)n * 4));
+    HIP_TRY(d_rng.alloc((size_t)n * 8));
+    PipeStreams *ps = nullptr;
+    rc = pipe_streams(idx->device, &ps);
+    if (rc) return rc;
+    hipStream_t st = ps->s[1];
+    Scratch scratch(idx, st, true);
+    struct Result {  // (as in fmx_locate_all_batch)
+        hipStream_t s;
+        int32_t *p = nullptr;
+        ~Result() {
+            (void)hipStreamSynchronize(s);
+            free(p);
+        }
+    } result{st};
+    if (chars > first) HIP_TRY(hipMemcpyAsync(d_pat.as<uint16_t>() + first, pat + first, (chars - first) * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off.p, pat_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
+    int32_t *dst_ = status ? d_st.as<int32_t>() : nullptr;
+    rc = locate_all_ranges_impl(idx, d_pat.as<uint16_t>(), d_off.as<int32_t>(), n, -1, d_hit.as<int64_t>(), nullptr, dst_, d_rng.as<int32_t>(),
+                                scratch, d_cnt.as<int32_t>());
+    if (rc) return rc;
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_hit.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
+    int64_t n_out = 0;
+    if (total > 0) {
+        const size_t ws_bytes = fmx::lines_of_hits_scratch_bytes(n, total);
+        if ((rc = alloc_for_hits(d_locs, (size_t)total * 4))) return rc;
+        if ((rc = alloc_for_hits(d_lines, (size_t)total * 4))) return rc;
+        if ((rc = alloc_for_hits(d_ws, ws_bytes))) return rc;
+        int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_rng.as<int32_t>(), d_hit.as<int64_t>(), n, (int64_t)0, total,
+                                    d_locs.as<int32_t>(), nullptr, dst_, st);
+        if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
+        e = fmx::launch_lines_of_hits(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_cu, n, d_hit.as<int64_t>(),
+                                      d_locs.as<int32_t>(), total, max_lines, d_loff.as<int64_t>(), d_lines.as<int32_t>(), d_lcnt.as<int32_t>(),
+                                      d_ws.p, d_ws.bytes, st);
+        if (e) return fail(FMX_E_HIP, std::string("lines of hits: ") + hipGetErrorString((hipError_t)e));
+        HIP_TRY(hipMemcpyAsync(&n_out, d_loff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        HIP_TRY(hipMemsetAsync(d_loff.p, 0, (size_t)(n + 1) * 8, st));
+        HIP_TRY(hipMemsetAsync(d_lcnt.p, 0, (size_t)n * 4, st));
+    }
+    if (n_out > 0) {
+        result.p = static_cast<int32_t *>(malloc((size_t)n_out * 4));
+        if (!result.p) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(n_out) + " lines");
+        HIP_TRY(hipMemcpyAsync(result.p, d_lines.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(line_off, d_loff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (line_count) HIP_TRY(hipMemcpyAsync(line_count, d_lcnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (occurrences) HIP_TRY(hipMemcpyAsync(occurrences, d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *lines = result.p;
     result.p = nullptr;
     return FMX_OK;
     });

@@ -23,6 +23,7 @@
 
 #if defined(__HIPCC__)
 #define FMX_HD __device__ inline __attribute__((always_inline))
+#define FMX_HHD __host__ __device__ inline  // ... one a launcher calls too
 // A COLD route: ONE real function per code object instead of a copy at every call site of the LF-walk kernels (the
 // reference's own routes through the wavelet tree, met on block boundaries and quirk paths: a fraction of a percent of the
 // LF-steps, but 80 % of the kernels' instructions when inlined at each of their ten-odd call sites).  It takes the index as a
@@ -31,6 +32,7 @@
 #define FMX_SELF(ix) ((ix).self)
 #else
 #define FMX_HD inline
+#define FMX_HHD inline
 #define FMX_COLD inline
 #define FMX_SELF(ix) (&(ix))
 #endif
@@ -2047,6 +2049,77 @@ FMX_HD int32_t fm_locate_all_resolve(const int64_t *slice, int32_t slice_count, 
     const int32_t i = fm_hit_pattern(slice, slice_count, t);
     k = (int32_t)(t - slice[i]);
     return p_lo + i;
+}
+
+// THE LINE TABLE of a resident index (fmx_line_table_build; fmx_hit_lines.hip): T = what locate() returns for the one-character
+// pattern {boundary}, sorted ascending, `count` int32 entries.  line(p) = the number of entries of T below p, for any int32 p:
+// a hit belongs to the line of its first character.  fm_line_of finds it by binary search.  Its first levels run over the FENCES,
+// every 2^shift-th entry of T (fences[j] = T[j << shift], n_fences = ceil(count / 2^shift) of them; a workgroup's copy in LDS),
+// the remaining `shift` levels over T itself (what that saves in dependent HBM loads: DESIGN.md section 4; reasoned, not
+// measured).  n_fences == 0: no fences, every level over T.
+constexpr int32_t kLineFences = 4096;  // 16 KiB of LDS per workgroup
+// the smallest shift at which at most max_fences fences cover `count` entries, and how many those are (max_fences <= 0: none)
+FMX_HHD int32_t fm_line_fence_shift(int32_t count, int32_t max_fences, int32_t &n_fences) {
+    int32_t s = 0;
+    n_fences = 0;
+    if (max_fences <= 0 || count <= 0) return 0;
+    while ((((int64_t)count + ((int64_t)1 << s) - 1) >> s) > max_fences) ++s;
+    n_fences = (int32_t)(((int64_t)count + ((int64_t)1 << s) - 1) >> s);
+    return s;
+}
+FMX_HD int32_t fm_line_of(const int32_t *T, int32_t count, const int32_t *fences, int32_t n_fences, int32_t shift, int32_t p) {
+    int32_t lo = 0, hi = count;  // the answer lies in [lo, hi]
+    if (n_fences > 0) {
+        int32_t a = 0, b = n_fences;  // f = the number of fences below p
+        while (a < b) {
+            const int32_t mid = a + ((b - a) >> 1);
+            if (fences[mid] < p)
+                a = mid + 1;
+            else
+                b = mid;
+        }
+        if (a == 0) return 0;                 // T[0] >= p
+        lo = (int32_t)(((int64_t)(a - 1) << shift) + 1);  // T[(f - 1) << shift] < p
+        if (a < n_fences) hi = a << shift;    // T[f << shift] >= p
+    }
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (T[mid] < p)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+// lines of a text of text_len characters: one behind the last boundary unless the text ends in one (or is empty)
+FMX_HD int64_t fm_line_total(const int32_t *T, int32_t count, int32_t text_len) {
+    if (text_len <= 0) return count;
+    const int32_t l = fm_line_of(T, count, nullptr, 0, 0, text_len - 1);
+    return (l < count && T[l] == text_len - 1) ? count : (int64_t)count + 1;
+}
+// [start, stop) of line k, the boundary itself excluded — what fmx_extract_batch takes; an id outside [0, n_lines): -1, -1
+FMX_HD void fm_line_bounds(const int32_t *T, int32_t count, int64_t n_lines, int32_t text_len, int32_t k, int32_t &start, int32_t &stop) {
+    if (k < 0 || k >= n_lines) {
+        start = stop = -1;
+        return;
+    }
+    start = k == 0 ? 0 : T[k - 1] + 1;
+    stop = k < count ? T[k] : text_len;
+}
+// The sort key of one packed hit: (pattern << line_bits) | line, so that ONE device-wide sort orders the batch by pattern, then
+// by line.  line is in [0, count]: line_bits = fm_bits(count); the pattern in [0, n], where n marks a slot behind hit_off[n]
+// (it sorts behind every hit): fm_bits(n) bits.  At most 31 + 31 bits.
+FMX_HHD int32_t fm_bits(uint32_t v) {
+    int32_t b = 1;
+    while (b < 32 && (v >> b)) ++b;
+    return b;
+}
+FMX_HD uint64_t fm_line_key(int32_t pattern, int32_t line, int32_t line_bits) { return ((uint64_t)(uint32_t)pattern << line_bits) | (uint32_t)line; }
+FMX_HD int32_t fm_line_key_pattern(uint64_t key, int32_t line_bits) { return (int32_t)(key >> line_bits); }
+FMX_HD int32_t fm_line_key_line(uint64_t key, int32_t line_bits) { return (int32_t)(key & (((uint64_t)1 << line_bits) - 1)); }
+// sorted key i opens a (pattern, line) pair of its own: a hit's key (pattern < n) that differs from its predecessor
+FMX_HD bool fm_line_head(const uint64_t *keys, int64_t i, int32_t n, int32_t line_bits) {
+    return fm_line_key_pattern(keys[i], line_bits) < n && (i == 0 || keys[i] != keys[i - 1]);
 }
 
 // up to four characters of one aligned 8-byte group of a destination row (mask: which of them): one store when all four are there

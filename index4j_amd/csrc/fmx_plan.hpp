@@ -46,4 +46,23 @@ size_t hit_offsets_scratch_bytes(int32_t n);
 int launch_hit_offsets(const int32_t *range, int32_t n, int32_t max_matches, int64_t *hit_off, void *scratch, size_t scratch_bytes,
                        void *stream);
 
+// fmx_hit_lines.hip — the line table of a resident index and packed hits -> packed distinct lines (fmx_line_table_build,
+// fmx_line_bounds_*, fmx_lines_of_hits_dev).  Compiled once, like fmx_hit_offsets.hip.  The launchers return a hipError_t as int;
+// `stream` is a hipStream_t; nothing is synchronised or allocated.
+// launch_line_table: T[0 .. count) = locs sorted ascending (scratch: line_table_scratch_bytes), *n_lines (device) = fm_line_total.
+size_t line_table_scratch_bytes(int32_t count);
+int launch_line_table(const int32_t *locs, int32_t count, int32_t text_len, int32_t *T, int64_t *n_lines, void *scratch, size_t scratch_bytes,
+                      void *stream);
+int launch_line_bounds(const int32_t *T, int32_t count, int64_t n_lines, int32_t text_len, int n_cu, const int32_t *ids, int32_t n,
+                       int32_t *start, int32_t *stop, void *stream);
+// the workspace of launch_lines_of_hits (0: nothing to do, or n_hits beyond 2^31 - 1); too small a workspace: hipErrorInvalidValue
+// before anything is launched
+size_t lines_of_hits_scratch_bytes(int32_t n, int64_t n_hits);
+int launch_lines_of_hits(const int32_t *T, int32_t count, int n_cu, int32_t n, const int64_t *hit_off, const int32_t *locs, int64_t n_hits,
+                         int32_t max_lines, int64_t *line_off, int32_t *lines, int32_t *line_count, void *ws, size_t ws_bytes, void *stream);
+// workgroups per CU the grids stop at (the rest of the hits by grid-stride loops): k_hit_line_keys takes tiles of kLocateAllTile
+// hits with 1,024 lanes, the element-wise kernels 256 lanes; hit_lines_geometry: the two grids of a call over n_hits hits
+constexpr int kHitLinesKeyGroupsPerCu = 2, kHitLinesFlatGroupsPerCu = 8;
+void hit_lines_geometry(int64_t n_hits, int n_cu, int32_t *key_grid, int32_t *flat_grid);
+
 }  // namespace fmx

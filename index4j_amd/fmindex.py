@@ -257,6 +257,51 @@ class FmIndex:
             lib.fmx_free_buffer(buf)
         return (locs, hit_off, status, steps) if want_steps else (locs, hit_off, status)
 
+    # ---- the lines that match (fmx.h "THE LINE TABLE", "THE LINES THAT MATCH") ----
+    def build_line_table(self, boundary="\n"):
+        """make the resident line table for `boundary` (fmx_line_table_build; a second call with the same boundary does nothing,
+        another boundary replaces it); returns the number of lines.  Not beside queries on the same index."""
+        b = boundary if isinstance(boundary, (int, np.integer)) else ord(boundary)
+        n_lines = C.c_int64(0)
+        check(lib.fmx_line_table_build(self._h, int(b), C.byref(n_lines)), "fmx_line_table_build")
+        return n_lines.value
+
+    def line_table_info(self):
+        """(boundary, n_boundaries, bytes) of the resident line table; (-1, 0, 0): none — fmx_line_table_info"""
+        b, k, nbytes = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        check(lib.fmx_line_table_info(self._h, C.byref(b), C.byref(k), C.byref(nbytes)), "fmx_line_table_info")
+        return b.value, k.value, nbytes.value
+
+    def line_bounds(self, lines):
+        """(start, stop) of every line id, the boundary excluded: what extract_batch takes; -1, -1 for an id that is no line"""
+        lines = np.ascontiguousarray(lines, dtype=np.int32)
+        start = np.zeros(len(lines), dtype=np.int32)
+        stop = np.zeros(len(lines), dtype=np.int32)
+        check(lib.fmx_line_bounds_batch(self._h, lines.ctypes.data, len(lines), start.ctypes.data, stop.ctypes.data), "fmx_line_bounds_batch")
+        return start, stop
+
+    def match_lines_batch(self, chars, offsets, max_lines=0, want_counts=False):
+        """the distinct lines of every pattern, packed and ascending (fmx_match_lines_batch): those of pattern i are
+        lines[line_off[i]:line_off[i + 1]], at most max_lines of them for max_lines > 0.  Returns (lines, line_off, status
+        [, line_count, occurrences]): line_count = all distinct lines of a pattern whatever the limit, occurrences = count()."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        n = len(offsets) - 1
+        line_off = np.zeros(n + 1, dtype=np.int64)
+        line_count = np.zeros(n, dtype=np.int32)
+        occurrences = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        buf = C.c_void_p()
+        check(lib.fmx_match_lines_batch(self._h, chars.ctypes.data, offsets.ctypes.data, n, int(max_lines), line_off.ctypes.data,
+                                        C.byref(buf), line_count.ctypes.data, occurrences.ctypes.data, status.ctypes.data),
+              "fmx_match_lines_batch")
+        total = int(line_off[n])
+        try:  # the library's buffer is copied into an array of NumPy's own and handed back
+            lines = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_int32)), shape=(total,)).copy() if total else np.zeros(0, np.int32)
+        finally:
+            lib.fmx_free_buffer(buf)
+        return (lines, line_off, status, line_count, occurrences) if want_counts else (lines, line_off, status)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -361,6 +406,15 @@ class FmIndex:
         locs, hit_off, status = self.locate_all_batch(sub, np.array([0, len(sub)], dtype=np.int32), maxMatches)
         raise_for_status(status[0])
         return locs
+
+    def match_lines(self, pattern, max_lines=0):
+        """the ids of the lines that hold `pattern`, each once, ascending (grep -n); at most max_lines of them for max_lines > 0"""
+        p = as_chars(pattern)
+        if len(p) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        lines, line_off, status = self.match_lines_batch(p, np.array([0, len(p)], dtype=np.int32), max_lines)
+        raise_for_status(status[0])
+        return lines
 
     def extract(self, start, stop, destination, offset=0):  # FM:564-608
         dst = np.ascontiguousarray(destination, dtype=np.uint16).reshape(1, len(destination))

@@ -1838,6 +1838,15 @@ FMX_HD bool fm_suffix_key(const DevIndex &ix, CodeAt code_at, int len, uint64_t 
 // how many of a pattern's m trailing characters the table may answer: every length from 2 to suffix_chars is tabulated
 FMX_HD int fm_suffix_len(const DevIndex &ix, int32_t m) { return m < ix.suffix_chars ? (int)m : ix.suffix_chars; }
 
+// What bounds a walk over a damaged index.  Every sample_rate-th text position is sampled, so a walk takes < sampleRate steps —
+// unless a quirk of the reference derails it (Q1: a run block's symbol masked to 8 bits sends the walk to another row, from where
+// it goes on to THAT row's next sample; the reference has no bound at all).  256 such stretches are out of reach for a
+// well-formed index and still end a walk over a damaged one in milliseconds instead of `length` steps.
+FMX_HD int32_t fm_walk_limit(const DevIndex &ix) {
+    const int64_t stretches = (int64_t)ix.sample_rate * 256;
+    return (int32_t)(stretches < 4096 ? 4096 : (stretches < (int64_t)ix.length ? stretches : (int64_t)ix.length));
+}
+
 // FM:526-548 for one hit: SA row i = start + 1 + k; LF-walk until a sampled row.
 // Returns the text position; *distance = number of LF-steps walked.
 template <int kWin = kWinAsk>
@@ -1850,12 +1859,7 @@ FMX_HD int32_t fm_locate_hit(const DevIndex &ix, const uint16_t *inv, int32_t st
     // Every round polls sampledSuffixes.access(j - 1) (FM:531) and, if the row is not sampled, runs
     // inverseSelect(j - 1) (FM:532): the bitmap cell and the block's InvHdr depend on j alone and are requested together.
     Quad scell = {0, 0, 0, 0};
-    // Every sample_rate-th text position is sampled, so a walk takes < sampleRate steps — unless a quirk of the reference
-    // derails it (Q1: a run block's symbol masked to 8 bits sends the walk to another row, from where it goes on to THAT
-    // row's next sample; the reference has no bound at all).  256 such stretches are out of reach for a well-formed index
-    // and still end a walk over a damaged one in milliseconds instead of `length` steps.
-    const int64_t stretches = (int64_t)ix.sample_rate * 256;
-    const int32_t walk_limit = (int32_t)(stretches < 4096 ? 4096 : (stretches < (int64_t)ix.length ? stretches : (int64_t)ix.length));
+    const int32_t walk_limit = fm_walk_limit(ix);
     for (;;) {
         const int32_t p = j - 1;
         if (p < 0 || p >= sv.length) {  // RrrVector.access throws (RRR:316-323)
@@ -1920,11 +1924,6 @@ struct WalkState {
     int32_t j, distance;
     int status;
 };
-// (fm_locate_hit: what bounds a walk over a damaged index)
-FMX_HD int32_t fm_walk_limit(const DevIndex &ix) {
-    const int64_t stretches = (int64_t)ix.sample_rate * 256;
-    return (int32_t)(stretches < 4096 ? 4096 : (stretches < (int64_t)ix.length ? stretches : (int64_t)ix.length));
-}
 template <int kForm = kFormAsk>
 FMX_HD bool fm_locate_steps_win(const DevIndex &ix, WalkState &w, int32_t budget, int32_t walk_limit) {
     FMX_NO_UNROLL
@@ -2017,6 +2016,94 @@ FMX_HD int32_t fm_rows_gather(const DevIndex &ix, const uint16_t *inv, int32_t s
     return steps;
 }
 
+// THE TICKET of the locate kernels (k_locate_walk, k_locate_walk_c, k_locate_walk_q; k_locate_rows splits t by its own shift and
+// mask and takes the rest): what launch_locate_walk sizes a call by, and the one statement of how ticket t becomes a pattern's
+// record, its share of the hits, `found` and the store of a hit.  tests/hostsim.cpp and tests/rows_hostsim.cpp drive the same.
+constexpr int kFineWindow = 1024;  // patterns of a window k_plan_fine orders (fmx_kernels.hip)
+constexpr int kWalkLanes = 128;    // lanes of a walk kernel per pattern (at most): two waves
+// hit slots of a pattern's row that a call can fill
+FMX_HHD int32_t fm_locate_slots(int32_t max_matches, int32_t loc_cap) {
+    const int32_t slots = (max_matches > 0 && max_matches < loc_cap) ? max_matches : loc_cap;
+    return slots < 1 ? 1 : slots;
+}
+FMX_HHD int32_t fm_walk_lanes(int32_t slots) { return slots < kWalkLanes ? slots : kWalkLanes; }
+// k_locate_rows: a group of 2^this lanes per pattern, a wave at most
+FMX_HHD int32_t fm_rows_lanes_log2(int32_t slots) {
+    int32_t lanes_log2 = 0;
+    while (lanes_log2 < 6 && (1 << lanes_log2) < slots) ++lanes_log2;
+    return lanes_log2;
+}
+// what a lane holds of a ticket: hits k, k + step, ... below `located` of pattern p, whose range starts at row `start`;
+// before = the hits earlier segments of a set took (0 without `taken`)
+struct LocateTicket {
+    int32_t p, start, k, step, located, before;
+};
+// order (nullable): the batch's records in walk order, the first *order_idle of them with nothing to locate.  WHOLE windows of
+// the fine pass below that mark get one lane per pattern, every other pattern `lanes` lanes.
+FMX_HD int64_t fm_ticket_idle(const void *order, const uint32_t *order_idle) {
+    return order ? (int64_t)(*order_idle / (uint32_t)kFineWindow) * kFineWindow : 0;
+}
+FMX_HD int64_t fm_ticket_total(int64_t idle, int32_t n, int32_t lanes) { return idle + ((int64_t)n - idle) * lanes; }
+// ticket t -> its record, and which of the record's hits it takes
+FMX_HD int64_t fm_ticket_split(int64_t t, int64_t idle, int32_t lanes, int32_t &k, int32_t &step) {
+    k = 0;
+    step = 1;
+    if (t < idle) return t;
+    const int64_t rec = idle + (t - idle) / lanes;
+    k = (int32_t)((t - idle) - (rec - idle) * lanes);
+    step = lanes;
+    return rec;
+}
+// record `rec` (order: 16 bytes {start, end, pattern, -}; without it pattern rec's pair of `range`) and the pattern's share:
+// fills p, start, before, located; returns `wanted`.  taken (nullable; segment sets): taken[p] hits came from earlier segments.
+FMX_HD int32_t fm_ticket_record(LocateTicket &tk, int64_t rec, const int32_t *range, const void *order, int32_t max_matches,
+                                int32_t loc_cap, const int32_t *taken) {
+    tk.p = (int32_t)rec;
+    int32_t end;
+    if (order) {
+        const Quad r = ld_quad(__builtin_assume_aligned(static_cast<const uint8_t *>(order) + 16 * rec, 8));
+        tk.start = (int32_t)r.x;
+        end = (int32_t)r.y;
+        tk.p = (int32_t)r.z;
+    } else {
+        tk.start = range[2 * tk.p];
+        end = range[2 * tk.p + 1];
+    }
+    tk.before = taken ? taken[tk.p] : 0;
+    int32_t wanted;
+    tk.located = fm_locate_share(tk.start, end, max_matches - tk.before, taken != nullptr, loc_cap, wanted);
+    return wanted;
+}
+// (the kernels' lanes share found / lf_steps / status_out rows; the host build runs them one after the other)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FMX_OR_INTO(at, v) atomicOr((at), (v))
+#define FMX_ADD_INTO(at, v) atomicAdd((at), (v))
+#else
+#define FMX_OR_INTO(at, v) ((void)(*(at) |= (v)))
+#define FMX_ADD_INTO(at, v) ((void)(*(at) += (v)))
+#endif
+// the lane that holds a pattern's hit 0 publishes how many hits the call stores, and the reference's overrun of `locations`
+FMX_HD void fm_ticket_publish(int32_t p, int32_t k, int32_t located, int32_t wanted, int32_t loc_cap, int32_t *found,
+                              int32_t *status_out) {
+    if (k != 0) return;
+    found[p] = located;
+    if (wanted > loc_cap && status_out) FMX_OR_INTO(&status_out[p], (int)ST_JAVA_AIOOBE);
+}
+// where hit k of pattern p goes in locs / set_locs: a set's row holds the earlier segments' hits in front
+FMX_HD int64_t fm_ticket_dest(int32_t p, int32_t before, int32_t k, int32_t loc_cap, const int64_t *set_locs) {
+    return (int64_t)p * loc_cap + (set_locs ? before : 0) + k;
+}
+// one finished hit: its position (a set's rows: int64 text positions moved by the segment's start), its LF-steps, its status
+FMX_HD void fm_ticket_store(int64_t dest, int32_t p, int32_t at, int32_t distance, int status, int32_t *locs, int64_t *set_locs,
+                            int64_t set_base, int32_t *lf_steps, int32_t *status_out) {
+    if (set_locs)
+        set_locs[dest] = set_base + at;
+    else
+        locs[dest] = at;
+    if (lf_steps && distance) FMX_ADD_INTO(&lf_steps[p], distance);
+    if (status && status_out) FMX_OR_INTO(&status_out[p], status);
+}
+
 // THE PACKED LAYOUT of "all occurrences" (fmx_locate_all_*; FM:487-552): hit_off[p] = hits of patterns 0 .. p - 1, n + 1 entries,
 // never decreasing.  Hit t of the packed order belongs to the LAST p with hit_off[p] <= t (a pattern without hits has
 // hit_off[p] == hit_off[p + 1]: a run of equal entries ends in the pattern that holds the hit).
@@ -2050,6 +2137,31 @@ FMX_HD int32_t fm_locate_all_resolve(const int64_t *slice, int32_t slice_count, 
     k = (int32_t)(t - slice[i]);
     return p_lo + i;
 }
+// The tile that starts at packed hit `tile` of a window that ends in front of `last`: its last hit, and its patterns
+// [p_lo, p_lo + slice_count) — two searches, the same for every lane of a workgroup (the loads are broadcasts).
+struct HitTile {
+    int64_t tile_last;
+    int32_t p_lo, slice_count;
+};
+FMX_HD HitTile fm_hit_tile(const int64_t *hit_off, int32_t n, int64_t tile, int64_t last) {
+    const int64_t tile_last = (last - tile < kLocateAllTile ? last : tile + kLocateAllTile) - 1;
+    const int32_t p_lo = fm_hit_pattern(hit_off, n, tile);
+    return HitTile{tile_last, p_lo, fm_hit_pattern(hit_off + p_lo, n - p_lo, tile_last) + 1};
+}
+#if defined(__HIPCC__)
+// ... and its slice of hit_off for a workgroup of kBlock lanes: a copy in s_off[kLocateAllSlice] where it fits (in_lds,
+// workgroup-uniform: the caller then ends the tile with a barrier, since the next tile's slice overwrites this one), else
+// hit_off where it lies
+template <int kBlock>
+__device__ __forceinline__ const int64_t *fm_hit_tile_slice(int64_t *s_off, const int64_t *__restrict__ hit_off, const HitTile &h,
+                                                            bool &in_lds) {
+    in_lds = h.slice_count <= kLocateAllSlice;
+    if (!in_lds) return hit_off + h.p_lo;
+    for (int32_t i = threadIdx.x; i < h.slice_count; i += kBlock) s_off[i] = hit_off[h.p_lo + i];
+    __syncthreads();
+    return s_off;
+}
+#endif
 
 // THE LINE TABLE of a resident index (fmx_line_table_build; fmx_hit_lines.hip): T = what locate() returns for the one-character
 // pattern {boundary}, sorted ascending, `count` int32 entries.  line(p) = the number of entries of T below p, for any int32 p:

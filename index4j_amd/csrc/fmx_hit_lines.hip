@@ -3,8 +3,8 @@
 // first k.  The line table T is the sorted answer of locate() for the boundary character (fmx_device.hpp "THE LINE TABLE").
 //
 // Every stage hands lanes to HITS, never to patterns, so a batch of one pattern that matches everywhere uses the whole device:
-//   k_hit_line_keys  a lane per packed hit: its pattern (fm_hit_pattern over an LDS slice of hit_off, as k_locate_all resolves
-//                    it), its line (fm_line_of: the first levels over the fences staged in LDS, the rest in HBM), the 64-bit
+//   k_hit_line_keys  a lane per packed hit: its pattern (fm_hit_pattern over an LDS slice of hit_off: the tile and its slice
+//                    are k_locate_all's, fm_hit_tile / fm_hit_tile_slice), its line (fm_line_of: the first levels over the fences staged in LDS, the rest in HBM), the 64-bit
 //                    key (pattern << line_bits) | line; a slot behind hit_off[n] gets the pattern n, which sorts last
 //   rocPRIM          ONE device-wide radix sort of the keys over the bits in use (not a segmented sort: that would hand a
 //                    pattern of 10^6 hits to one workgroup).  The keys of pattern p then lie at [hit_off[p], hit_off[p + 1])
@@ -53,18 +53,11 @@ __global__ __launch_bounds__(kKeyBlock) void k_hit_line_keys(const int32_t *__re
             if (t < n_hits) keys[t] = fm_line_key(n, 0, line_bits);
             continue;
         }
-        const int64_t tile_last = (total - tile < kLocateAllTile ? total : tile + kLocateAllTile) - 1;
-        const int32_t p_lo = fm_hit_pattern(hit_off, n, tile);
-        const int32_t p_hi = p_lo + fm_hit_pattern(hit_off + p_lo, n - p_lo, tile_last);
-        const int32_t slice_count = p_hi - p_lo + 1;
-        const bool in_lds = slice_count <= kLocateAllSlice;
-        if (in_lds) {
-            for (int32_t i = threadIdx.x; i < slice_count; i += kKeyBlock) s_off[i] = hit_off[p_lo + i];
-            __syncthreads();
-        }
-        const int64_t *slice = in_lds ? s_off : hit_off + p_lo;
-        if (t <= tile_last) {
-            const int32_t p = p_lo + fm_hit_pattern(slice, slice_count, t);
+        const HitTile h = fm_hit_tile(hit_off, n, tile, total);
+        bool in_lds;
+        const int64_t *slice = fm_hit_tile_slice<kKeyBlock>(s_off, hit_off, h, in_lds);
+        if (t <= h.tile_last) {
+            const int32_t p = h.p_lo + fm_hit_pattern(slice, h.slice_count, t);
             keys[t] = fm_line_key(p, fm_line_of(T, count, s_fence, n_fences, shift, locs[t]), line_bits);
         } else if (t < n_hits) {
             keys[t] = fm_line_key(n, 0, line_bits);

@@ -241,7 +241,7 @@ constexpr uint32_t kPlanLongPattern = 0x3fffffu;
 constexpr int kFineBits = 10;  // width of the window-local order of k_plan_fine (counting sort in LDS)
 constexpr int kFineThreads = 512;
 constexpr int kFineItems = 2;
-constexpr int kFineWindow = kFineThreads * kFineItems;  // 1,024 patterns: the window k_plan_fine orders
+static_assert(kFineWindow == kFineThreads * kFineItems, "the window k_plan_fine orders (fmx_device.hpp: 1,024 patterns)");
 
 // recs (nullable): the plan — the batch's records in processing order; lane pair q takes record q (one coalesced
 // 16-byte load, no gather).  plan_look_up (mode 2): code of the plan's alphabet -> character, to translate code
@@ -1098,7 +1098,6 @@ int launch_win_flat(const DevIndex &ix, int n_cu, uint32_t n_pos, uint32_t *flat
 
 // FM:526-548: hit k of pattern p is SA row i = start + 1 + k; walk LF until a sampled row.
 constexpr int kRedoHead = 4;   // ints in front of a redo list's entries ({count, 0, 0, 0}: 16 bytes)
-constexpr int kWalkLanes = 128;  // lanes of k_locate_walk per pattern (at most): two waves
 template <int kBlock, int kWin>
 FMX_WALK_KERNEL(kBlock) void k_locate_walk(DevIndex ix_global, const int32_t *__restrict__ range, int32_t n,
                                                         int32_t max_matches, int32_t *__restrict__ locs,
@@ -1120,53 +1119,22 @@ FMX_WALK_KERNEL(kBlock) void k_locate_walk(DevIndex ix_global, const int32_t *__
     // two waves (with maxMatches 1000 most slots stay empty, and a lane per slot spent its time finding that out: 1 M queries
     // at sampleRate 1 3.3 -> 2.5 ms; a cap of one wave costs maxMatches 100 its second round: +3..+8 %): lane g walks hits g,
     // g + lanes, ... — adjacent lanes walk adjacent SA rows.
-    const int32_t lanes = slots < kWalkLanes ? slots : kWalkLanes;
-    const int64_t idle = order ? (int64_t)(*order_idle / (uint32_t)kFineWindow) * kFineWindow : 0;
-    const int64_t total = idle + ((int64_t)n - idle) * lanes;
+    // The ticket itself — record, share of the hits, `found`, the store of a hit — is fmx_device.hpp's (fm_ticket_*).
+    const int32_t lanes = fm_walk_lanes(slots);
+    const int64_t idle = fm_ticket_idle(order, order_idle);
+    const int64_t total = fm_ticket_total(idle, n, lanes);
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
-        int64_t rec = t;
-        int32_t k = 0, step = 1;
-        if (t >= idle) {
-            rec = idle + (t - idle) / lanes;
-            k = (int32_t)((t - idle) - (rec - idle) * lanes);
-            step = lanes;
-        }
-        int32_t p = (int32_t)rec;
-        int32_t start, end;
-        if (order) {
-            const Quad r = ld_quad(order + rec);
-            start = (int32_t)r.x;
-            end = (int32_t)r.y;
-            p = (int32_t)r.z;
-        } else {
-            start = range[2 * p];
-            end = range[2 * p + 1];
-        }
-        int32_t hits = start < end ? end - start : 0;
-        // segment sets: `taken[p]` hits came from earlier segments, the caller's loop passes maxMatches - taken
-        int32_t limit = max_matches;
-        if (taken) {
-            limit = max_matches - taken[p];
-            if (limit <= 0) hits = 0;
-        }
-        // the reference stops at maxMatches (FM:544-546) and overruns `locations` beyond its length (Java AIOOBE)
-        const int32_t wanted = (limit > 0 && hits > limit) ? limit : hits;
-        const int32_t located = wanted < loc_cap ? wanted : loc_cap;
-        if (k == 0) {
-            found[p] = located;
-            if (wanted > loc_cap && status_out) atomicOr(&status_out[p], ST_JAVA_AIOOBE);
-        }
-        for (; k < located; k += step) {
+        LocateTicket tk;
+        const int64_t rec = fm_ticket_split(t, idle, lanes, tk.k, tk.step);
+        const int32_t wanted = fm_ticket_record(tk, rec, range, order, max_matches, loc_cap, taken);
+        fm_ticket_publish(tk.p, tk.k, tk.located, wanted, loc_cap, found, status_out);
+        for (int32_t k = tk.k; k < tk.located; k += tk.step) {
             int status = ST_OK;
             int32_t distance;
-            const int32_t at = fm_locate_hit<kWin>(ix, s_inv, start, k, distance, status);
-            if (set_locs)
-                set_locs[(int64_t)p * loc_cap + (taken ? taken[p] : 0) + k] = set_base + at;
-            else
-                locs[(int64_t)p * loc_cap + k] = at;
-            if (lf_steps && distance) atomicAdd(&lf_steps[p], distance);
-            if (status && status_out) atomicOr(&status_out[p], status);
+            const int32_t at = fm_locate_hit<kWin>(ix, s_inv, tk.start, k, distance, status);
+            fm_ticket_store(fm_ticket_dest(tk.p, tk.before, k, loc_cap, set_locs), tk.p, at, distance, status, locs, set_locs, set_base,
+                            lf_steps, status_out);
         }
     }
 }
@@ -1186,7 +1154,7 @@ FMX_WALK_KERNEL(256) void k_rows_fill(DevIndex ix_global, uint32_t n_rows, uint3
     }
     if (mine) atomicAdd(replay, mine);
 }
-// k_locate_rows: k_locate_walk's arguments and stores, the hits GATHERED from the row table: a pattern's hits are end - start
+// k_locate_rows: k_locate_walk's arguments, records and shares (fm_ticket_record / _publish), the hits GATHERED from the row table: a pattern's hits are end - start
 // adjacent words.  A group of 2^lanes_log2 lanes per pattern (the launcher sizes it to the slot count: 16 lanes read <= 16 hits
 // as one sector and write one; a whole wave strides over the range where the slots are many), lane g takes hits g, g + lanes, ...
 // A word that says kRowReplay, or a row outside the table, is walked by its lane (fm_rows_hit).  The groups are aligned inside a
@@ -1202,35 +1170,20 @@ __global__ __launch_bounds__(kBlock) void k_locate_rows(DevIndex ix, const int32
     const int64_t total = (int64_t)n << lanes_log2;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
-        const int64_t rec = t >> lanes_log2;
         const int32_t g = (int32_t)(t & (lanes - 1));
-        int32_t p = (int32_t)rec;
-        int32_t start, end;
-        if (order) {  // (the batch's records {start, end, pattern} by the first row of their ranges: launch_locate_walk)
-            const Quad r = ld_quad(order + rec);
-            start = (int32_t)r.x;
-            end = (int32_t)r.y;
-            p = (int32_t)r.z;
-        } else {
-            start = range[2 * p];
-            end = range[2 * p + 1];
-        }
-        const int32_t before = taken ? taken[p] : 0;  // segment sets: hits that came from earlier segments
-        int32_t wanted;
-        const int32_t located = fm_locate_share(start, end, taken ? max_matches - before : max_matches, taken != nullptr, loc_cap, wanted);
-        if (g == 0) {
-            found[p] = located;
-            if (wanted > loc_cap && status_out) atomicOr(&status_out[p], ST_JAVA_AIOOBE);
-        }
+        LocateTicket tk;  // (order: the batch's records by the first row of their ranges, launch_locate_walk)
+        const int32_t wanted = fm_ticket_record(tk, t >> lanes_log2, range, order, max_matches, loc_cap, taken);
+        fm_ticket_publish(tk.p, g, tk.located, wanted, loc_cap, found, status_out);
         int status = ST_OK;
         // (the value-of-offset table of a compact image where it lies, not staged: only a replayed hit reads it)
-        int32_t steps = fm_rows_gather<kWinAsk>(ix, ix.inv_global, start, located, g, lanes, locs + (int64_t)p * loc_cap,
-                                                set_locs ? set_locs + (int64_t)p * loc_cap + before : nullptr, set_base, status);
+        int32_t steps = fm_rows_gather<kWinAsk>(ix, ix.inv_global, tk.start, tk.located, g, lanes, locs + (int64_t)tk.p * loc_cap,
+                                                set_locs ? set_locs + fm_ticket_dest(tk.p, tk.before, 0, loc_cap, set_locs) : nullptr,
+                                                set_base, status);
         if (lf_steps) {
             for (int32_t o = lanes >> 1; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
-            if (g == 0 && steps) atomicAdd(&lf_steps[p], steps);
+            if (g == 0 && steps) atomicAdd(&lf_steps[tk.p], steps);
         }
-        if (status && status_out) atomicOr(&status_out[p], status);
+        if (status && status_out) atomicOr(&status_out[tk.p], status);
     }
 }
 
@@ -1254,22 +1207,15 @@ __device__ __forceinline__ void locate_all_tiles(const DevIndex &ix, const uint1
     const int64_t last = n_hits < total - first_hit ? first_hit + n_hits : total;  // (no first_hit + n_hits beyond 2^63)
     const int lane = threadIdx.x & 63;
     for (int64_t tile = first_hit + (int64_t)blockIdx.x * kLocateAllTile; tile < last; tile += (int64_t)gridDim.x * kLocateAllTile) {
-        const int64_t tile_last = (last - tile < kLocateAllTile ? last : tile + kLocateAllTile) - 1;
-        const int32_t p_lo = fm_hit_pattern(hit_off, n, tile);
-        const int32_t p_hi = p_lo + fm_hit_pattern(hit_off + p_lo, n - p_lo, tile_last);
-        const int32_t slice_count = p_hi - p_lo + 1;
-        const bool in_lds = slice_count <= kLocateAllSlice;
-        if (in_lds) {
-            for (int32_t i = threadIdx.x; i < slice_count; i += kBlock) s_off[i] = hit_off[p_lo + i];
-            __syncthreads();
-        }
-        const int64_t *slice = in_lds ? s_off : hit_off + p_lo;
+        const HitTile h = fm_hit_tile(hit_off, n, tile, last);
+        bool in_lds;
+        const int64_t *slice = fm_hit_tile_slice<kBlock>(s_off, hit_off, h, in_lds);
         for (int32_t i = threadIdx.x; i < kLocateAllTile; i += kBlock) {
             const int64_t t = tile + i;
             int32_t p = -1, steps = 0;
-            if (t <= tile_last) {
+            if (t <= h.tile_last) {
                 int32_t k, distance = 0;
-                p = fm_locate_all_resolve(slice, slice_count, p_lo, t, k);
+                p = fm_locate_all_resolve(slice, h.slice_count, h.p_lo, t, k);
                 const int32_t start = range[2 * (int64_t)p];
                 int status = ST_OK;
                 locs[t - first_hit] = kRows ? fm_rows_hit<kWin>(ix, inv, start, k, distance, status)
@@ -1331,7 +1277,7 @@ int launch_rows_fill(const DevIndex &ix, int n_cu, uint32_t n_rows, uint32_t *ro
 // of its 64 walks meets a sampled row — sample_rate - 1 steps where the average walk takes half of that: half of the wave-steps ran
 // on lanes whose walk was over (profiles/r05_experiments.txt 12).  After an instalment every lane still walking writes its state
 // {row, distance, status, where the position goes} to LDS at its rank among them, the workgroup's first lanes take the states
-// over, and the waves behind them fall through the next instalment.  Same tickets, same stores as k_locate_walk.
+// over, and the waves behind them fall through the next instalment.  The tickets and the stores are k_locate_walk's: fm_ticket_*.
 template <int kBlock, int kForm>
 FMX_WALK_KERNEL(kBlock) void k_locate_walk_c(DevIndex ix_global, const int32_t *__restrict__ range, int32_t n,
                                              int32_t max_matches, int32_t *__restrict__ locs, int32_t loc_cap, int32_t slots,
@@ -1344,9 +1290,9 @@ FMX_WALK_KERNEL(kBlock) void k_locate_walk_c(DevIndex ix_global, const int32_t *
     __shared__ Quad s_state[kBlock];        // {row, distance, status, pattern}
     __shared__ int64_t s_dest[kBlock];      // index of the hit's position in locs / set_locs
     __shared__ uint32_t s_walking[kBlock / 64];
-    const int32_t lanes = slots < kWalkLanes ? slots : kWalkLanes;
-    const int64_t idle = order ? (int64_t)(*order_idle / (uint32_t)kFineWindow) * kFineWindow : 0;
-    const int64_t total = idle + ((int64_t)n - idle) * lanes;
+    const int32_t lanes = fm_walk_lanes(slots);
+    const int64_t idle = fm_ticket_idle(order, order_idle);
+    const int64_t total = fm_ticket_total(idle, n, lanes);
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     const int32_t walk_limit = fm_walk_limit(ix);
     // instalments: two packings — after sample_rate / 2 and 3 sample_rate / 4 steps — or three, after every quarter (option walk_pack)
@@ -1355,58 +1301,25 @@ FMX_WALK_KERNEL(kBlock) void k_locate_walk_c(DevIndex ix_global, const int32_t *
     // (every lane of the workgroup runs the same number of rounds: the barriers below are the workgroup's)
     for (int64_t t0 = (int64_t)blockIdx.x * kBlock; t0 < total; t0 += stride) {
         const int64_t t = t0 + threadIdx.x;
-        const bool have = t < total;
-        int64_t rec = have ? t : 0;
-        int32_t k = 0, step = 1;
-        if (have && t >= idle) {
-            rec = idle + (t - idle) / lanes;
-            k = (int32_t)((t - idle) - (rec - idle) * lanes);
-            step = lanes;
+        LocateTicket tk = {0, 0, 0, 1, 0, 0};  // (a lane behind the last ticket holds none: no hits)
+        if (t < total) {
+            const int64_t rec = fm_ticket_split(t, idle, lanes, tk.k, tk.step);
+            const int32_t wanted = fm_ticket_record(tk, rec, range, order, max_matches, loc_cap, taken);
+            fm_ticket_publish(tk.p, tk.k, tk.located, wanted, loc_cap, found, status_out);
         }
-        int32_t p = (int32_t)rec, start = 0, end = 0, taken_p = 0, located = 0;
-        if (have) {
-            if (order) {
-                const Quad r = ld_quad(order + rec);
-                start = (int32_t)r.x;
-                end = (int32_t)r.y;
-                p = (int32_t)r.z;
-            } else {
-                start = range[2 * p];
-                end = range[2 * p + 1];
-            }
-            int32_t hits = start < end ? end - start : 0;
-            int32_t limit = max_matches;
-            if (taken) {
-                taken_p = taken[p];
-                limit = max_matches - taken_p;
-                if (limit <= 0) hits = 0;
-            }
-            // the reference stops at maxMatches (FM:544-546) and overruns `locations` beyond its length (Java AIOOBE)
-            const int32_t wanted = (limit > 0 && hits > limit) ? limit : hits;
-            located = wanted < loc_cap ? wanted : loc_cap;
-            if (k == 0) {
-                found[p] = located;
-                if (wanted > loc_cap && status_out) atomicOr(&status_out[p], ST_JAVA_AIOOBE);
-            }
-        }
-        for (;; k += step) {  // this ticket's hits k, k + step, ...: a round of the workgroup per hit
-            const bool hit = have && k < located;
+        for (int32_t k = tk.k;; k += tk.step) {  // this ticket's hits k, k + step, ...: a round of the workgroup per hit
+            const bool hit = k < tk.located;
             if (!__syncthreads_or(hit ? 1 : 0)) break;
             // the walk this lane carries (after a packing: another lane's)
-            WalkState w = {start + 1 + k, 0, ST_OK};  // FM:527-529
-            int32_t wp = p;
-            int64_t dest = (int64_t)p * loc_cap + (set_locs ? taken_p : 0) + k;
+            WalkState w = {tk.start + 1 + k, 0, ST_OK};  // FM:527-529
+            int32_t wp = tk.p;
+            int64_t dest = fm_ticket_dest(tk.p, tk.before, k, loc_cap, set_locs);
             bool walking = hit;
             for (int phase = 0; phase <= packings; ++phase) {
                 const int32_t budget = phase == packings ? 0x7fffffff : (phase == 0 ? first : second);
                 if (walking && fm_locate_steps_win<kForm>(ix, w, budget, walk_limit)) {
-                    const int32_t at = fm_locate_finish_win(ix, s_inv, w);
-                    if (set_locs)
-                        set_locs[dest] = set_base + at;
-                    else
-                        locs[dest] = at;
-                    if (lf_steps && w.distance) atomicAdd(&lf_steps[wp], w.distance);
-                    if (w.status && status_out) atomicOr(&status_out[wp], w.status);
+                    fm_ticket_store(dest, wp, fm_locate_finish_win(ix, s_inv, w), w.distance, w.status, locs, set_locs, set_base, lf_steps,
+                                    status_out);
                     walking = false;
                 }
                 if (phase == packings) break;
@@ -1447,7 +1360,7 @@ FMX_WALK_KERNEL(kBlock) void k_locate_walk_c(DevIndex ix_global, const int32_t *
 // packing).  Here a wave owns a run of `chunk` consecutive tickets and hands them out itself: every `burst` steps the lanes whose
 // walk is over take the next hit of their ticket, or the next tickets of the run (a ballot and a prefix count: no LDS, no
 // barrier), and walk on beside the lanes still under way.  A lane idles for half a burst per walk instead of half a walk.
-// Same tickets, same stores as k_locate_walk: which lane walks which hit is free (results go to the hit's own slot).
+// The tickets and the stores are k_locate_walk's (fm_ticket_*): which lane walks which hit is free (results go to the hit's own slot).
 template <int kBlock, int kForm>
 FMX_WALK_KERNEL(kBlock) void k_locate_walk_q(DevIndex ix, const int32_t *__restrict__ range, int32_t n, int32_t max_matches,
                                              int32_t *__restrict__ locs, int32_t loc_cap, int32_t slots,
@@ -1456,9 +1369,9 @@ FMX_WALK_KERNEL(kBlock) void k_locate_walk_q(DevIndex ix, const int32_t *__restr
                                              const PlanRec *__restrict__ order, const uint32_t *__restrict__ order_idle,
                                              int64_t *__restrict__ set_locs, int64_t set_base, int32_t chunk, int32_t burst) {
     FMX_FM_INV(ix);
-    const int32_t lanes = slots < kWalkLanes ? slots : kWalkLanes;
-    const int64_t idle = order ? (int64_t)(*order_idle / (uint32_t)kFineWindow) * kFineWindow : 0;
-    const int64_t total = idle + ((int64_t)n - idle) * lanes;
+    const int32_t lanes = fm_walk_lanes(slots);
+    const int64_t idle = fm_ticket_idle(order, order_idle);
+    const int64_t total = fm_ticket_total(idle, n, lanes);
     const int32_t walk_limit = fm_walk_limit(ix);
     const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
     const int64_t wave_id = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -1466,8 +1379,8 @@ FMX_WALK_KERNEL(kBlock) void k_locate_walk_q(DevIndex ix, const int32_t *__restr
     for (int64_t run = wave_id * chunk; run < total; run += waves * chunk) {
         int64_t next = run;  // wave-uniform: the run's first ticket not handed out yet
         const int64_t run_end = run + chunk < total ? run + chunk : total;
-        // the ticket a lane holds: hits k, k + step, ... < located of pattern p; and the walk it carries
-        int32_t p = 0, start = 0, k = 0, step = 1, located = 0, taken_p = 0;
+        // the ticket a lane holds (tk.k: the hit it is at), and the walk it carries
+        LocateTicket tk = {0, 0, 0, 1, 0, 0};
         bool walking = false;
         WalkState w = {0, 0, ST_OK};
         for (;;) {
@@ -1475,53 +1388,23 @@ FMX_WALK_KERNEL(kBlock) void k_locate_walk_q(DevIndex ix, const int32_t *__restr
             // ticket, and takes a new ticket when that one is done (or there was none yet)
             bool need = false;
             if (!walking) {
-                k += step;
-                need = k >= located;
+                tk.k += tk.step;
+                need = tk.k >= tk.located;
             }
             const unsigned long long ball = __ballot(need ? 1 : 0);
             const int64_t mine = next + (int64_t)__popcll(ball & below);
             next += (int64_t)__popcll(ball);
             if (need) {
-                located = 0;  // (no ticket left for this lane: it idles until the run is walked)
-                k = 0;
+                tk.located = 0;  // (no ticket left for this lane: it idles until the run is walked)
+                tk.k = 0;
                 if (mine < run_end) {
-                    int64_t rec = mine;
-                    step = 1;
-                    if (mine >= idle) {
-                        rec = idle + (mine - idle) / lanes;
-                        k = (int32_t)((mine - idle) - (rec - idle) * lanes);
-                        step = lanes;
-                    }
-                    p = (int32_t)rec;
-                    int32_t end;
-                    if (order) {
-                        const Quad r = ld_quad(order + rec);
-                        start = (int32_t)r.x;
-                        end = (int32_t)r.y;
-                        p = (int32_t)r.z;
-                    } else {
-                        start = range[2 * p];
-                        end = range[2 * p + 1];
-                    }
-                    int32_t hits = start < end ? end - start : 0;
-                    int32_t limit = max_matches;
-                    taken_p = 0;
-                    if (taken) {  // segment sets: `taken[p]` hits came from earlier segments (the caller's loop passes maxMatches - taken)
-                        taken_p = taken[p];
-                        limit = max_matches - taken_p;
-                        if (limit <= 0) hits = 0;
-                    }
-                    // the reference stops at maxMatches (FM:544-546) and overruns `locations` beyond its length (Java AIOOBE)
-                    const int32_t wanted = (limit > 0 && hits > limit) ? limit : hits;
-                    located = wanted < loc_cap ? wanted : loc_cap;
-                    if (k == 0) {
-                        found[p] = located;
-                        if (wanted > loc_cap && status_out) atomicOr(&status_out[p], ST_JAVA_AIOOBE);
-                    }
+                    const int64_t rec = fm_ticket_split(mine, idle, lanes, tk.k, tk.step);
+                    const int32_t wanted = fm_ticket_record(tk, rec, range, order, max_matches, loc_cap, taken);
+                    fm_ticket_publish(tk.p, tk.k, tk.located, wanted, loc_cap, found, status_out);
                 }
             }
-            if (!walking && k < located) {
-                w.j = start + 1 + k;  // FM:527-529
+            if (!walking && tk.k < tk.located) {
+                w.j = tk.start + 1 + tk.k;  // FM:527-529
                 w.distance = 0;
                 w.status = ST_OK;
                 walking = true;
@@ -1531,14 +1414,8 @@ FMX_WALK_KERNEL(kBlock) void k_locate_walk_q(DevIndex ix, const int32_t *__restr
                 continue;
             }
             if (walking && fm_locate_steps_win<kForm>(ix, w, burst, walk_limit)) {
-                const int32_t at = fm_locate_finish_win(ix, s_inv, w);
-                const int64_t dest = (int64_t)p * loc_cap + (set_locs ? taken_p : 0) + k;
-                if (set_locs)
-                    set_locs[dest] = set_base + at;
-                else
-                    locs[dest] = at;
-                if (lf_steps && w.distance) atomicAdd(&lf_steps[p], w.distance);
-                if (w.status && status_out) atomicOr(&status_out[p], w.status);
+                fm_ticket_store(fm_ticket_dest(tk.p, tk.before, tk.k, loc_cap, set_locs), tk.p, fm_locate_finish_win(ix, s_inv, w),
+                                w.distance, w.status, locs, set_locs, set_base, lf_steps, status_out);
                 walking = false;
             }
         }
@@ -2732,8 +2609,7 @@ int launch_locate_walk(const DevIndex &ix, int n_cu, const int32_t *range, int32
                        const int32_t *taken, void *workspace, size_t workspace_bytes, bool head_is_zero, hipStream_t st,
                        int64_t *set_locs, int64_t set_base) {
     if (n <= 0) return 0;
-    int32_t slots = (max_matches > 0 && max_matches < loc_cap) ? max_matches : loc_cap;
-    if (slots < 1) slots = 1;
+    const int32_t slots = fm_locate_slots(max_matches, loc_cap);
     const PlanRec *order = nullptr;
     const uint32_t *order_idle = nullptr;
     // (a row table: the hits are gathered, not walked — in the caller's order unless option "rows_order" asks for the walk order)
@@ -2765,13 +2641,12 @@ int launch_locate_walk(const DevIndex &ix, int n_cu, const int32_t *range, int32
         order_idle = ticket + 1;
     }
     if (ix.rows) {  // a row table: k_locate_rows, a group of lanes per pattern sized to the slot count (a wave at most)
-        int lanes_log2 = 0;
-        while (lanes_log2 < 6 && (1 << lanes_log2) < slots) ++lanes_log2;
+        const int32_t lanes_log2 = fm_rows_lanes_log2(slots);
         FMX_DISPATCH(k_locate_rows, (int64_t)n << lanes_log2, ix, range, n, max_matches, locs, loc_cap, lanes_log2, found, lf, status, taken,
                      order, set_locs, set_base);
         return (int)hipGetLastError();
     }
-    const int64_t tickets = (int64_t)n * (slots < kWalkLanes ? slots : kWalkLanes);
+    const int64_t tickets = (int64_t)n * fm_walk_lanes(slots);
     // a window directory and many hits per pattern: the ticket-queue form (k_locate_walk_q).  Measured (round 6, profiles/r06_experiments.txt
     // 3): locate(100) of the reference-shaped series 2.47 -> 2.14-2.26 ms; with <= 16 hits per pattern the hand-out's record loads cost
     // more than the idle lanes they save (configs[2] 0.247 -> 0.34 ms, locate(1) 1.09 -> 1.14): those keep the packed form below

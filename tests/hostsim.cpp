@@ -339,45 +339,50 @@ int64_t sim_count_table(const uint8_t *blob, int32_t chars, const uint16_t *pat,
     return (int64_t)entries;
 }
 
-// mirrors k_locate_walk
-void sim_locate_walk(const uint8_t *blob, const int32_t *range, int32_t n, int32_t max_matches, int32_t *locs,
-                     int32_t loc_cap, int32_t *found, int32_t *lf, int32_t *status_out) {
+int32_t sim_fine_window() { return kFineWindow; }
+int32_t sim_walk_lanes() { return kWalkLanes; }
+
+// mirrors launch_locate_walk's sizes and the ticket loop of k_locate_walk / k_locate_walk_c / k_locate_walk_q: every ticket t of
+// [0, total) one after the other through the header's own split, record, publish and store (fm_ticket_*), a ticket's hits walked to
+// their end in turn.  order (nullable): 4 ints per record {start, end, pattern, -}, the first *order_idle of them with nothing to
+// locate; taken (nullable) / set_locs (nullable) / set_base: a segment of a set.  Returns the lanes a pattern gets.
+int32_t sim_locate_walk(const uint8_t *blob, const int32_t *range, int32_t n, int32_t max_matches, int32_t *locs, int32_t loc_cap,
+                        int32_t *found, int32_t *lf, int32_t *status_out, const int32_t *taken = nullptr, const int32_t *order = nullptr,
+                        const uint32_t *order_idle = nullptr, int64_t *set_locs = nullptr, int64_t set_base = 0) {
     DevIndex ix = make_index(blob);
-    int32_t slots = (max_matches > 0 && max_matches < loc_cap) ? max_matches : loc_cap;
-    if (slots < 1) slots = 1;
-    for (int32_t p = 0; p < n; ++p)
-        for (int32_t k = 0; k < slots; ++k) {
-            const int32_t start = range[2 * p], end = range[2 * p + 1];
-            const int32_t hits = start < end ? end - start : 0;
-            const int32_t wanted = (max_matches > 0 && hits > max_matches) ? max_matches : hits;
-            const int32_t located = wanted < loc_cap ? wanted : loc_cap;
-            if (k == 0) {
-                found[p] = located;
-                if (wanted > loc_cap && status_out) status_out[p] |= ST_JAVA_AIOOBE;
-            }
-            if (k >= located) continue;
+    const int32_t lanes = fm_walk_lanes(fm_locate_slots(max_matches, loc_cap));
+    const int64_t idle = fm_ticket_idle(order, order_idle);
+    const int64_t total = fm_ticket_total(idle, n, lanes);
+    for (int64_t t = 0; t < total; ++t) {
+        LocateTicket tk;
+        const int64_t rec = fm_ticket_split(t, idle, lanes, tk.k, tk.step);
+        const int32_t wanted = fm_ticket_record(tk, rec, range, order, max_matches, loc_cap, taken);
+        fm_ticket_publish(tk.p, tk.k, tk.located, wanted, loc_cap, found, status_out);
+        for (int32_t k = tk.k; k < tk.located; k += tk.step) {
             int status = ST_OK;
-            int32_t distance;
+            int32_t distance, at;
             if (ix.win && g_pack && ix.sample_rate >= 8) {
                 // (as launch_locate_walk picks over a window directory: k_locate_walk_c — the walk in instalments of sample_rate / 2,
                 // sample_rate / 4 steps and the rest, as the kernel takes them between its packings)
-                WalkState w = {start + 1 + k, 0, ST_OK};
+                WalkState w = {tk.start + 1 + k, 0, ST_OK};
                 const int32_t limit = fm_walk_limit(ix);
                 // (the kernel's instantiation for the directory's form: FMX_DISPATCH_FORM)
                 auto steps = [&](int32_t budget) {
                     return ix.win_flat ? fm_locate_steps_win<kFormFlat>(ix, w, budget, limit) : fm_locate_steps_win<kFormCells>(ix, w, budget, limit);
                 };
                 if (!steps(ix.sample_rate / 2) && !steps(ix.sample_rate / 4)) (void)steps(0x7fffffff);
-                locs[(int64_t)p * loc_cap + k] = fm_locate_finish_win(ix, ix.inv_global, w);
+                at = fm_locate_finish_win(ix, ix.inv_global, w);
                 distance = w.distance;
                 status = w.status;
             } else
-            locs[(int64_t)p * loc_cap + k] = ix.win_flat ? fm_locate_hit<kWinFlat>(ix, ix.inv_global, start, k, distance, status)  // (as launch_locate_walk picks)
-                                             : ix.win    ? fm_locate_hit<kWinAlways>(ix, ix.inv_global, start, k, distance, status)
-                                                         : fm_locate_hit<kWinNever>(ix, ix.inv_global, start, k, distance, status);
-            if (lf) lf[p] += distance;
-            if (status && status_out) status_out[p] |= status;
+                at = ix.win_flat ? fm_locate_hit<kWinFlat>(ix, ix.inv_global, tk.start, k, distance, status)  // (as launch_locate_walk picks)
+                     : ix.win    ? fm_locate_hit<kWinAlways>(ix, ix.inv_global, tk.start, k, distance, status)
+                                 : fm_locate_hit<kWinNever>(ix, ix.inv_global, tk.start, k, distance, status);
+            fm_ticket_store(fm_ticket_dest(tk.p, tk.before, k, loc_cap, set_locs), tk.p, at, distance, status, locs, set_locs, set_base, lf,
+                            status_out);
         }
+    }
+    return lanes;
 }
 
 void sim_extract(const uint8_t *blob, const int32_t *starts, const int32_t *stops, int32_t n, uint16_t *dst,

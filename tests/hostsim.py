@@ -159,14 +159,20 @@ class HostSim:
                                         C.c_void_p(lf.ctypes.data), C.c_void_p(st.ctypes.data), C.c_void_p(answered.ctypes.data))
         return counts, st, lf, int(answered[0]), int(entries)
 
-    def locate_batch(self, chars, offsets, max_matches, loc_cap):
+    def locate_batch(self, chars, offsets, max_matches, loc_cap, taken=None, order=None, order_idle=None, set_locs=None, set_base=0):
+        """the count phase, then the walk kernels' ticket loop (sim_locate_walk).  order: int32 [n, 4] records {start, end, pattern, -}
+        in walk order, the first `order_idle` of them with nothing to locate; taken (int32 [n]) / set_locs (int64 [n, loc_cap],
+        written in place) / set_base: a segment of a set"""
         counts, st, lf, rng = self.count_batch(chars, offsets)
         n = len(counts)
         locs = np.zeros((n, max(loc_cap, 0)), np.int32)
         found = np.zeros(n, np.int32)
-        self.L.sim_locate_walk(C.c_void_p(self.p), C.c_void_p(rng.ctypes.data), n, max_matches,
-                              C.c_void_p(locs.ctypes.data), loc_cap, C.c_void_p(found.ctypes.data),
-                              C.c_void_p(lf.ctypes.data), C.c_void_p(st.ctypes.data))
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        taken = None if taken is None else np.ascontiguousarray(taken, np.int32)
+        order = None if order is None else np.ascontiguousarray(order, np.int32)
+        idle = None if order is None else np.array([order_idle or 0], np.uint32)
+        self.L.sim_locate_walk(C.c_void_p(self.p), ptr(rng), n, max_matches, ptr(locs), loc_cap, ptr(found), ptr(lf), ptr(st),
+                               ptr(taken), ptr(order), ptr(idle), ptr(set_locs), C.c_int64(set_base))
         return locs, found, st, lf
 
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None):

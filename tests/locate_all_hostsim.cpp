@@ -1,5 +1,5 @@
 // locate_all_hostsim.cpp — TEST-ONLY host build of the device code of "all occurrences, packed" (fmx_locate_all_*):
-// index4j_amd/csrc/fmx_device.hpp's fm_locate_all_hits, fm_hit_pattern, fm_locate_all_resolve and the one-hit functions
+// index4j_amd/csrc/fmx_device.hpp's fm_locate_all_hits, fm_hit_pattern, fm_hit_tile, fm_locate_all_resolve and the one-hit functions
 // fm_locate_hit / fm_rows_hit, driven by a mirror of k_locate_all's tile loop (fmx_kernels.hip) with the lanes run one after
 // the other.  g++ compiles the header's FMX_HD functions as plain C++, so the CPU suite checks the very source the kernel runs
 // against the oracle (tests/test_locate_all_cpu.py).  The image's view, the window directory and the row table come from
@@ -55,24 +55,21 @@ int64_t sim_locate_all(const uint8_t *blob, const uint32_t *rows, const int32_t 
     std::vector<int32_t> lane_p(64), lane_steps(64);
     for (int64_t group = 0; group < grid; ++group) {
         for (int64_t tile = first_hit + group * kLocateAllTile; tile < last; tile += (int64_t)grid * kLocateAllTile) {
-            const int64_t tile_last = (last - tile < kLocateAllTile ? last : tile + kLocateAllTile) - 1;
-            const int32_t p_lo = fm_hit_pattern(hit_off, n, tile);
-            const int32_t p_hi = p_lo + fm_hit_pattern(hit_off + p_lo, n - p_lo, tile_last);
-            const int32_t slice_count = p_hi - p_lo + 1;
-            const bool in_lds = slice_count <= slice_max;
+            const HitTile h = fm_hit_tile(hit_off, n, tile, last);
+            const bool in_lds = h.slice_count <= slice_max;  // (fm_hit_tile_slice, with the caller's bound)
             if (in_lds)
-                for (int32_t i = 0; i < slice_count; ++i) s_off[(size_t)i] = hit_off[p_lo + i];
+                for (int32_t i = 0; i < h.slice_count; ++i) s_off[(size_t)i] = hit_off[h.p_lo + i];
             else
                 ++global_tiles;
-            const int64_t *slice = in_lds ? s_off.data() : hit_off + p_lo;
+            const int64_t *slice = in_lds ? s_off.data() : hit_off + h.p_lo;
             for (int32_t round = 0; round < kLocateAllTile; round += block) {
                 for (int32_t wave = 0; wave < block; wave += 64) {
                     for (int32_t lane = 0; lane < 64; ++lane) {
                         const int64_t t = tile + round + wave + lane;
                         int32_t p = -1, steps = 0;
-                        if (t <= tile_last) {
+                        if (t <= h.tile_last) {
                             int32_t k, distance = 0;
-                            p = fm_locate_all_resolve(slice, slice_count, p_lo, t, k);
+                            p = fm_locate_all_resolve(slice, h.slice_count, h.p_lo, t, k);
                             int status = ST_OK;
                             locs[t - first_hit] = all_hit(ix, range[2 * (int64_t)p], k, distance, status);
                             steps = distance;

@@ -3,9 +3,9 @@
 // fm_bits, fm_line_key and its unpacking, fm_line_head — with fm_hit_pattern for a hit's pattern — driven by a mirror of the
 // stages of fmx_hit_lines.hip with the lanes run one after the other (the device-wide radix sort = std::sort on the keys, the
 // scans = running sums).  g++ compiles the header's functions as plain C++, so the CPU suite checks the source of those FUNCTIONS
-// (tests/test_match_lines_cpu.py).  NOT mirrored: k_hit_line_keys' tile loop — p_lo / p_hi, the LDS slice of hit_off and the
-// search of hit_off where it lies for a tile of more than kLocateAllSlice patterns — which copies k_locate_all's
-// (tests/locate_all_hostsim.cpp mirrors that one); here a hit's pattern is ONE fm_hit_pattern over the whole of hit_off.  The
+// (tests/test_match_lines_cpu.py).  NOT mirrored: k_hit_line_keys' tile loop — the tile's patterns, the LDS slice of hit_off and
+// the search of hit_off where it lies for a tile of more than kLocateAllSlice patterns — which is k_locate_all's (fm_hit_tile;
+// tests/locate_all_hostsim.cpp mirrors that loop); here a hit's pattern is ONE fm_hit_pattern over the whole of hit_off.  The
 // kernel's own route runs in tests/test_gpu_match_lines.py only.  Never part of libfmx.so.
 #include "../index4j_amd/csrc/fmx_device.hpp"
 

@@ -1,5 +1,6 @@
 // rows_hostsim.cpp — TEST-ONLY host build of the row table's device code (index4j_amd/csrc/fmx_device.hpp: fm_row_word,
-// fm_locate_share, fm_rows_hit, fm_rows_gather — what k_rows_fill and k_locate_rows of fmx_kernels.hip run).
+// fm_ticket_record / fm_ticket_publish (fm_locate_share), fm_rows_hit, fm_rows_gather — what k_rows_fill and k_locate_rows of
+// fmx_kernels.hip run).
 //
 // g++ compiles the header's FMX_HD functions as plain C++, so the CPU suite checks the very source the kernels run against the
 // oracle (tests/test_locate_rows_cpu.py).  Everything else a resident index has — the image's view, the window directory in its
@@ -52,42 +53,27 @@ void sim_row_walk_all(const uint8_t *blob, int32_t *at, int32_t *distance, int32
 }
 
 // mirrors launch_locate_walk's row-table branch + k_locate_rows: a group of 2^lanes_log2 lanes per pattern, lane g takes hits
-// g, g + lanes, ...; the lanes of a group run one after the other here.  order (nullable): 4 ints per record {start, end, pattern, -}.
+// g, g + lanes, ...; the lanes of a group run one after the other here, each through the header's record, share and publish
+// (fm_ticket_*).  order (nullable): 4 ints per record {start, end, pattern, -}.
 // set_locs (nullable) / set_base / taken (nullable): a segment of a set.  Returns the group's width.
 int32_t sim_locate_rows(const uint8_t *blob, const uint32_t *rows, const int32_t *range, int32_t n, int32_t max_matches, int32_t *locs,
                         int32_t loc_cap, int32_t *found, int32_t *lf, int32_t *status_out, const int32_t *taken, const int32_t *order,
                         int64_t *set_locs, int64_t set_base) {
     const DevIndex ix = rows_index(blob, rows);
-    int32_t slots = (max_matches > 0 && max_matches < loc_cap) ? max_matches : loc_cap;
-    if (slots < 1) slots = 1;
-    int lanes_log2 = 0;
-    while (lanes_log2 < 6 && (1 << lanes_log2) < slots) ++lanes_log2;
+    const int32_t lanes_log2 = fm_rows_lanes_log2(fm_locate_slots(max_matches, loc_cap));
     const int32_t lanes = 1 << lanes_log2;
     const int64_t total = (int64_t)n << lanes_log2;
     for (int64_t t = 0; t < total; ++t) {
-        const int64_t rec = t >> lanes_log2;
         const int32_t g = (int32_t)(t & (lanes - 1));
-        int32_t p = (int32_t)rec, start, end;
-        if (order) {
-            start = order[4 * rec];
-            end = order[4 * rec + 1];
-            p = order[4 * rec + 2];
-        } else {
-            start = range[2 * p];
-            end = range[2 * p + 1];
-        }
-        const int32_t before = taken ? taken[p] : 0;
-        int32_t wanted;
-        const int32_t located = fm_locate_share(start, end, taken ? max_matches - before : max_matches, taken != nullptr, loc_cap, wanted);
-        if (g == 0) {
-            found[p] = located;
-            if (wanted > loc_cap && status_out) status_out[p] |= ST_JAVA_AIOOBE;
-        }
+        LocateTicket tk;
+        const int32_t wanted = fm_ticket_record(tk, t >> lanes_log2, range, order, max_matches, loc_cap, taken);
+        fm_ticket_publish(tk.p, g, tk.located, wanted, loc_cap, found, status_out);
         int status = ST_OK;
-        const int32_t steps = fm_rows_gather<kWinAsk>(ix, ix.inv_global, start, located, g, lanes, locs + (int64_t)p * loc_cap,
-                                                      set_locs ? set_locs + (int64_t)p * loc_cap + before : nullptr, set_base, status);
-        if (lf) lf[p] += steps;
-        if (status && status_out) status_out[p] |= status;
+        const int32_t steps = fm_rows_gather<kWinAsk>(ix, ix.inv_global, tk.start, tk.located, g, lanes, locs + (int64_t)tk.p * loc_cap,
+                                                      set_locs ? set_locs + fm_ticket_dest(tk.p, tk.before, 0, loc_cap, set_locs) : nullptr,
+                                                      set_base, status);
+        if (lf) lf[tk.p] += steps;
+        if (status && status_out) status_out[tk.p] |= status;
     }
     return lanes;
 }

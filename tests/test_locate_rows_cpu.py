@@ -311,7 +311,8 @@ def test_rows_outside_the_table_and_marked_rows_are_walked(simdir):
         locs, found, lf, st = np.full((5, 8), -7, np.int32), np.zeros(5, np.int32), np.zeros(5, np.int32), np.zeros(5, np.int32)
         sim.L.sim_locate_rows(sim.p, ptr(table), ptr(rng), 5, -1, ptr(locs), 8, ptr(found), ptr(lf), ptr(st), None, None, None, C.c_int64(0))
         walk = np.full((5, 8), -7, np.int32), np.zeros(5, np.int32), np.zeros(5, np.int32), np.zeros(5, np.int32)
-        sim.L.sim_locate_walk(sim.p, ptr(rng), 5, -1, ptr(walk[0]), 8, ptr(walk[1]), ptr(walk[2]), ptr(walk[3]))
+        sim.L.sim_locate_walk(sim.p, ptr(rng), 5, -1, ptr(walk[0]), 8, ptr(walk[1]), ptr(walk[2]), ptr(walk[3]), None, None, None, None,
+                              C.c_int64(0))
         assert (locs == walk[0]).all() and (found == walk[1]).all() and (lf == walk[2]).all() and (st == walk[3]).all()
         out.append(locs)
     assert (out[0] == out[1]).all() and st[0] == 9 and st[3] == 0
@@ -336,6 +337,173 @@ def test_segment_stores_carry_taken_and_base(simdir):
         n, l = ref.locate(p, max_matches=left, cap=cap) if left > 0 else (0, np.zeros(0, np.int32))
         assert found[i] == n and (set_locs[i, taken[i]:taken[i] + n] == l.astype(np.int64) + (1 << 33)).all()
         assert (set_locs[i, :taken[i]] == -7).all() and (set_locs[i, taken[i] + n:] == -7).all()
+
+
+# THE TICKET (fmx_device.hpp fm_ticket_*, fm_locate_slots, fm_walk_lanes, fm_rows_lanes_log2): what k_locate_walk, k_locate_walk_c,
+# k_locate_walk_q and k_locate_rows make of ticket t — run here by sim_locate_walk and sim_locate_rows over one small index, at
+# sample rates 1 and 8, over the tree (fm_locate_hit<kWinNever>) and over a window directory (fm_locate_hit<kWinAlways> at rate 1,
+# the instalment walk at rate 8).
+TICKET_TEXT = HD[:6_000]
+TICKET_ROUTES = [(1, None), (1, 4), (8, None), (8, 4)]
+_TICKET = {}
+
+
+class TicketSim:
+    """an index over `text`, its patterns' ranges and count-phase results, and the oracle's locate() per shape, each made once"""
+
+    def __init__(self, simdir, text, sr, form, pats):
+        self.sim = RowsSim(simdir, text, sr)
+        self.sim.directory(form)
+        self.rows, _ = self.sim.fill()
+        self.ref = orc.OracleFmIndex(text, sr, True)
+        self.pats = pats
+        ch, off = ia.pack_patterns(pats)
+        self.counts, self.st0, self.lf0, rng = self.sim.count(ch, off)
+        self.rng = rng.reshape(-1, 2)
+        self._oracle = {}
+
+    def oracle(self, mm, cap):
+        """per pattern (found, positions, LF-steps of the whole locate() or None, status) as check_locate_against_oracle reads them"""
+        if (mm, cap) not in self._oracle:
+            out = []
+            for p in self.pats:
+                orc.counters_reset()
+                try:
+                    n, l = self.ref.locate(p, max_matches=mm, cap=cap)
+                    out.append((n, l, orc.counters()["lf_steps"], 0))
+                except IndexError:  # more hits wanted than `locations` holds (Java AIOOBE): the first loc_cap are stored
+                    n, l = self.ref.locate(p, max_matches=cap, cap=cap)
+                    out.append((cap, l, None, 9))
+            self._oracle[(mm, cap)] = out
+        return self._oracle[(mm, cap)]
+
+    def walk(self, which, mm, cap, order=None, order_idle=0, taken=None, set_locs=None, set_base=0, rows=False):
+        """sim_locate_walk (or sim_locate_rows) over patterns `which` (indices into self.pats, the caller's order of this call);
+        returns (locs, found, status, LF-steps, lanes per pattern)"""
+        which = np.asarray(which)
+        n = len(which)
+        rng = np.ascontiguousarray(self.rng[which])
+        lf, st = self.lf0[which].copy(), self.st0[which].copy()
+        locs, found = np.full((n, max(cap, 0)), -7, np.int32), np.full(n, -7, np.int32)
+        if rows:
+            lanes = self.sim.L.sim_locate_rows(self.sim.p, ptr(self.rows), ptr(rng), n, int(mm), ptr(locs), int(cap), ptr(found), ptr(lf),
+                                               ptr(st), ptr(taken), ptr(order), ptr(set_locs), C.c_int64(set_base))
+        else:
+            idle = np.array([order_idle], np.uint32)
+            lanes = self.sim.L.sim_locate_walk(self.sim.p, ptr(rng), n, int(mm), ptr(locs), int(cap), ptr(found), ptr(lf), ptr(st),
+                                               ptr(taken), ptr(order), ptr(idle) if order is not None else None, ptr(set_locs),
+                                               C.c_int64(set_base))
+        return locs, found, st, lf, lanes
+
+    def check(self, which, mm, cap, got):
+        locs, found, st, lf, _ = got
+        want = self.oracle(mm, cap)
+        for i, j in enumerate(which):
+            n, l, steps, status = want[j]
+            assert st[i] == status and found[i] == n and (locs[i, :n] == l[:n]).all(), (i, j, mm, cap)
+            assert (locs[i, n:] == -7).all()  # nothing stored beyond the hits
+            assert steps is None or lf[i] == steps, (i, j, mm, cap)
+
+
+def ticket_sim(simdir, sr, form):
+    if (sr, form) not in _TICKET:
+        t16 = ia.as_chars(TICKET_TEXT)
+        pats = sample_patterns(t16, np.random.default_rng(77), 30)
+        _TICKET[(sr, form)] = TicketSim(simdir, TICKET_TEXT, sr, form, pats)
+    return _TICKET[(sr, form)]
+
+
+@pytest.mark.parametrize("sr,form", TICKET_ROUTES)
+def test_walk_order_with_an_idle_prefix(simdir, sr, form):
+    """Records sorted by `start`, the patterns with nothing to locate first, *order_idle = their count: the walk kernels give WHOLE
+    windows of kFineWindow such records one lane each and every other record `lanes` lanes.  A prefix of 0 windows (0, 1,
+    kFineWindow - 1 idle records), of exactly one (kFineWindow, kFineWindow + 1) and of two with a remainder (2 kFineWindow + 3)."""
+    ts = ticket_sim(simdir, sr, form)
+    window = int(ts.sim.L.sim_fine_window())
+    assert window == 1024
+    hit = np.flatnonzero(ts.rng[:, 0] < ts.rng[:, 1])
+    none = np.flatnonzero(ts.rng[:, 0] >= ts.rng[:, 1])
+    assert len(hit) > 20 and len(none) >= 1
+    mm, cap = 5, 8  # five lanes per pattern: ticket -> record is a division, not a shift
+    rnd = np.random.default_rng(5)
+    for n_idle in (0, 1, window - 1, window, window + 1, 2 * window + 3):
+        which = np.concatenate([hit, none[rnd.integers(0, len(none), n_idle)]])
+        which = which[rnd.permutation(len(which))]  # the caller's order: idle patterns anywhere
+        start, end = ts.rng[which, 0], ts.rng[which, 1]
+        idle = np.flatnonzero(start >= end)
+        busy = np.flatnonzero(start < end)
+        by = np.concatenate([idle, busy[np.argsort(start[busy], kind="stable")]])
+        order = np.zeros((len(which), 4), np.int32)
+        order[:, 0], order[:, 1], order[:, 2] = start[by], end[by], by
+        assert len(idle) == n_idle
+        plain = ts.walk(which, mm, cap)
+        ordered = ts.walk(which, mm, cap, order=order, order_idle=n_idle)
+        assert plain[4] == ordered[4] == 5
+        for a, b in zip(plain[:4], ordered[:4]):
+            assert (a == b).all(), n_idle
+        ts.check(which, mm, cap, ordered)
+
+
+@pytest.mark.parametrize("sr,form", TICKET_ROUTES)
+def test_slots_up_to_and_beyond_the_walk_lanes(simdir, sr, form):
+    """slots = maxMatches where it is positive and below the capacity, else the capacity, at least 1; a pattern gets
+    min(slots, kWalkLanes) lanes and lane g walks hits g, g + lanes, ...: 1 and 2 lanes, kWalkLanes - 1, kWalkLanes itself, and
+    one slot more than lanes.  (-1, 128): every pattern with more than 128 hits, and no other, raises the reference's AIOOBE."""
+    ts = ticket_sim(simdir, sr, form)
+    cap_lanes = int(ts.sim.L.sim_walk_lanes())
+    assert cap_lanes == 128
+    assert int(ts.counts.max()) > 2 * cap_lanes  # a pattern whose lanes take a second and a third hit each
+    which = np.arange(len(ts.pats))
+    for slots, (mm, cap) in ((1, (1, 1)), (2, (2, 5)), (127, (127, 200)), (128, (-1, 128)), (129, (129, 129))):
+        got = ts.walk(which, mm, cap)
+        assert got[4] == min(slots, cap_lanes), (mm, cap)
+        ts.check(which, mm, cap, got)
+        if mm == -1:
+            over = ts.counts > cap
+            assert over.any() and not over.all()
+            assert ((got[2] == 9) == over).all() and (got[2][~over] == 0).all()
+        via_rows = ts.walk(which, mm, cap, rows=True)  # the gather: the same share, publish and stores
+        assert via_rows[4] == min(1 << (slots - 1).bit_length(), 64)
+        for a, b in zip(got[:4], via_rows[:4]):
+            assert (a == b).all(), (mm, cap)
+
+
+@pytest.mark.parametrize("sr,form", TICKET_ROUTES)
+def test_two_segments_of_a_set_share_one_row(simdir, sr, form):
+    """Segment 0, then segment 1 with taken = segment 0's `found`, both into one set_locs: maxMatches less what segment 0 took.
+    Patterns that segment 0 exhausts (limit <= 0 in segment 1), that segment 1 cuts in the middle, and that neither cuts."""
+    texts = (TICKET_TEXT, HD[6_000:12_000])
+    t16 = ia.as_chars(texts[0])
+    pats = sample_patterns(t16, np.random.default_rng(78), 30) + [ia.as_chars(p) for p in ("blk_", "INFO", "dfs", "Receiving")]
+    key = ("set", sr, form)
+    if key not in _TICKET:
+        _TICKET[key] = [TicketSim(simdir, text, sr, form, pats) for text in texts]
+    segs = _TICKET[key]
+    mm = cap = 10  # (a set's rows hold maxMatches slots)
+    c0, c1 = segs[0].counts.astype(np.int64), segs[1].counts.astype(np.int64)
+    exhausted, cut, untouched = c0 >= mm, (c0 > 0) & (c0 < mm) & (c0 + c1 > mm), (c0 > 0) & (c1 > 0) & (c0 + c1 < mm)
+    assert exhausted.any() and cut.any() and untouched.any()
+    which = np.arange(len(pats))
+    bases = (0, 1 << 33)
+    runs = []
+    for rows in (False, True):
+        set_locs = np.full((len(pats), cap), -7, np.int64)
+        first = segs[0].walk(which, mm, cap, set_locs=set_locs, set_base=bases[0], rows=rows)
+        taken = first[1].copy()
+        second = segs[1].walk(which, mm, cap, taken=taken, set_locs=set_locs, set_base=bases[1], rows=rows)
+        for i, p in enumerate(pats):
+            n0, l0 = segs[0].ref.locate(p, max_matches=mm, cap=cap)
+            left = mm - n0
+            n1, l1 = segs[1].ref.locate(p, max_matches=left, cap=cap) if left > 0 else (0, np.zeros(0, np.int32))
+            assert first[1][i] == n0 and second[1][i] == n1 and first[2][i] == 0 and second[2][i] == 0, i
+            assert (set_locs[i, :n0] == l0[:n0].astype(np.int64) + bases[0]).all(), i
+            assert (set_locs[i, n0:n0 + n1] == l1[:n1].astype(np.int64) + bases[1]).all(), i
+            assert (set_locs[i, n0 + n1:] == -7).all(), i
+            assert (n1 == 0) if exhausted[i] else (n0 + n1 == mm) if cut[i] else True
+        assert (first[0] == -7).all() and (second[0] == -7).all()  # nothing goes to `locs` when a set's rows take the hits
+        runs.append((set_locs, first[1], first[2], first[3], second[1], second[2], second[3]))
+    for a, b in zip(*runs):  # the walk and the gather agree: rows, found, statuses, LF-steps
+        assert (a == b).all()
 
 
 def test_option_and_info_on_handles_without_a_table():

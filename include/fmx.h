@@ -224,6 +224,31 @@ int fmx_match_lines_batch(const fmx_index *idx, const uint16_t *pat, const int32
  * start = stop = -1.  Host buffers, synchronous.  FMX_E_ARG without a line table. */
 int fmx_line_bounds_batch(const fmx_index *idx, const int32_t *lines, int32_t n, int32_t *start, int32_t *stop);
 
+/* THE LINES THAT MATCH A QUERY OF SEVERAL TERMS — the host form of fmx_locate_all_ranges_dev + fmx_locate_all_fill_dev (every
+ * hit, no limit) + fmx_query_lines_of_hits_dev (below: what a query is, the rules, the key-width limit).  The batch holds n
+ * TERMS, packed as everywhere (pat, pat_off), cut into q queries by query_off (q + 1 ints, query_off[0] = 0, never decreasing,
+ * query_off[q] = n); term_kind[t] = FMX_TERM_ALL, FMX_TERM_ANY or FMX_TERM_NONE.  Needs a line table (fmx_line_table_build).
+ * host buffers, synchronous: line_off = q + 1 int64 (out), the exclusive sum of max_lines > 0 ? min(line_count, max_lines) :
+ * line_count (max_lines -1 and 0: every line); *lines = line_off[q] ints owned by the library until
+ * fmx_free_buffer((uint8_t *)*lines) (NULL when there are none, and on every failure): (*lines)[line_off[Q] .. line_off[Q + 1]) =
+ * the line ids of query Q, ascending, each once — with a limit the smallest max_lines of them; line_count[Q] (nullable, q
+ * entries) = ALL lines of query Q whatever the limit; occurrences[t] (nullable, n entries) = count() of term t; status[t]
+ * (nullable, n entries) as fmx_locate_all_batch leaves it (an empty pattern: FMX_ST_JAVA_AIOOBE and no hits — as an ALL term it
+ * empties its query, as a NONE term it filters nothing).  q queries of ONE ALL term each give, array for array, what
+ * fmx_match_lines_batch gives for those patterns.  What comes down from the device is the lines of the QUERIES, not the hits
+ * and not the lines of the terms.  Device scratch grows with the batch's hits, no windows in this version: 48 bytes per hit
+ * (positions 4, lines 4, fmx_query_lines_of_hits_dev's workspace 40) plus rocPRIM's temporary storage: FMX_E_NOMEM when it, or
+ * the result, cannot be allocated.  FMX_E_ARG for null or negative arguments, a query_off that does not start at 0, decreases
+ * or does not end at n, a kind above 2, an index without a line table (fmx_last_error names fmx_line_table_build), a batch of
+ * more than 2^31 - 1 hits, a key of more than 64 bits, a SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE
+ * for a handle that is not resident.  n == 0 with q > 0 (queries without terms) is a batch like any other: no lines. */
+#define FMX_TERM_ALL 0
+#define FMX_TERM_ANY 1
+#define FMX_TERM_NONE 2
+int fmx_match_query_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const int32_t *query_off,
+                          const uint8_t *term_kind, int32_t q, int32_t max_lines, int64_t *line_off, int32_t **lines,
+                          int32_t *line_count, int32_t *occurrences, int32_t *status);
+
 /* int extract(int start, int stop, char[] destination, int offset) FM:564-608.  dst is n rows of
  * dst_len chars (row i = the `destination` array of query i, in/out); out_len[i] = return value. */
 int fmx_extract_batch(const fmx_index *idx, const int32_t *start, const int32_t *stop, int32_t n, uint16_t *dst,
@@ -342,6 +367,44 @@ int fmx_lines_of_hits_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_
 /* the grids fmx_lines_of_hits_dev launches for n_hits hits on this index's device: workgroups of the key kernel (a tile of 1,024
  * hits each, per round) and of the element-wise kernels (256 lanes); what is beyond them is taken by grid-stride loops */
 int fmx_hit_lines_geometry(const fmx_index *idx, int64_t n_hits, int32_t *key_grid, int32_t *flat_grid);
+/* PACKED HITS OF A BATCH OF TERMS -> THE PACKED DISTINCT LINES OF EACH QUERY.  The n patterns of the two packed stages are TERMS;
+ * query_off (q + 1 ints: query_off[0] = 0, never decreasing, query_off[q] = n) cuts them into q queries, and term_kind[t] says
+ * what term t asks of a line: FMX_TERM_ALL (0) the line must hold it, FMX_TERM_ANY (1) the line must hold at least one of its
+ * query's ANY terms (if the query has any), FMX_TERM_NONE (2) the line must not hold it.  With lines(t) = exactly what
+ * fmx_lines_of_hits_dev answers for pattern t without a limit (a hit belongs to the line of its first character; the line table
+ * is what the index answers), the lines of query Q are
+ *     the intersection of lines(t) over Q's ALL terms, intersected with the union of lines(t) over Q's ANY terms if Q has any,
+ *     less the union of lines(t) over Q's NONE terms;
+ * ascending, every line once.  A query without an ALL and without an ANY term — only NONE terms, or no terms — has NO lines:
+ * NONE filters, it does not enumerate the text.  The same pattern may stand twice in a query: two terms.  A term without hits
+ * (an empty pattern among them) empties its query as an ALL term and filters nothing as a NONE term.
+ * query_off and term_kind are HOST arrays, here too (as seg_base is in the segment forms): the call validates them, derives its
+ * tables from them (the query of every term, the ALL and ANY terms of every query) and has copied those into d_ws when it
+ * returns — the caller may free or change the arrays at once.  That copy is the one thing the call waits for (a copy from
+ * pageable host memory: the runtime has read the source when the call comes back); nothing else is synchronised, nothing is
+ * allocated on the device, everything runs on `stream`.
+ * Input: exactly what fmx_locate_all_ranges_dev (max_matches = -1) and fmx_locate_all_fill_dev leave — d_hit_off (n + 1 entries)
+ * and d_locs, which holds hits [0, n_hits) of the packed order, n_hits >= d_hit_off[n].  Output: d_line_count[Q] (nullable, q
+ * entries) = the lines of query Q; d_line_off (q + 1 int64) = the exclusive sum of max_lines > 0 ? min(line_count, max_lines) :
+ * line_count; d_lines[d_line_off[Q] .. d_line_off[Q + 1]) = the line ids of query Q, ascending (with a limit: the smallest
+ * max_lines of them).  The caller gives d_lines room for n_hits ints (there are never more lines than hits); entries from
+ * d_line_off[q] on keep the caller's values.
+ * Lanes are handed to hits, to sorted keys or to (query, line) groups in every stage: a key query | line | term per hit, ONE
+ * device-wide radix sort, a word per distinct key (an ALL count and two flags), a reduction by (query, line), a scan, a
+ * compaction — ONE query whose terms match everywhere uses the whole device, and the result does not depend on scheduling.
+ * THE KEY-WIDTH LIMIT: bits(q) + bits(|T|) + bits(the largest number of terms in one query) <= 64, where bits(v) is the number
+ * of binary digits of v (1 for 0) and |T| the boundaries of the line table; the per-group word itself sets no smaller limit.
+ * d_ws: at least fmx_query_lines_scratch_bytes(n, q, n_hits) bytes (40 per hit — two key arrays, the group heads and their
+ * words, 8 each; flags and their scan, 4 each — plus the tables and rocPRIM's temporary storage; 0 for an empty call).
+ * q == 0 or n_hits == 0 (n == 0 among them): the q + 1 offsets are zeroed and nothing else is written.  FMX_E_ARG for null or
+ * negative arguments, a bad query_off (see above), a kind above 2, a workspace that is too small (nothing is launched, nothing
+ * is written), an index without a line table (fmx_last_error names fmx_line_table_build), n_hits > 2^31 - 1, the key-width
+ * limit, a SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident. */
+size_t fmx_query_lines_scratch_bytes(int32_t n, int32_t q, int64_t n_hits);
+int fmx_query_lines_of_hits_dev(const fmx_index *idx, int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind,
+                                const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int32_t max_lines,
+                                int64_t *d_line_off, int32_t *d_lines, int32_t *d_line_count, void *d_ws, size_t ws_bytes,
+                                void *stream);
 int fmx_extract_batch_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n,
                           uint16_t *d_dst, int32_t dst_len, int32_t offset, int32_t *d_out_len,
                           int32_t *d_lf_steps, int32_t *d_status, void *stream);

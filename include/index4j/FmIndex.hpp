@@ -211,6 +211,55 @@ public:
         if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
         return matchLinesBatch({pattern}, maxLines).lines;
     }
+    // the lines that match a QUERY of several terms (fmx.h "THE LINES THAT MATCH A QUERY OF SEVERAL TERMS"): a line must hold every
+    // term of `all`, at least one of `any` (if there are any) and none of `none`; a query without `all` and `any` has no lines.
+    // matchQueryBatch: lines[offsets[Q] .. offsets[Q + 1]) are those of query Q, ascending; lineCount per query, occurrences per
+    // term, in the order all, any, none of query 0, then query 1 ...
+    struct Query {
+        std::vector<std::u16string> all, any, none;
+    };
+    Lines matchQueryBatch(const std::vector<Query> &queries, int maxLines = 0) const {
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        for (const Query &qu : queries) {
+            const std::vector<std::u16string> *groups[3] = {&qu.all, &qu.any, &qu.none};
+            for (int k = 0; k < 3; ++k)
+                for (const std::u16string &t : *groups[k]) {
+                    terms.push_back(t);
+                    kind.push_back((uint8_t)k);
+                }
+            queryOff.push_back((int32_t)terms.size());
+        }
+        std::vector<uint16_t> chars;
+        std::vector<int32_t> off;
+        pack(terms, chars, off);
+        const int32_t n = (int32_t)terms.size(), q = (int32_t)queries.size();
+        Lines out;
+        out.offsets.assign((size_t)q + 1, 0);
+        out.lineCount.assign(queries.size(), 0);
+        out.occurrences.assign(terms.size(), 0);
+        std::vector<int32_t> status(terms.size());
+        int32_t *buf = nullptr;
+        detail::check(fmx_match_query_batch(h_, chars.data(), off.data(), n, queryOff.data(), kind.data(), q, maxLines, out.offsets.data(), &buf,
+                                            out.lineCount.data(), out.occurrences.data(), status.data()),
+                      "fmx_match_query_batch");
+        try {
+            if (buf) out.lines.assign(buf, buf + out.offsets[(size_t)q]);
+        } catch (...) {
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+            throw;
+        }
+        fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+        for (int s : status) detail::raise_for_status(s);
+        return out;
+    }
+    std::vector<int32_t> matchQuery(const Query &query, int maxLines = 0) const {
+        for (const std::vector<std::u16string> *g : {&query.all, &query.any, &query.none})
+            for (const std::u16string &t : *g)
+                if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        return matchQueryBatch({query}, maxLines).lines;
+    }
 
     // locate, then extract(loc, min(getInputLength(), loc + extractLength), row, 0) per hit, both on the device:
     // the composite the reference times in locateAndExtractBenchmark (FmIndexThroughputBenchmark.java:231-249).

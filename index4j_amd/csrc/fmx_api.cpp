@@ -1887,6 +1887,53 @@ int fmx_lines_of_hits_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_
     });
 }
 
+// ---- a query of several terms: packed hits -> the lines of each query (fmx_query_lines.hip) -------------------------------------
+// the HOST arrays that describe the queries: query_off (q + 1) starts at 0, never decreases, ends at n; every kind is 0, 1 or 2
+static int check_queries(int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind) {
+    if (n < 0 || q < 0 || !query_off || (n > 0 && !term_kind)) return fail(FMX_E_ARG, "bad arguments");
+    if (query_off[0] != 0) return fail(FMX_E_ARG, "query_off does not start at 0");
+    for (int32_t i = 0; i < q; ++i)
+        if (query_off[i + 1] < query_off[i]) return fail(FMX_E_ARG, "query_off decreases at query " + std::to_string(i));
+    if (query_off[q] != n) return fail(FMX_E_ARG, "query_off does not end at the number of terms");
+    for (int32_t t = 0; t < n; ++t)
+        if (term_kind[t] > 2) return fail(FMX_E_ARG, "term " + std::to_string(t) + " has a kind above 2");
+    return FMX_OK;
+}
+static int check_query_key_width(const fmx_index *idx, int32_t q, const int32_t *query_off) {
+    const int32_t bits = fmx::fm_query_key_width(q, idx->line_count, fmx::query_lines_max_terms(q, query_off));
+    if (bits > 64) return fail(FMX_E_ARG, "the key query | line | term would take " + std::to_string(bits) + " bits (at most 64)");
+    return FMX_OK;
+}
+
+size_t fmx_query_lines_scratch_bytes(int32_t n, int32_t q, int64_t n_hits) { return fmx::query_lines_scratch_bytes(n, q, n_hits); }
+
+int fmx_query_lines_of_hits_dev(const fmx_index *idx, int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind,
+                                const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int32_t max_lines, int64_t *d_line_off,
+                                int32_t *d_lines, int32_t *d_line_count, void *d_ws, size_t ws_bytes, void *stream) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || q < 0 || n_hits < 0 || !d_line_off || !query_off || (n > 0 && (!d_hit_off || !term_kind)) ||
+        (n > 0 && q > 0 && n_hits > 0 && (!d_locs || !d_lines)))
+        return fail(FMX_E_ARG, "bad arguments");
+    if (n_hits > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one call");
+    int rc = check_queries(n, q, query_off, term_kind);
+    if (rc) return rc;
+    if ((rc = require_fm_device(idx))) return rc;
+    if ((rc = require_line_table(idx))) return rc;
+    if ((rc = check_query_key_width(idx, q, query_off))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (q == 0 || n == 0 || n_hits == 0) {
+        HIP_TRY(hipMemsetAsync(d_line_off, 0, ((size_t)q + 1) * sizeof(int64_t), st));
+        return FMX_OK;
+    }
+    if (!d_ws || ws_bytes < fmx::query_lines_scratch_bytes(n, q, n_hits))
+        return fail(FMX_E_ARG, "the workspace is smaller than fmx_query_lines_scratch_bytes");
+    int e = fmx::launch_query_lines(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_cu, n, q, query_off, term_kind,
+                                    d_hit_off, d_locs, n_hits, max_lines, d_line_off, d_lines, d_line_count, d_ws, ws_bytes, stream);
+    if (e) return fail(FMX_E_HIP, std::string("lines of queries: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+    });
+}
+
 int fmx_extract_batch_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n,
                           uint16_t *d_dst, int32_t dst_len, int32_t offset, int32_t *d_out_len, int32_t *d_lf_steps,
                           int32_t *d_status, void *stream) {
@@ -3108,6 +3155,98 @@ int fmx_match_lines_batch(const fmx_index *idx, const uint16_t *pat, const int32
     }
     HIP_TRY(hipMemcpyAsync(line_off, d_loff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
     if (line_count) HIP_TRY(hipMemcpyAsync(line_count, d_lcnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (occurrences) HIP_TRY(hipMemcpyAsync(occurrences, d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *lines = result.p;
+    result.p = nullptr;
+    return FMX_OK;
+    });
+}
+
+// The host form of "which lines match each QUERY": fmx_match_lines_batch's sequence with the query stage in place of
+// launch_lines_of_hits — the range stage, ONE 8-byte read of the hit total, the fill, fmx_query_lines_of_hits_dev's stages, ONE 8-byte
+// read of the line total, the result malloc'ed to that size.  What comes down is the lines of the queries.
+int fmx_match_query_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const int32_t *query_off,
+                          const uint8_t *term_kind, int32_t q, int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t *line_count,
+                          int32_t *occurrences, int32_t *status) {
+    return guarded([&]() -> int {
+    if (lines) *lines = nullptr;
+    if (!idx || n < 0 || q < 0 || !line_off || !lines || !query_off || (n > 0 && (!pat_off || !term_kind)))
+        return fail(FMX_E_ARG, "bad arguments");
+    int rc = check_queries(n, q, query_off, term_kind);
+    if (rc) return rc;
+    if ((rc = require_fm_device(idx))) return rc;
+    if ((rc = require_line_table(idx))) return rc;
+    if ((rc = check_query_key_width(idx, q, query_off))) return rc;
+    if (n == 0) {  // queries without terms: no lines
+        for (int32_t i = 0; i <= q; ++i) line_off[i] = 0;
+        for (int32_t i = 0; i < q && line_count; ++i) line_count[i] = 0;
+        return FMX_OK;
+    }
+    HIP_TRY(hipSetDevice(idx->device));
+    rc = check_offsets(pat_off, n);
+    if (rc) return rc;
+    const size_t chars = (size_t)(pat_off[n] > 0 ? pat_off[n] : 0), first = first_char(pat_off);
+    if (chars > first && !pat) return fail(FMX_E_ARG, "bad arguments");
+    DevBuf d_pat, d_off, d_hit, d_cnt, d_st, d_rng, d_loff, d_lcnt, d_locs, d_lines, d_ws;
+    HIP_TRY(d_pat.alloc(chars * 2 + 8));
+    HIP_TRY(d_off.alloc((size_t)(n + 1) * 4));
+    HIP_TRY(d_hit.alloc((size_t)(n + 1) * 8));
+    HIP_TRY(d_loff.alloc((size_t)(q + 1) * 8));
+    HIP_TRY(d_cnt.alloc((size_t)n * 4));
+    HIP_TRY(d_lcnt.alloc((size_t)q * 4 + 4));
+    if (status) HIP_TRY(d_st.alloc((size_t)n * 4));
+    HIP_TRY(d_rng.alloc((size_t)n * 8));
+    PipeStreams *ps = nullptr;
+    rc = pipe_streams(idx->device, &ps);
+    if (rc) return rc;
+    hipStream_t st = ps->s[1];
+    Scratch scratch(idx, st, true);
+    struct Result {  // (as in fmx_locate_all_batch)
+        hipStream_t s;
+        int32_t *p = nullptr;
+        ~Result() {
+            (void)hipStreamSynchronize(s);
+            free(p);
+        }
+    } result{st};
+    if (chars > first) HIP_TRY(hipMemcpyAsync(d_pat.as<uint16_t>() + first, pat + first, (chars - first) * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off.p, pat_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
+    int32_t *dst_ = status ? d_st.as<int32_t>() : nullptr;
+    rc = locate_all_ranges_impl(idx, d_pat.as<uint16_t>(), d_off.as<int32_t>(), n, -1, d_hit.as<int64_t>(), nullptr, dst_, d_rng.as<int32_t>(),
+                                scratch, d_cnt.as<int32_t>());
+    if (rc) return rc;
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_hit.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
+    int64_t n_out = 0;
+    if (total > 0 && q > 0) {
+        const size_t ws_bytes = fmx::query_lines_scratch_bytes(n, q, total);
+        if ((rc = alloc_for_hits(d_locs, (size_t)total * 4))) return rc;
+        if ((rc = alloc_for_hits(d_lines, (size_t)total * 4))) return rc;
+        if ((rc = alloc_for_hits(d_ws, ws_bytes))) return rc;
+        int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_rng.as<int32_t>(), d_hit.as<int64_t>(), n, (int64_t)0, total,
+                                    d_locs.as<int32_t>(), nullptr, dst_, st);
+        if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
+        e = fmx::launch_query_lines(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_cu, n, q, query_off, term_kind,
+                                    d_hit.as<int64_t>(), d_locs.as<int32_t>(), total, max_lines, d_loff.as<int64_t>(), d_lines.as<int32_t>(),
+                                    d_lcnt.as<int32_t>(), d_ws.p, d_ws.bytes, st);
+        if (e) return fail(FMX_E_HIP, std::string("lines of queries: ") + hipGetErrorString((hipError_t)e));
+        HIP_TRY(hipMemcpyAsync(&n_out, d_loff.as<int64_t>() + q, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        HIP_TRY(hipMemsetAsync(d_loff.p, 0, (size_t)(q + 1) * 8, st));
+        HIP_TRY(hipMemsetAsync(d_lcnt.p, 0, (size_t)q * 4 + 4, st));
+    }
+    if (n_out > 0) {
+        result.p = static_cast<int32_t *>(malloc((size_t)n_out * 4));
+        if (!result.p) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(n_out) + " lines");
+        HIP_TRY(hipMemcpyAsync(result.p, d_lines.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(line_off, d_loff.p, (size_t)(q + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (line_count && q > 0) HIP_TRY(hipMemcpyAsync(line_count, d_lcnt.p, (size_t)q * 4, hipMemcpyDeviceToHost, st));
     if (occurrences) HIP_TRY(hipMemcpyAsync(occurrences, d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));

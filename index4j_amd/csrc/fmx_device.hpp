@@ -2234,6 +2234,63 @@ FMX_HD bool fm_line_head(const uint64_t *keys, int64_t i, int32_t n, int32_t lin
     return fm_line_key_pattern(keys[i], line_bits) < n && (i == 0 || keys[i] != keys[i - 1]);
 }
 
+// A QUERY OF SEVERAL TERMS (fmx_query_lines_of_hits_dev; fmx_query_lines.hip): the n patterns of a batch are TERMS, cut into q
+// queries by query_off (q + 1 entries); term t has a kind.  A line belongs to query Q iff it holds every ALL term of Q, at least
+// one of Q's ANY terms if Q has any, and no NONE term of Q — and Q has an ALL or an ANY term at all (NONE filters, it does not
+// enumerate the text).
+constexpr int32_t kTermAll = 0, kTermAny = 1, kTermNone = 2;
+// The sort key of one packed hit: query | line | term index inside its query, most significant first, so that ONE device-wide
+// sort orders the batch by query, then by line, and the keys of one (query, line) GROUP lie together with equal keys — several
+// hits of one term on one line — next to each other.  query in [0, q] (q marks a slot behind hit_off[n]: it sorts last), line
+// in [0, count], term in [0, the largest number of terms of one query): fm_query_key_width bits, at most 64.
+FMX_HHD int32_t fm_query_key_width(int32_t q, int32_t count, int32_t max_terms) {
+    return fm_bits((uint32_t)q) + fm_bits((uint32_t)count) + fm_bits((uint32_t)max_terms);
+}
+FMX_HD uint64_t fm_query_key(int32_t query, int32_t line, int32_t term, int32_t line_bits, int32_t term_bits) {
+    return (((((uint64_t)(uint32_t)query) << line_bits) | (uint32_t)line) << term_bits) | (uint32_t)term;
+}
+FMX_HD uint64_t fm_query_key_group(uint64_t key, int32_t term_bits) { return key >> term_bits; }  // (query, line)
+FMX_HD int32_t fm_query_key_query(uint64_t key, int32_t line_bits, int32_t term_bits) { return (int32_t)(key >> (line_bits + term_bits)); }
+FMX_HD int32_t fm_query_key_line(uint64_t key, int32_t line_bits, int32_t term_bits) {
+    return (int32_t)((key >> term_bits) & (((uint64_t)1 << line_bits) - 1));
+}
+FMX_HD int32_t fm_query_key_term(uint64_t key, int32_t term_bits) { return (int32_t)(key & (((uint64_t)1 << term_bits) - 1)); }
+// What one (query, line) group has seen, in one 64-bit word: the number of distinct ALL terms in the low 32 bits (a query has
+// fewer than 2^31 terms), "an ANY term" in bit 32, "a NONE term" in bit 33.  fm_query_word_join is associative and commutative
+// over such words (the count adds, the flags OR), so a segmented reduction over a group may join them in any order.
+constexpr uint64_t kQueryWordAny = (uint64_t)1 << 32, kQueryWordNone = (uint64_t)1 << 33;
+FMX_HD uint64_t fm_query_word(int32_t kind) { return kind == kTermAll ? 1 : kind == kTermAny ? kQueryWordAny : kQueryWordNone; }
+FMX_HHD uint64_t fm_query_word_join(uint64_t a, uint64_t b) {
+    return (((a & 0xffffffffu) + (b & 0xffffffffu)) & 0xffffffffu) | ((a | b) & (kQueryWordAny | kQueryWordNone));
+}
+// sorted key i contributes its term's word when it is a hit's key (query < q) that differs from its predecessor — a distinct
+// (query, line, term) triple; a repeated key (the term's second hit on the line) and a slot behind the hits contribute nothing.
+// query_off / term_kind: the batch's tables (the kind of term `term` of query Q is term_kind[query_off[Q] + term]).
+FMX_HD uint64_t fm_query_contribution(const uint64_t *keys, int64_t i, int32_t q, int32_t line_bits, int32_t term_bits,
+                                      const int32_t *query_off, const uint8_t *term_kind) {
+    const uint64_t key = keys[i];
+    const int32_t query = fm_query_key_query(key, line_bits, term_bits);
+    if (query >= q || (i > 0 && keys[i - 1] == key)) return 0;
+    return fm_query_word(term_kind[query_off[query] + fm_query_key_term(key, term_bits)]);
+}
+// the group matches its query, which has n_all ALL terms and n_any ANY terms
+FMX_HD bool fm_query_matches(uint64_t word, int32_t n_all, int32_t n_any) {
+    return (int64_t)(word & 0xffffffffu) == n_all && (n_any == 0 || (word & kQueryWordAny)) && !(word & kQueryWordNone) &&
+           (int64_t)n_all + n_any > 0;
+}
+// the first of the n_groups ascending group heads (full keys, the first of each group) whose query is not below `query`
+FMX_HD int64_t fm_query_first_group(const uint64_t *group_key, int64_t n_groups, int32_t query, int32_t line_bits, int32_t term_bits) {
+    int64_t lo = 0, hi = n_groups;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (fm_query_key_query(group_key[mid], line_bits, term_bits) < query)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
 // up to four characters of one aligned 8-byte group of a destination row (mask: which of them): one store when all four are there
 FMX_HD void fm_flush_chars(uint16_t *group_at, uint64_t group, uint32_t mask) {
     if (mask == 0xfu) {

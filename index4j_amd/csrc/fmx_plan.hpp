@@ -65,4 +65,14 @@ int launch_lines_of_hits(const int32_t *T, int32_t count, int n_cu, int32_t n, c
 constexpr int kHitLinesKeyGroupsPerCu = 2, kHitLinesFlatGroupsPerCu = 8;
 void hit_lines_geometry(int64_t n_hits, int n_cu, int32_t *key_grid, int32_t *flat_grid);
 
+// fmx_query_lines.hip — packed hits of a batch of terms -> the packed distinct lines of each QUERY (fmx_query_lines_of_hits_dev).
+// Compiled once.  query_off (q + 1) and term_kind (n) are HOST arrays the caller has validated; the tables made from them are
+// copied into the workspace before the launcher returns.  The grids are hit_lines_geometry's.  hipErrorInvalidValue before anything
+// is launched or written: too small a workspace, n_hits beyond 2^31 - 1, a key of more than 64 bits (fm_query_key_width).
+size_t query_lines_scratch_bytes(int32_t n, int32_t q, int64_t n_hits);
+int32_t query_lines_max_terms(int32_t q, const int32_t *query_off);  // the largest number of terms of one query
+int launch_query_lines(const int32_t *T, int32_t count, int n_cu, int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind,
+                       const int64_t *hit_off, const int32_t *locs, int64_t n_hits, int32_t max_lines, int64_t *line_off, int32_t *lines,
+                       int32_t *line_count, void *ws, size_t ws_bytes, void *stream);
+
 }  // namespace fmx

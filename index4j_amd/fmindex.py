@@ -302,6 +302,35 @@ class FmIndex:
             lib.fmx_free_buffer(buf)
         return (lines, line_off, status, line_count, occurrences) if want_counts else (lines, line_off, status)
 
+    def match_query_batch(self, chars, offsets, query_off, term_kind, max_lines=0, want_counts=False):
+        """the lines of every QUERY of several terms, packed and ascending (fmx_match_query_batch): the patterns (chars, offsets)
+        are terms, query_off (q + 1 entries, from 0 to the number of terms) cuts them into queries, term_kind[t] is 0 ALL (the
+        line must hold the term), 1 ANY (at least one of the query's ANY terms), 2 NONE (the line must not hold it); a query
+        without an ALL or ANY term has no lines.  Those of query Q are lines[line_off[Q]:line_off[Q + 1]], at most max_lines of
+        them for max_lines > 0.  Returns (lines, line_off, status[, line_count, occurrences]): status and occurrences per TERM,
+        line_count per query (all its lines whatever the limit)."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        query_off = np.ascontiguousarray(query_off, dtype=np.int32)
+        term_kind = np.ascontiguousarray(term_kind, dtype=np.uint8)
+        n, q = len(offsets) - 1, len(query_off) - 1
+        if len(term_kind) != n:
+            raise ValueError("term_kind has %d entries for %d terms" % (len(term_kind), n))
+        line_off = np.zeros(q + 1, dtype=np.int64)
+        line_count = np.zeros(q, dtype=np.int32)
+        occurrences = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        buf = C.c_void_p()
+        check(lib.fmx_match_query_batch(self._h, chars.ctypes.data, offsets.ctypes.data, n, query_off.ctypes.data, term_kind.ctypes.data, q,
+                                        int(max_lines), line_off.ctypes.data, C.byref(buf), line_count.ctypes.data, occurrences.ctypes.data,
+                                        status.ctypes.data), "fmx_match_query_batch")
+        total = int(line_off[q])
+        try:  # the library's buffer is copied into an array of NumPy's own and handed back
+            lines = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_int32)), shape=(total,)).copy() if total else np.zeros(0, np.int32)
+        finally:
+            lib.fmx_free_buffer(buf)
+        return (lines, line_off, status, line_count, occurrences) if want_counts else (lines, line_off, status)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -414,6 +443,22 @@ class FmIndex:
             raise IndexError("ArrayIndexOutOfBoundsException")
         lines, line_off, status = self.match_lines_batch(p, np.array([0, len(p)], dtype=np.int32), max_lines)
         raise_for_status(status[0])
+        return lines
+
+    def match_query(self, all=(), any=(), none=(), max_lines=0):  # noqa: A002 (the words of the query)
+        """the ids of the lines that hold every pattern of `all`, at least one of `any` (if given) and none of `none`, each once,
+        ascending; at most max_lines of them for max_lines > 0.  Without `all` and `any` there are no lines (`none` filters)."""
+        terms, kinds = [], []
+        for kind, group in enumerate((all, any, none)):  # (a lone str is one term)
+            for p in ([group] if isinstance(group, str) else group):
+                terms.append(as_chars(p))
+                kinds.append(kind)
+        if min((len(t) for t in terms), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        chars, offsets = pack_patterns(terms)
+        lines, line_off, status = self.match_query_batch(chars, offsets, [0, len(terms)], np.array(kinds, np.uint8), max_lines)
+        for st in status:
+            raise_for_status(st)
         return lines
 
     def extract(self, start, stop, destination, offset=0):  # FM:564-608

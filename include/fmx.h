@@ -249,6 +249,24 @@ int fmx_match_query_batch(const fmx_index *idx, const uint16_t *pat, const int32
                           const uint8_t *term_kind, int32_t q, int32_t max_lines, int64_t *line_off, int32_t **lines,
                           int32_t *line_count, int32_t *occurrences, int32_t *status);
 
+/* THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY (extract, FM:564-608, batched) — the host form of
+ * fmx_extract_packed_offsets_dev + fmx_extract_packed_fill_dev (below: the layout, the statuses, how the work is cut).
+ * host buffers, synchronous: text_off = n + 1 int64 (out), text_off[0] = 0; *chars = text_off[n] UTF-16 code units owned by the
+ * library until fmx_free_buffer((uint8_t *)*chars) (NULL when there are none, and on every failure); status nullable, n ints.
+ * (*chars)[text_off[i] .. text_off[i + 1]) is what extract(start[i], stop[i], destination, 0) leaves in destination[0 .. stop -
+ * start).  Memory follows the SUM of the lengths, not n times the longest.  One index on one device and one device buffer for
+ * the whole answer in this version: FMX_E_NOMEM when it, or the result, cannot be allocated (nothing is left behind);
+ * FMX_E_ARG for null or negative arguments, for an answer of more than 2^35 characters, and for a SuffixArray, RrrVector or
+ * stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident.  n == 0: FMX_OK, text_off[0] = 0. */
+int fmx_extract_packed_batch(const fmx_index *idx, const int32_t *start, const int32_t *stop, int32_t n, int64_t *text_off,
+                             uint16_t **chars, int32_t *status);
+/* ... of LINES: the ids go through the resident line table on the device (fmx_line_table_build; fmx_line_bounds_batch's rule)
+ * and nothing in between comes down.  An id that is no line gets FMX_ST_POS_NEGATIVE and length 0.  FMX_E_ARG without a table. */
+int fmx_line_text_batch(const fmx_index *idx, const int32_t *lines, int32_t n, int64_t *text_off, uint16_t **chars, int32_t *status);
+/* how many ranges the calling thread's last fmx_extract_packed_batch / fmx_line_text_batch ran literally (the redo list below);
+ * -1 before the first such call.  0 on an index without quirk rows. */
+int64_t fmx_extract_packed_last_redo(void);
+
 /* int extract(int start, int stop, char[] destination, int offset) FM:564-608.  dst is n rows of
  * dst_len chars (row i = the `destination` array of query i, in/out); out_len[i] = return value. */
 int fmx_extract_batch(const fmx_index *idx, const int32_t *start, const int32_t *stop, int32_t n, uint16_t *dst,
@@ -325,6 +343,31 @@ int fmx_locate_all_ranges_dev(const fmx_index *idx, const uint16_t *d_pat, const
 int fmx_locate_all_fill_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_off, const int32_t *d_range_ws,
                             int64_t first_hit, int64_t n_hits, int32_t *d_locs, int32_t *d_lf_steps, int32_t *d_status,
                             void *stream);
+/* EXTRACT, PACKED, in two stages over device pointers; asynchronous on `stream`, nothing is allocated, no host wait.
+ * stage 1: d_status[i] = the status FM:566-576 raise for (d_start[i], d_stop[i]), in their order — FMX_ST_NOT_ENABLED,
+ * FMX_ST_POS_NEGATIVE, FMX_ST_STOP_TOO_LONG, then FMX_ST_JAVA_AIOOBE for a negative IntVector index (FMX_ST_DEST_TOO_SMALL cannot
+ * occur: every range gets the room it needs); d_text_off (n + 1 int64, d_text_off[0] = 0) = the exclusive sum of the lengths: stop
+ * - start, and 0 for a range with a status or with stop <= start (which is FMX_ST_OK); d_piece_off (n + 1 int64) = the exclusive
+ * sum of the ranges' PIECES.  A range is cut at multiples of P in text coordinates, P = the smallest multiple of the sample rate
+ * that is >= 32: every piece but a range's last ends on a position sample, so each is an independent walk of at most P +
+ * sampleRate LF-steps for one lane, and a batch is balanced by pieces, not by ranges.  The sums are int64: they do not wrap.
+ * The caller reads d_text_off[n] between the stages and gives d_chars that many code units.
+ * stage 2: d_chars[d_text_off[i] .. d_text_off[i + 1]) = what extract(start, stop, destination, 0) leaves in destination[0 .. stop
+ * - start) — the reference's quirks included: a piece whose walk meets a step that is not clean (a status, or a route through the
+ * wavelet tree on which the reference's own result differs from the text) stores no further and puts its RANGE on a redo list,
+ * once; a second launch, which reads the list's count on the device, runs the literal extract for those ranges, one lane each,
+ * into the same slice and leaves its status in d_status.  On an index without such rows the list stays empty.  Code units of
+ * d_chars outside [0, d_text_off[n]) and d_status of the other ranges keep their values.  No per-range LF-steps in this version.
+ * scratch: at least *bytes of fmx_extract_packed_scratch_bytes(idx, n, &bytes), the same block for both stages (256-byte aligned); after stage 2 its first int32 is the number of ranges that were redone.
+ * FMX_E_ARG for null or negative arguments and a scratch that is too small (nothing is launched); FMX_E_NO_DEVICE for a handle
+ * that is not resident.  n == 0: stage 1 zeroes the two offsets' first entry, stage 2 does nothing. */
+int fmx_extract_packed_scratch_bytes(const fmx_index *idx, int32_t n, size_t *bytes);
+int fmx_extract_packed_offsets_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n,
+                                   int64_t *d_text_off, int64_t *d_piece_off, int32_t *d_status, void *scratch,
+                                   size_t scratch_bytes, void *stream);
+int fmx_extract_packed_fill_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n,
+                                const int64_t *d_text_off, const int64_t *d_piece_off, uint16_t *d_chars, int32_t *d_status,
+                                void *scratch, size_t scratch_bytes, void *stream);
 /* THE LINE TABLE of a resident FM-index — a resident extra like the row table and the window directory, 4 bytes per line, made
  * on request: T = the positions locate(new char[]{boundary}, locations) returns, sorted ascending, as int32 in the index's
  * device memory.  It holds what the INDEX answers (quirk Q1 included), not what the text "really" holds, so that everything

@@ -261,6 +261,45 @@ public:
         return matchQueryBatch({query}, maxLines).lines;
     }
 
+    // the text of ranges and of lines in ONE packed array (fmx.h "THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY"): range / line
+    // i is chars[offsets[i] .. offsets[i + 1]) — what extract(start, stop, destination, 0) leaves in destination; memory follows
+    // the sum of the lengths.  status[i] is the range's own (not thrown: one range out of the text does not hide the others);
+    // a range with a status, or with stop <= start, is empty.  lineText throws for an id that is no line.
+    struct Text {
+        std::vector<int64_t> offsets;
+        std::vector<int32_t> status;
+        std::u16string chars;
+        std::u16string operator[](size_t i) const { return chars.substr((size_t)offsets[i], (size_t)(offsets[i + 1] - offsets[i])); }
+    };
+    Text extractPacked(const std::vector<int32_t> &starts, const std::vector<int32_t> &stops) const {
+        if (starts.size() != stops.size()) throw std::invalid_argument("extractPacked: starts and stops differ in length");
+        const int32_t n = (int32_t)starts.size();
+        Text out;
+        out.offsets.assign((size_t)n + 1, 0);
+        out.status.assign(starts.size(), 0);
+        uint16_t *buf = nullptr;
+        detail::check(fmx_extract_packed_batch(h_, starts.data(), stops.data(), n, out.offsets.data(), &buf, out.status.data()),
+                      "fmx_extract_packed_batch");
+        return takeText(out, buf, n);
+    }
+    Text lineTextBatch(const std::vector<int32_t> &lines) const {
+        const int32_t n = (int32_t)lines.size();
+        Text out;
+        out.offsets.assign((size_t)n + 1, 0);
+        out.status.assign(lines.size(), 0);
+        uint16_t *buf = nullptr;
+        detail::check(fmx_line_text_batch(h_, lines.data(), n, out.offsets.data(), &buf, out.status.data()), "fmx_line_text_batch");
+        return takeText(out, buf, n);
+    }
+    std::vector<std::u16string> lineText(const std::vector<int32_t> &lines) const {
+        const Text t = lineTextBatch(lines);
+        for (int s : t.status) detail::raise_for_status(s);
+        std::vector<std::u16string> out;
+        out.reserve(lines.size());
+        for (size_t i = 0; i < lines.size(); ++i) out.push_back(t[i]);
+        return out;
+    }
+
     // locate, then extract(loc, min(getInputLength(), loc + extractLength), row, 0) per hit, both on the device:
     // the composite the reference times in locateAndExtractBenchmark (FmIndexThroughputBenchmark.java:231-249).
     // Hit k of pattern i: locations[i*maxMatches+k], rows[i*maxMatches+k] (extractLength chars, only the first
@@ -341,6 +380,18 @@ public:
 
 private:
     explicit FmIndex(fmx_index *h) : h_(h) {}
+    // the library's buffer of a packed text, copied into the result and handed back
+    static Text takeText(Text &out, uint16_t *buf, int32_t n) {
+        try {
+            if (buf) out.chars.assign(reinterpret_cast<const char16_t *>(buf), (size_t)out.offsets[(size_t)n]);
+        } catch (...) {
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+            throw;
+        }
+        fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+        return out;
+    }
+
     static void pack(const std::vector<std::u16string> &patterns, std::vector<uint16_t> &chars,
                      std::vector<int32_t> &off) {
         off.assign(1, 0);

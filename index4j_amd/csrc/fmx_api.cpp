@@ -60,6 +60,7 @@ FMX_DISPATCH_FN(launch_locate_walk)
 FMX_DISPATCH_FN(walk_workspace_bytes)
 FMX_DISPATCH_FN(launch_locate_all)
 FMX_DISPATCH_FN(launch_extract)
+FMX_DISPATCH_FN(launch_extract_packed_fill)
 FMX_DISPATCH_FN(launch_extract_boundary)
 FMX_DISPATCH_FN(boundary_workspace_bytes)
 FMX_DISPATCH_FN(boundary_order_bytes)
@@ -3253,6 +3254,172 @@ int fmx_match_query_batch(const fmx_index *idx, const uint16_t *pat, const int32
     *lines = result.p;
     result.p = nullptr;
     return FMX_OK;
+    });
+}
+
+// ---- extract, packed (fmx_extract_packed.hip): the text of ranges and lines in one array ---------------------------------------
+int fmx_extract_packed_scratch_bytes(const fmx_index *idx, int32_t n, size_t *bytes) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || !bytes) return fail(FMX_E_ARG, "bad arguments");
+    *bytes = fmx::extract_packed_scratch_bytes(n);
+    return FMX_OK;
+    });
+}
+
+int fmx_extract_packed_offsets_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n, int64_t *d_text_off,
+                                   int64_t *d_piece_off, int32_t *d_status, void *scratch, size_t scratch_bytes, void *stream) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || !d_text_off || !d_piece_off || (n > 0 && (!d_start || !d_stop || !d_status || !scratch)))
+        return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_text_off, 0, sizeof(int64_t), st));
+        HIP_TRY(hipMemsetAsync(d_piece_off, 0, sizeof(int64_t), st));
+        return FMX_OK;
+    }
+    if (scratch_bytes < fmx::extract_packed_scratch_bytes(n)) return fail(FMX_E_ARG, "scratch smaller than fmx_extract_packed_scratch_bytes");
+    int e = fmx::launch_extract_packed_offsets(idx->dev, d_start, d_stop, n, d_text_off, d_piece_off, d_status, scratch, scratch_bytes, stream);
+    if (e) return fail(FMX_E_HIP, std::string("extract packed offsets: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+    });
+}
+
+// both stages' launches behind the arguments' checks; pieces: piece_off[n] where the host has read it, else -1
+static int extract_packed_fill_impl(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n, const int64_t *d_text_off,
+                                    const int64_t *d_piece_off, int64_t pieces, uint16_t *d_chars, int32_t *d_status, void *scratch,
+                                    hipStream_t st) {
+    int e = k_launch_extract_packed_fill(idx, idx->dev, idx->n_cu, d_start, d_stop, n, d_text_off, d_piece_off, pieces, d_chars, d_status,
+                                         fmx::extract_packed_redo(scratch), fmx::extract_packed_flags(scratch, n), st);
+    if (e) return fail(FMX_E_HIP, std::string("k_extract_packed_fill launch: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+}
+
+int fmx_extract_packed_fill_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n, const int64_t *d_text_off,
+                                const int64_t *d_piece_off, uint16_t *d_chars, int32_t *d_status, void *scratch, size_t scratch_bytes,
+                                void *stream) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || !d_text_off || !d_piece_off || (n > 0 && (!d_start || !d_stop || !d_chars || !d_status || !scratch)))
+        return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if (n == 0) return FMX_OK;
+    if (scratch_bytes < fmx::extract_packed_scratch_bytes(n)) return fail(FMX_E_ARG, "scratch smaller than fmx_extract_packed_scratch_bytes");
+    return extract_packed_fill_impl(idx, d_start, d_stop, n, d_text_off, d_piece_off, -1, d_chars, d_status, scratch, static_cast<hipStream_t>(stream));
+    });
+}
+
+// The host forms: the layout, ONE wait for the two totals, the answer in one device buffer and one malloc'ed host buffer, the
+// fill, everything down.  Nothing of the caller's is written before the last wait has succeeded.
+constexpr int64_t kExtractPackedMaxChars = (int64_t)1 << 35;  // 64 GiB of characters in one answer
+static thread_local int64_t g_extract_packed_redo = -1;
+int64_t fmx_extract_packed_last_redo(void) { return g_extract_packed_redo; }
+
+// d_start / d_stop: the ranges, on the device already (lines: made there from the ids)
+static int extract_packed_host(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n, hipStream_t st,
+                               int64_t *text_off, uint16_t **chars, int32_t *status) {
+    DevBuf d_toff, d_poff, d_st, d_ws, d_chars;
+    HIP_TRY(d_toff.alloc((size_t)(n + 1) * 8));
+    HIP_TRY(d_poff.alloc((size_t)(n + 1) * 8));
+    HIP_TRY(d_st.alloc((size_t)n * 4));
+    const size_t ws_bytes = fmx::extract_packed_scratch_bytes(n);
+    int rc;
+    if ((rc = alloc_for_hits(d_ws, ws_bytes))) return rc;
+    struct Result {  // (as in fmx_locate_all_batch)
+        hipStream_t s;
+        uint16_t *p = nullptr;
+        ~Result() {
+            (void)hipStreamSynchronize(s);
+            free(p);
+        }
+    } result{st};
+    int e = fmx::launch_extract_packed_offsets(idx->dev, d_start, d_stop, n, d_toff.as<int64_t>(), d_poff.as<int64_t>(), d_st.as<int32_t>(),
+                                               d_ws.p, d_ws.bytes, st);
+    if (e) return fail(FMX_E_HIP, std::string("extract packed offsets: ") + hipGetErrorString((hipError_t)e));
+    int64_t total = 0, pieces = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_toff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&pieces, d_poff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (total > kExtractPackedMaxChars)
+        return fail(FMX_E_ARG, "the batch's ranges hold " + std::to_string(total) + " characters, more than one answer's " +
+                                   std::to_string(kExtractPackedMaxChars));
+    int32_t redo = 0;
+    if (total > 0) {
+        if ((rc = alloc_for_hits(d_chars, (size_t)total * 2 + 8))) return rc;
+        result.p = static_cast<uint16_t *>(malloc((size_t)total * 2));
+        if (!result.p) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(total) + " characters");
+        rc = extract_packed_fill_impl(idx, d_start, d_stop, n, d_toff.as<int64_t>(), d_poff.as<int64_t>(), pieces, d_chars.as<uint16_t>(),
+                                      d_st.as<int32_t>(), d_ws.p, st);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(result.p, d_chars.p, (size_t)total * 2, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&redo, fmx::extract_packed_redo(d_ws.p), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(hipMemcpyAsync(text_off, d_toff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    g_extract_packed_redo = redo;
+    *chars = result.p;
+    result.p = nullptr;
+    return FMX_OK;
+}
+
+int fmx_extract_packed_batch(const fmx_index *idx, const int32_t *start, const int32_t *stop, int32_t n, int64_t *text_off, uint16_t **chars,
+                             int32_t *status) {
+    return guarded([&]() -> int {
+    if (chars) *chars = nullptr;
+    if (!idx || n < 0 || !text_off || !chars || (n > 0 && (!start || !stop))) return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if (n == 0) {
+        text_off[0] = 0;
+        g_extract_packed_redo = 0;
+        return FMX_OK;
+    }
+    HIP_TRY(hipSetDevice(idx->device));
+    PipeStreams *ps = nullptr;
+    rc = pipe_streams(idx->device, &ps);
+    if (rc) return rc;
+    hipStream_t st = ps->s[1];
+    DevBuf d_start, d_stop;
+    HIP_TRY(d_start.alloc((size_t)n * 4));
+    HIP_TRY(d_stop.alloc((size_t)n * 4));
+    StreamWait wait{st};
+    HIP_TRY(hipMemcpyAsync(d_start.p, start, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_stop.p, stop, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    return extract_packed_host(idx, d_start.as<int32_t>(), d_stop.as<int32_t>(), n, st, text_off, chars, status);
+    });
+}
+
+int fmx_line_text_batch(const fmx_index *idx, const int32_t *lines, int32_t n, int64_t *text_off, uint16_t **chars, int32_t *status) {
+    return guarded([&]() -> int {
+    if (chars) *chars = nullptr;
+    if (!idx || n < 0 || !text_off || !chars || (n > 0 && !lines)) return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if ((rc = require_line_table(idx))) return rc;
+    if (n == 0) {
+        text_off[0] = 0;
+        g_extract_packed_redo = 0;
+        return FMX_OK;
+    }
+    HIP_TRY(hipSetDevice(idx->device));
+    PipeStreams *ps = nullptr;
+    rc = pipe_streams(idx->device, &ps);
+    if (rc) return rc;
+    hipStream_t st = ps->s[1];
+    DevBuf d_in, d_start, d_stop;
+    HIP_TRY(d_in.alloc((size_t)n * 4));
+    HIP_TRY(d_start.alloc((size_t)n * 4));
+    HIP_TRY(d_stop.alloc((size_t)n * 4));
+    StreamWait wait{st};
+    HIP_TRY(hipMemcpyAsync(d_in.p, lines, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    // the ids become ranges where they are (an id that is no line: start = stop = -1, FMX_ST_POS_NEGATIVE below)
+    int e = fmx::launch_line_bounds(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_lines, line_text_length(idx),
+                                    idx->n_cu, d_in.as<int32_t>(), n, d_start.as<int32_t>(), d_stop.as<int32_t>(), st);
+    if (e) return fail(FMX_E_HIP, std::string("k_line_bounds launch: ") + hipGetErrorString((hipError_t)e));
+    return extract_packed_host(idx, d_start.as<int32_t>(), d_stop.as<int32_t>(), n, st, text_off, chars, status);
     });
 }
 

@@ -2364,6 +2364,103 @@ FMX_HD int32_t fm_extract(const DevIndex &ix, const uint16_t *inv, int32_t start
     return range;
 }
 
+// EXTRACT, PACKED (fmx_extract_packed_*; fmx_extract_packed.hip): the text of n ranges in ONE array, range i at text_off[i] (n + 1
+// int64 entries), walked in PIECES of about one sample interval — the characters extract(start, stop) stores are what any walk
+// through the same rows yields as long as its steps are clean (no status, no `suspect`), so a range is cut at samples and every
+// piece walked by its own lane into its own slice.  A piece that meets a step that is not clean stores no further and puts its
+// RANGE on a redo list; the literal fm_extract then runs for it.
+// the status FM:566-576 raise for a range, in their order (then the negative IntVector index); such a range has length 0
+FMX_HD int fm_extract_packed_status(const DevIndex &ix, int32_t start, int32_t stop) {
+    if (!ix.enable_extract) return ST_NOT_ENABLED;
+    if (start < 0) return ST_POS_NEGATIVE;
+    if (stop >= ix.length) return ST_STOP_TOO_LONG;
+    if (stop / ix.sample_rate + 1 < 0) return ST_JAVA_AIOOBE;
+    return ST_OK;
+}
+FMX_HD int64_t fm_extract_packed_length(int status, int32_t start, int32_t stop) {
+    return (status == ST_OK && stop > start) ? (int64_t)stop - start : 0;
+}
+// P, the length of a piece: the smallest multiple of the sample rate that is >= 32
+FMX_HD int32_t fm_piece_len(const DevIndex &ix) {
+    const int32_t s = ix.sample_rate;
+    return s >= 32 ? s : (31 / s + 1) * s;
+}
+// Pieces are cut at multiples of P in TEXT coordinates: every piece but a range's last ends ON a sample, the last at `stop`.
+// (start, stop): a range of status ST_OK; stop <= start: no piece
+FMX_HD int64_t fm_piece_count(const DevIndex &ix, int32_t start, int32_t stop) {
+    if (stop <= start) return 0;
+    const int32_t p = fm_piece_len(ix);
+    return (int64_t)((stop - 1) / p) - start / p + 1;
+}
+FMX_HD void fm_piece_bounds(const DevIndex &ix, int32_t start, int32_t stop, int32_t k, int32_t &a, int32_t &b) {
+    const int64_t p = fm_piece_len(ix);
+    const int64_t first = start / p;
+    const int64_t end = (first + k + 1) * p;
+    a = k == 0 ? start : (int32_t)((first + k) * p);
+    b = end < stop ? (int32_t)end : stop;
+}
+// The sample AT or after x: the one at the smallest multiple of the sample rate >= x (skip 0 when x is on it), with
+// fm_seek_after's end-of-text rule and clamp.  (fm_seek_after itself sends an x on a sample a whole interval further.)
+FMX_HD void fm_seek_at_or_after(const DevIndex &ix, int32_t x, int32_t &row, int32_t &skip) {
+    const int32_t s = ix.sample_rate;
+    const int32_t q = x / s + (x % s != 0);
+    row = fm_packed_get(ix.pos_words, (int64_t)q, ix.bw_positions) + 1;
+    skip = (int32_t)((int64_t)q * s - x);
+    if (q == ix.n_positions - 1) skip = ix.length - x;  // the entry behind the last sample stands for the end of the text (FM:367-369)
+    if (skip > ix.length - x) skip = ix.length - x;     // (a damaged sample count, as in fm_seek_after)
+}
+// One piece [a, b) of a range: its characters to dest[0 .. b - a), four per aligned 8 bytes where the piece covers the group
+// (fm_flush_chars; a group's other characters are a neighbouring piece's, or the caller's).  `last`: the piece ends at the
+// range's stop — it starts where the reference starts (fm_seek_after: a step of its skip that is not clean derails the
+// reference's walk for the whole range); every other piece ends on a sample and starts there.  false: a step was not clean —
+// the range is to be redone.  steps: LF-steps taken.
+template <int kWin = kWinAsk>
+FMX_HD bool fm_extract_piece(const DevIndex &ix, const uint16_t *inv, int32_t a, int32_t b, bool last, uint16_t *dest, int32_t &steps) {
+    int32_t row, skip;
+    if (last)
+        fm_seek_after(ix, b, row, skip);
+    else
+        fm_seek_at_or_after(ix, b, row, skip);
+    int32_t remaining = b - a, distance = 0;
+    uint64_t group = 0;
+    uint32_t group_mask = 0;
+    steps = 0;
+    while (remaining > 0) {
+        int32_t c;
+        int status = ST_OK;
+        bool suspect = false;
+        row = fm_lf_step<false, kWin>(ix, inv, row, c, status, suspect);
+        ++steps;
+        if (status != ST_OK || suspect) return false;
+        if (distance >= skip) {
+            uint16_t *at = dest + (remaining - 1);
+            const uint32_t slot = (uint32_t)(reinterpret_cast<uintptr_t>(at) >> 1) & 3u;
+            group |= (uint64_t)fm_char_of(ix, c) << (16u * slot);
+            group_mask |= 1u << slot;
+            --remaining;
+            if (slot == 0u || remaining == 0) {
+                fm_flush_chars(at - slot, group, group_mask);
+                group = 0;
+                group_mask = 0;
+            }
+        }
+        ++distance;
+    }
+    return true;
+}
+// range r onto the redo list {count, 0, 0, 0, ranges...}, once: flag[r] says it is there (both zero before the launch)
+constexpr int32_t kPackedRedoHead = 4;
+FMX_HD void fm_redo_once(int32_t *flag, int32_t *redo, int32_t r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (atomicExch(&flag[r], 1) != 0) return;
+    redo[kPackedRedoHead + atomicAdd(&redo[0], 1)] = r;
+#else
+    if (flag[r]) return;
+    flag[r] = 1;
+    redo[kPackedRedoHead + redo[0]++] = r;
+#endif
+}
+
 // ---- right part of extractUntilBoundary / extractUntilBoundaryRight (FM:692-758 / FM:853-921) ----------
 // The reference fetches the text right of `from` in +4-char chunks; chunk t re-seeks the ISA sample after
 // from+4t and walks back skip+4 LF-steps, i.e. ~(s/2+4)/4 steps per character.  The per-character control

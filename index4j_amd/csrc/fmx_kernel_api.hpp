@@ -46,6 +46,12 @@ int launch_extract_boundary(const fmx::DevIndex &ix, int n_cu, const int32_t *fr
                             int32_t *aux, void *workspace, size_t workspace_bytes, const int32_t *slot_found, int32_t slots,
                             void *order_ws, size_t order_ws_bytes, bool head_is_zero, hipStream_t st);
 
+// extract, packed (fmx_extract_packed.hip, compiled per image form like fmx_kernels.hip): the pieces of the layout text_off /
+// piece_off describe into chars, then the ranges a piece put on the redo list, literally.  redo / flags: fmx_plan.hpp
+int launch_extract_packed_fill(const fmx::DevIndex &ix, int n_cu, const int32_t *start, const int32_t *stop, int32_t n,
+                               const int64_t *text_off, const int64_t *piece_off, int64_t pieces, uint16_t *chars, int32_t *status,
+                               int32_t *redo, int32_t *flags, hipStream_t st);
+
 // the stand-alone structures: RrrVector, WaveletFixedBlockBoosting
 int launch_rrr_rank_ones(const fmx::DevIndex &ix, int n_cu, const int32_t *pos, int32_t n, int32_t *out, hipStream_t st);
 int launch_rrr_access(const fmx::DevIndex &ix, int n_cu, const int32_t *pos, int32_t n, uint8_t *out, int32_t *status,

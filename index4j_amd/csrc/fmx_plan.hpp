@@ -46,6 +46,18 @@ size_t hit_offsets_scratch_bytes(int32_t n);
 int launch_hit_offsets(const int32_t *range, int32_t n, int32_t max_matches, int64_t *hit_off, void *scratch, size_t scratch_bytes,
                        void *stream);
 
+// fmx_extract_packed.hip — the packed layout of fmx_extract_packed_*: status[i], text_off[i] = characters of ranges 0 .. i - 1 and
+// piece_off[i] = their pieces (n + 1 entries each) from the ranges themselves.  It looks at the index's length, sample rate and
+// enableExtract only.  scratch: extract_packed_scratch_bytes(n), ONE workspace for both stages of a call — the fill (declared in
+// fmx_kernel_api.hpp: it walks the image) keeps its redo list {count, 0, 0, 0, ranges...} at extract_packed_redo and a flag per
+// range at extract_packed_flags.  The launcher returns a hipError_t as int; `stream` a hipStream_t.
+struct DevIndex;
+size_t extract_packed_scratch_bytes(int32_t n);
+int32_t *extract_packed_redo(void *scratch);
+int32_t *extract_packed_flags(void *scratch, int32_t n);
+int launch_extract_packed_offsets(const DevIndex &ix, const int32_t *start, const int32_t *stop, int32_t n, int64_t *text_off,
+                                  int64_t *piece_off, int32_t *status, void *scratch, size_t scratch_bytes, void *stream);
+
 // fmx_hit_lines.hip — the line table of a resident index and packed hits -> packed distinct lines (fmx_line_table_build,
 // fmx_line_bounds_*, fmx_lines_of_hits_dev).  Compiled once, like fmx_hit_offsets.hip.  The launchers return a hipError_t as int;
 // `stream` is a hipStream_t; nothing is synchronised or allocated.

@@ -345,6 +345,36 @@ class FmIndex:
               "fmx_extract_batch")
         return (dst, out_len, status, steps) if want_steps else (dst, out_len, status)
 
+    def _packed_text(self, call, where, *args):
+        """(chars, text_off, status) of a host form that answers in one packed array of the library's making"""
+        n = args[-1]
+        text_off = np.zeros(n + 1, dtype=np.int64)
+        status = np.zeros(n, dtype=np.int32)
+        buf = C.c_void_p()
+        check(call(self._h, *args, text_off.ctypes.data, C.byref(buf), status.ctypes.data), where)
+        total = int(text_off[n])
+        try:  # the library's buffer is copied into an array of NumPy's own and handed back
+            chars = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_uint16)), shape=(total,)).copy() if total else np.zeros(0, np.uint16)
+        finally:
+            lib.fmx_free_buffer(buf)
+        return chars, text_off, status
+
+    def extract_packed_batch(self, starts, stops):
+        """the text of every range [starts[i], stops[i]) in ONE packed array (fmx_extract_packed_batch; FM:564-608): range i is
+        chars[text_off[i]:text_off[i + 1]], what extract(start, stop, destination, 0) leaves in destination[:stop - start]; a
+        range with a status, or with stop <= start, is empty.  Returns (chars, text_off, status)."""
+        starts = np.ascontiguousarray(starts, dtype=np.int32)
+        stops = np.ascontiguousarray(stops, dtype=np.int32)
+        if len(starts) != len(stops):
+            raise ValueError("%d starts for %d stops" % (len(starts), len(stops)))
+        return self._packed_text(lib.fmx_extract_packed_batch, "fmx_extract_packed_batch", starts.ctypes.data, stops.ctypes.data, len(starts))
+
+    def line_text_batch(self, lines):
+        """the text of every line id, the boundary excluded, in one packed array (fmx_line_text_batch; needs build_line_table):
+        (chars, text_off, status), as extract_packed_batch; an id that is no line is empty and has status ST_POS_NEGATIVE"""
+        lines = np.ascontiguousarray(lines, dtype=np.int32)
+        return self._packed_text(lib.fmx_line_text_batch, "fmx_line_text_batch", lines.ctypes.data, len(lines))
+
     def extract_boundary_batch(self, froms, boundary, mode, dst_len, offset=0, dst=None, want_steps=False):
         froms = np.ascontiguousarray(froms, dtype=np.int32)
         n = len(froms)
@@ -460,6 +490,24 @@ class FmIndex:
         for st in status:
             raise_for_status(st)
         return lines
+
+    def line_text(self, lines):
+        """the lines with these ids as a list of str (the boundary excluded); raises for an id that is no line"""
+        chars, text_off, status = self.line_text_batch(lines)
+        for st in status:
+            raise_for_status(st)
+        return [chars[a:b].tobytes().decode("utf-16-le", "surrogatepass") for a, b in zip(text_off[:-1], text_off[1:])]
+
+    def grep(self, pattern=None, all=(), any=(), none=(), max_lines=0):  # noqa: A002 (the words of the query)
+        """[(line id, line)] of the lines that hold `pattern` — or, without one, that match the query of all / any / none
+        (match_query) — ascending, at most max_lines of them for max_lines > 0: match_lines / match_query, then line_text_batch"""
+        if pattern is not None:
+            if all or any or none:
+                raise ValueError("a pattern or a query, not both")
+            ids = self.match_lines(pattern, max_lines)
+        else:
+            ids = self.match_query(all, any, none, max_lines)
+        return list(zip(ids.tolist(), self.line_text(ids)))
 
     def extract(self, start, stop, destination, offset=0):  # FM:564-608
         dst = np.ascontiguousarray(destination, dtype=np.uint16).reshape(1, len(destination))

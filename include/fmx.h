@@ -49,6 +49,7 @@ typedef struct fmx_index fmx_index;
 #define FMX_ST_NO_BOUNDARY 7     /* IllegalArgumentException "Boundary does not exist"           FM:659-661, 792-794, 849-851 */
 #define FMX_ST_DOES_NOT_FIT 8    /* RuntimeException "Extraction does not fit in the supplied destination. Currently extracted: N" (N in aux[]) FM:732-737, 816-821, 893-898 */
 #define FMX_ST_JAVA_AIOOBE 9     /* the JVM would raise ArrayIndexOutOfBoundsException (e.g. empty pattern FM:456-457, locations[] too small FM:538) */
+#define FMX_ST_TOO_MANY_RANGES 10 /* RuntimeError "Class pattern keeps more than max_ranges ranges" (the class calls only; no reference counterpart) */
 
 /* ---- construction, persistence, lifetime ------------------------------------------------- */
 
@@ -249,6 +250,35 @@ int fmx_match_query_batch(const fmx_index *idx, const uint16_t *pat, const int32
                           const uint8_t *term_kind, int32_t q, int32_t max_lines, int64_t *line_off, int32_t **lines,
                           int32_t *line_count, int32_t *occurrences, int32_t *status);
 
+/* PATTERNS OF CHARACTER CLASSES (grep -i, [0-9]) — the host forms of fmx_class_ranges_count_dev + fmx_class_ranges_fill_dev and what
+ * follows them (below: what a class pattern is, its ranges, the statuses, max_ranges).  A batch is three packed arrays, one level
+ * more than the literal calls take: alt = UTF-16 code units; pos_off = n_pos + 1 ints, never decreasing: position j has the
+ * alternatives alt[pos_off[j] .. pos_off[j + 1]); pat_off = n + 1 ints, never decreasing, indexing POSITIONS: pattern i is positions
+ * pat_off[i] .. pat_off[i + 1).  The answer of pattern i is the union of the reference's answers for the distinct literal strings
+ * it spells.  Host buffers, synchronous.
+ * fmx_count_class_batch: counts[i] (n ints) = the sum of count() over those strings; status nullable, n ints.
+ * fmx_locate_all_class_batch: hit_off = n + 1 int64 (out); *locs = hit_off[n] ints owned by the library until
+ * fmx_free_buffer((uint8_t *)*locs) (NULL when there are no hits, and on every failure): the hits of pattern i, its ranges ascending
+ * by SA row and inside a range the order fmx_locate_all_fill_dev stores — every literal's locate() list, intact.  The hits come down
+ * in windows of 2^24, like fmx_locate_all_batch's.  status (nullable) has the walks' statuses folded in.
+ * fmx_match_query_class_batch: the TERMS are class patterns; query_off, term_kind, q, max_lines, line_off, *lines, line_count,
+ * occurrences and status as fmx_match_query_batch (q queries of ONE ALL term each are the match_lines of class patterns).  A term
+ * with FMX_ST_TOO_MANY_RANGES has no hits.  Needs a line table.
+ * All three: FMX_E_ARG for null or negative arguments, offsets that start below 0 or decrease, pat_off[n] above n_pos, max_ranges
+ * outside [1, FMX_CLASS_RANGES_MAX], more than 2^31 - 1 ranges in one batch, and a SuffixArray, RrrVector or stand-alone wavelet
+ * handle (the query form: as fmx_match_query_batch besides); FMX_E_NO_DEVICE for a handle that is not resident; FMX_E_NOMEM when
+ * scratch or the result cannot be allocated.  Nothing is left behind on failure.  n == 0: FMX_OK, the offsets' first entry 0. */
+#define FMX_CLASS_RANGES_MAX 1024
+#define FMX_CLASS_ALTS_MAX 64
+int fmx_count_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                          int32_t n, int32_t max_ranges, int32_t *counts, int32_t *status);
+int fmx_locate_all_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                               int32_t n, int32_t max_ranges, int64_t *hit_off, int32_t **locs, int32_t *status);
+int fmx_match_query_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                int32_t n, int32_t max_ranges, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t *line_count, int32_t *occurrences,
+                                int32_t *status);
+
 /* THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY (extract, FM:564-608, batched) — the host form of
  * fmx_extract_packed_offsets_dev + fmx_extract_packed_fill_dev (below: the layout, the statuses, how the work is cut).
  * host buffers, synchronous: text_off = n + 1 int64 (out), text_off[0] = 0; *chars = text_off[n] UTF-16 code units owned by the
@@ -448,6 +478,44 @@ int fmx_query_lines_of_hits_dev(const fmx_index *idx, int32_t n, int32_t q, cons
                                 const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int32_t max_lines,
                                 int64_t *d_line_off, int32_t *d_lines, int32_t *d_line_count, void *d_ws, size_t ws_bytes,
                                 void *stream);
+/* CLASS PATTERNS over device pointers (d_alt, d_pos_off, d_pat_off: the three packed arrays of fmx_count_class_batch, in device
+ * memory and trusted as the literal device forms trust theirs); asynchronous on `stream`, nothing is allocated or synchronised.
+ * THE SEARCH keeps, per pattern, a frontier of SA ranges: the last position gives {C[c], C[c + 1]} of each of its codes, every
+ * further position advances every range by every one of its codes with the two rank calls the literal search makes (FM:469-470).
+ * A range with start >= end dies at once (FM:464); an alternative the alphabet lacks matches nothing (FM:458-460, 466-468);
+ * duplicate alternatives count once.  THE RANGES of pattern i are what is left after its first position: one {start, end} pair per
+ * literal string with hits, bit for bit the pair fmx_locate_all_ranges_dev leaves in d_range_ws for that literal, ascending by
+ * start.  Adjacent ranges are not merged and the suffix table is not asked in this version.
+ * STATUSES: a pattern without positions gets FMX_ST_JAVA_AIOOBE; a position without alternatives matches nothing (count 0,
+ * FMX_ST_OK); a pattern whose frontier is larger than max_ranges after any position, or that has a position of more than
+ * FMX_CLASS_ALTS_MAX alternatives, gets FMX_ST_TOO_MANY_RANGES, count 0 and no ranges — whatever the launch shape and the image
+ * form.  max_ranges is in [1, FMX_CLASS_RANGES_MAX]: the frontier lives in LDS, two buffers of max_ranges pairs per pattern.
+ * stage 1: d_range_off (n + 1 int64) = the exclusive sum of the patterns' range counts, d_range_off[n] = m, the ranges of the
+ * batch; d_counts (nullable, n ints) = the sum of end - start over a pattern's ranges = the sum of the literals' count();
+ * d_status (nullable, n ints).  scratch: at least fmx_class_ranges_scratch_bytes(n) bytes (256-byte aligned).
+ * The caller reads m between the stages and gives d_ranges 2 * m ints.
+ * stage 2: the same search again — the price of a layout that does not depend on scheduling — stores the ranges of pattern i at
+ * d_ranges[2 * d_range_off[i] ..).  Same arguments as stage 1.
+ * fmx_class_hit_offsets_dev: d_range_hit_off (m + 1 int64) = the packed layout of the m ranges' hits, every hit (what
+ * fmx_locate_all_ranges_dev leaves for m patterns with max_matches -1), and d_hit_off[i] = d_range_hit_off[d_range_off[i]] for i in
+ * 0 .. n.  scratch: fmx_class_hit_offsets_scratch_bytes(m).  After it fmx_locate_all_fill_dev(idx, m, d_range_hit_off, d_ranges, ...)
+ * fills the hits, and (d_hit_off, d_locs) is what fmx_lines_of_hits_dev and fmx_query_lines_of_hits_dev take for n patterns or terms.
+ * fmx_class_fold_status_dev: d_status[i] |= d_range_status[r] for the ranges r of pattern i (the walk statuses the fill ORs per range).
+ * FMX_E_ARG for null or negative arguments, max_ranges outside its interval, m above 2^31 - 1, a scratch that is too small (nothing
+ * is launched) and a SuffixArray, RrrVector or stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident.
+ * n == 0: stage 1 zeroes d_range_off[0], the others do nothing (fmx_class_hit_offsets_dev zeroes d_hit_off[0] and
+ * d_range_hit_off[0]). */
+size_t fmx_class_ranges_scratch_bytes(int32_t n);
+int fmx_class_ranges_count_dev(const fmx_index *idx, const uint16_t *d_alt, const int32_t *d_pos_off, const int32_t *d_pat_off, int32_t n,
+                               int32_t max_ranges, int64_t *d_range_off, int32_t *d_counts, int32_t *d_status, void *scratch,
+                               size_t scratch_bytes, void *stream);
+int fmx_class_ranges_fill_dev(const fmx_index *idx, const uint16_t *d_alt, const int32_t *d_pos_off, const int32_t *d_pat_off, int32_t n,
+                              int32_t max_ranges, const int64_t *d_range_off, int32_t *d_ranges, void *stream);
+size_t fmx_class_hit_offsets_scratch_bytes(int64_t m);
+int fmx_class_hit_offsets_dev(const fmx_index *idx, int32_t n, const int64_t *d_range_off, const int32_t *d_ranges, int64_t m,
+                              int64_t *d_range_hit_off, int64_t *d_hit_off, void *scratch, size_t scratch_bytes, void *stream);
+int fmx_class_fold_status_dev(const fmx_index *idx, int32_t n, const int64_t *d_range_off, int64_t m, const int32_t *d_range_status,
+                              int32_t *d_status, void *stream);
 int fmx_extract_batch_dev(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n,
                           uint16_t *d_dst, int32_t dst_len, int32_t offset, int32_t *d_out_len,
                           int32_t *d_lf_steps, int32_t *d_status, void *stream);

@@ -261,6 +261,89 @@ public:
         return matchQueryBatch({query}, maxLines).lines;
     }
 
+    // patterns of character classes (fmx.h "PATTERNS OF CHARACTER CLASSES"): a ClassPattern is its positions, a position the code
+    // units it may hold; the answer is the union over the literal strings the pattern spells.  A pattern that keeps more than
+    // maxRanges SA ranges throws std::runtime_error (FMX_ST_TOO_MANY_RANGES).  ignoreCase: per ASCII letter both cases.
+    using ClassPattern = std::vector<std::u16string>;
+    static ClassPattern ignoreCase(const std::u16string &text) {
+        ClassPattern p;
+        for (char16_t c : text) {
+            std::u16string alts(1, c);
+            if (c >= u'a' && c <= u'z') alts.push_back((char16_t)(c - 32));
+            if (c >= u'A' && c <= u'Z') alts.push_back((char16_t)(c + 32));
+            p.push_back(alts);
+        }
+        return p;
+    }
+    std::vector<int32_t> countClass(const std::vector<ClassPattern> &patterns, int maxRanges = 256) const {
+        ClassArrays a(patterns);
+        std::vector<int32_t> counts(patterns.size()), status(patterns.size());
+        detail::check(fmx_count_class_batch(h_, a.alt.data(), a.posOff.data(), a.nPos(), a.patOff.data(), a.n(), maxRanges, counts.data(),
+                                            status.data()),
+                      "fmx_count_class_batch");
+        for (int s : status) detail::raise_for_status(s);
+        return counts;
+    }
+    // locations[offsets[i] .. offsets[i + 1]): the hits of pattern i, one literal string's locate() list after the other
+    Hits locateAllClass(const std::vector<ClassPattern> &patterns, int maxRanges = 256) const {
+        ClassArrays a(patterns);
+        Hits hits;
+        hits.offsets.assign(patterns.size() + 1, 0);
+        std::vector<int32_t> status(patterns.size());
+        int32_t *buf = nullptr;
+        detail::check(fmx_locate_all_class_batch(h_, a.alt.data(), a.posOff.data(), a.nPos(), a.patOff.data(), a.n(), maxRanges,
+                                                 hits.offsets.data(), &buf, status.data()),
+                      "fmx_locate_all_class_batch");
+        try {
+            if (buf) hits.locations.assign(buf, buf + hits.offsets[patterns.size()]);
+        } catch (...) {
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+            throw;
+        }
+        fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+        for (int s : status) detail::raise_for_status(s);
+        return hits;
+    }
+    // matchQueryBatch with class patterns as terms (needs buildLineTable)
+    struct ClassQuery {
+        std::vector<ClassPattern> all, any, none;
+    };
+    Lines matchQueryClass(const std::vector<ClassQuery> &queries, int maxLines = 0, int maxRanges = 256) const {
+        std::vector<ClassPattern> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        for (const ClassQuery &qu : queries) {
+            const std::vector<ClassPattern> *groups[3] = {&qu.all, &qu.any, &qu.none};
+            for (int k = 0; k < 3; ++k)
+                for (const ClassPattern &t : *groups[k]) {
+                    terms.push_back(t);
+                    kind.push_back((uint8_t)k);
+                }
+            queryOff.push_back((int32_t)terms.size());
+        }
+        ClassArrays a(terms);
+        const int32_t q = (int32_t)queries.size();
+        Lines out;
+        out.offsets.assign((size_t)q + 1, 0);
+        out.lineCount.assign(queries.size(), 0);
+        out.occurrences.assign(terms.size(), 0);
+        std::vector<int32_t> status(terms.size());
+        int32_t *buf = nullptr;
+        detail::check(fmx_match_query_class_batch(h_, a.alt.data(), a.posOff.data(), a.nPos(), a.patOff.data(), a.n(), maxRanges, queryOff.data(),
+                                                  kind.data(), q, maxLines, out.offsets.data(), &buf, out.lineCount.data(),
+                                                  out.occurrences.data(), status.data()),
+                      "fmx_match_query_class_batch");
+        try {
+            if (buf) out.lines.assign(buf, buf + out.offsets[(size_t)q]);
+        } catch (...) {
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+            throw;
+        }
+        fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+        for (int s : status) detail::raise_for_status(s);
+        return out;
+    }
+
     // the text of ranges and of lines in ONE packed array (fmx.h "THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY"): range / line
     // i is chars[offsets[i] .. offsets[i + 1]) — what extract(start, stop, destination, 0) leaves in destination; memory follows
     // the sum of the lengths.  status[i] is the range's own (not thrown: one range out of the text does not hide the others);
@@ -401,6 +484,23 @@ private:
         }
         if (chars.empty()) chars.push_back(0);
     }
+    // the three packed arrays of a batch of class patterns (fmx_count_class_batch)
+    struct ClassArrays {
+        std::vector<uint16_t> alt;
+        std::vector<int32_t> posOff{0}, patOff{0};
+        explicit ClassArrays(const std::vector<ClassPattern> &patterns) {
+            for (const ClassPattern &p : patterns) {
+                for (const std::u16string &alts : p) {
+                    alt.insert(alt.end(), alts.begin(), alts.end());
+                    posOff.push_back((int32_t)alt.size());
+                }
+                patOff.push_back((int32_t)posOff.size() - 1);
+            }
+            if (alt.empty()) alt.push_back(0);
+        }
+        int32_t nPos() const { return (int32_t)posOff.size() - 1; }
+        int32_t n() const { return (int32_t)patOff.size() - 1; }
+    };
     HitRows pipeline(const std::vector<std::u16string> &patterns, int maxMatches, int rowLength, int mode,
                      char16_t boundary) const {
         std::vector<uint16_t> chars;

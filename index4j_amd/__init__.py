@@ -9,6 +9,9 @@ from .fmindex import (  # noqa: F401
     FmIndexBuilder,
     as_chars,
     chars_to_str,
+    ignore_case,
+    pack_class_patterns,
+    parse_classes,
     pack_patterns,
     raise_for_status,
     synth_log,
@@ -23,5 +26,5 @@ from . import bwt  # noqa: F401
 from .bwt import computeRedundancyOfText, createBurrowsWheelerTransform  # noqa: F401
 from .wavelet import WaveletFixedBlockBoosting  # noqa: F401
 
-__all__ = ["SuffixArray", "bwt", "createBurrowsWheelerTransform", "computeRedundancyOfText", "ReplicaSet", "SegmentReplicaSet", "shard_range", "WaveletFixedBlockBoosting", "RrrVector", "SegmentedFmIndex", "cut_points", "FmIndex", "FmIndexBuilder", "FmxError", "as_chars", "chars_to_str", "pack_patterns",
+__all__ = ["SuffixArray", "bwt", "createBurrowsWheelerTransform", "computeRedundancyOfText", "ReplicaSet", "SegmentReplicaSet", "shard_range", "WaveletFixedBlockBoosting", "RrrVector", "SegmentedFmIndex", "cut_points", "FmIndex", "FmIndexBuilder", "FmxError", "as_chars", "chars_to_str", "pack_patterns", "pack_class_patterns", "ignore_case", "parse_classes",
            "raise_for_status", "synth_log", "synth_log_multichar", "synth_patterns", "lib", "LIB_PATH", "SYMBOLS"]

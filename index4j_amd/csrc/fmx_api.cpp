@@ -1658,6 +1658,34 @@ static int require_fm_device(const fmx_index *idx) {
     return rc;
 }
 
+extern "C++" {
+namespace fmx {
+int class_view(const fmx_index *idx, ClassView *view) {  // fmx_class_api.cpp: what a class search launches over
+    if (const int rc = require_fm_device(idx)) return rc;
+    *view = {&idx->dev, idx->n_cu, idx->device, image_is_compact(idx)};
+    return FMX_OK;
+}
+int class_scratch_take(size_t *bytes, int *device, void **p) {  // a block of the host forms' recycling cache (DevBuf's rule)
+    DevBuf b;
+    const hipError_t e = b.alloc(*bytes);
+    *bytes = b.bytes;
+    *device = b.device;
+    *p = e == hipSuccess ? b.p : nullptr;
+    b.p = nullptr;
+    return (int)e;
+}
+void class_scratch_give(int device, size_t bytes, void *p) {
+    if (p && !g_scratch.give(device, bytes, p)) (void)hipFree(p);
+}
+int class_call_stream(int device, void **stream) {  // the calling thread's kernel stream on that device
+    PipeStreams *ps = nullptr;
+    const int rc = pipe_streams(device, &ps);
+    if (rc == FMX_OK) *stream = ps->s[1];
+    return rc;
+}
+}  // namespace fmx
+}
+
 static int locate_all_ranges_impl(const fmx_index *idx, const uint16_t *d_pat, const int32_t *d_pat_off, int32_t n, int32_t max_matches,
                                   int64_t *d_hit_off, int32_t *d_lf_steps, int32_t *d_status, int32_t *d_range_ws, Scratch &scratch,
                                   int32_t *d_counts = nullptr /* n ints: count() of every pattern, for a caller that wants it */) {
@@ -3962,6 +3990,7 @@ const char *fmx_status_message(int status) {
         case FMX_ST_NO_BOUNDARY: return "Boundary does not exist";
         case FMX_ST_DOES_NOT_FIT: return "Extraction does not fit in the supplied destination. Currently extracted: %d";
         case FMX_ST_JAVA_AIOOBE: return "ArrayIndexOutOfBoundsException";
+        case FMX_ST_TOO_MANY_RANGES: return "Class pattern keeps more than max_ranges ranges";
         default: return "unknown status";
     }
 }

@@ -2461,6 +2461,60 @@ FMX_HD void fm_redo_once(int32_t *flag, int32_t *redo, int32_t r) {
 #endif
 }
 
+// ---- CLASS SEARCH: patterns of character classes (fmx_class_*; fmx_class_search.hip) ---------------------------------------------
+// A class pattern gives every position a set of alternatives; its answer is the union of the answers of the literal strings it
+// spells (duplicate alternatives count once).  The backward search (FM:455-474) keeps a FRONTIER of SA ranges instead of one:
+// the last position's frontier is {C[c], C[c + 1]} of each of its codes (FM:458-463), and every further position advances every
+// range of the frontier by every one of its codes with the two wt_rank_folded calls a literal makes (FM:469-470).  A range
+// with start >= end is dead (FM:464) and leaves the frontier at once; a code of 0 — a character the alphabet lacks — matches
+// nothing (FM:458-460, 466-468) and is dropped before any rank.  The ranges of different strings of one length are disjoint, and
+// taking the candidates code-major (ascending) and range-minor keeps the frontier ascending by `start` without a sort: ranks
+// are monotone in the row.  Ranges are never merged and the suffix table is not asked: every surviving pair is bit for bit
+// what k_count leaves for that literal.  A team of kClassTeam lanes runs one pattern: a lane pair per candidate, role 0 `start`,
+// role 1 `end`, as count_one.
+constexpr int32_t kClassRangesMax = 1024;  // FMX_CLASS_RANGES_MAX: the largest max_ranges a call may ask for
+constexpr int32_t kClassAltsMax = 64;      // FMX_CLASS_ALTS_MAX: alternatives of one position
+constexpr int kClassTeam = 16;             // lanes per pattern: four patterns per wave (reasoned, not measured)
+constexpr int kClassPairs = kClassTeam / 2;
+constexpr int ST_TOO_MANY_RANGES = 10;     // FMX_ST_TOO_MANY_RANGES
+// what a team keeps per pattern: two frontiers of max_ranges {start, end} pairs, the position's codes as mapped and as kept
+FMX_HHD size_t fm_class_team_bytes(int32_t max_ranges) { return (size_t)max_ranges * 16 + (size_t)kClassAltsMax * 4; }
+// alternative t of a position whose n_alt alternatives map to codes[]: kept iff the alphabet has it and no earlier one equals it
+FMX_HD bool fm_class_keep(const int16_t *codes, int32_t n_alt, int32_t t) {
+    const int16_t c = codes[t];
+    if (c == 0) return false;
+    for (int32_t k = 0; k < t; ++k)
+        if (codes[k] == c) return false;
+    return true;
+}
+// kept[] = codes[] with 0 for every alternative that is not kept: the place of alternative t among the kept, ascending by code
+FMX_HD int32_t fm_class_rank(const int16_t *kept, int32_t n_alt, int32_t t) {
+    const int16_t c = kept[t];
+    int32_t below = 0;
+    for (int32_t k = 0; k < n_alt; ++k) below += (kept[k] != 0 && kept[k] < c) ? 1 : 0;
+    return below;
+}
+// the last position: the range of code c (FM:461-462)
+FMX_HD void fm_class_first(const DevIndex &ix, int32_t c, int32_t &start, int32_t &end) {
+    start = ix.C[c];
+    end = ix.C[c + 1];
+}
+// candidate q of a position over a frontier of n_cur ranges: code a of the position's kept codes, range r of the frontier
+FMX_HD void fm_class_candidate(int32_t q, int32_t n_cur, int32_t &a, int32_t &r) {
+    a = q / n_cur;
+    r = q - a * n_cur;
+}
+// one lane of a candidate's pair: role 0 advances `start`, role 1 `end` (FM:469-470) — the call count_one makes
+FMX_HD int32_t fm_class_advance(const DevIndex &ix, const uint16_t *inv, int32_t start, int32_t end, int role, int32_t c, int &status) {
+    return wt_rank_folded(ix, inv, (uint32_t)(role ? end : start), c, status);
+}
+FMX_HD bool fm_class_survives(int32_t start, int32_t end) { return start < end; }  // FM:464
+// where the survivors of one round go: `before` survivors of the round in front of this one, `total` in the round, n_next in the
+// frontier so far; -1: the frontier would pass max_ranges (the pattern ends with ST_TOO_MANY_RANGES: nothing is stored)
+FMX_HD int32_t fm_class_slot(int32_t n_next, int32_t before, int32_t total, int32_t max_ranges) {
+    return n_next + total > max_ranges ? -1 : n_next + before;
+}
+
 // ---- right part of extractUntilBoundary / extractUntilBoundaryRight (FM:692-758 / FM:853-921) ----------
 // The reference fetches the text right of `from` in +4-char chunks; chunk t re-seeks the ISA sample after
 // from+4t and walks back skip+4 LF-steps, i.e. ~(s/2+4)/4 steps per character.  The per-character control

@@ -52,6 +52,13 @@ int launch_extract_packed_fill(const fmx::DevIndex &ix, int n_cu, const int32_t 
                                const int64_t *text_off, const int64_t *piece_off, int64_t pieces, uint16_t *chars, int32_t *status,
                                int32_t *redo, int32_t *flags, hipStream_t st);
 
+// class patterns (fmx_class_search.hip, compiled per image form like fmx_kernels.hip): the frontier search of a batch.  Stage 1
+// (ranges == nullptr): range_cnt = n + 1 int64 (class_ranges_counts of the call's workspace: fmx_plan.hpp), counts / status
+// nullable; stage 2: the ranges of pattern i at range_off[i]
+int launch_class_search(const fmx::DevIndex &ix, int n_cu, const uint16_t *alt, const int32_t *pos_off, const int32_t *pat_off, int32_t n,
+                        int32_t max_ranges, int64_t *range_cnt, int32_t *counts, int32_t *status, const int64_t *range_off,
+                        int32_t *ranges, hipStream_t st);
+
 // the stand-alone structures: RrrVector, WaveletFixedBlockBoosting
 int launch_rrr_rank_ones(const fmx::DevIndex &ix, int n_cu, const int32_t *pos, int32_t n, int32_t *out, hipStream_t st);
 int launch_rrr_access(const fmx::DevIndex &ix, int n_cu, const int32_t *pos, int32_t n, uint8_t *out, int32_t *status,

@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+struct fmx_index;  // the handle of include/fmx.h (class_view)
+
 namespace fmx {
 
 struct SortShape {
@@ -57,6 +59,30 @@ int32_t *extract_packed_redo(void *scratch);
 int32_t *extract_packed_flags(void *scratch, int32_t n);
 int launch_extract_packed_offsets(const DevIndex &ix, const int32_t *start, const int32_t *stop, int32_t n, int64_t *text_off,
                                   int64_t *piece_off, int32_t *status, void *scratch, size_t scratch_bytes, void *stream);
+
+// fmx_class_search.hip — what the class search (fmx_class_*) does outside the image: the exclusive scan of the patterns' range
+// counts (stage 1 leaves them at class_ranges_counts of the workspace, n + 1 int64), the hit offsets of the patterns from those of
+// their ranges (launch_hit_offsets over the m ranges, every hit, then one gather; scratch: hit_offsets_scratch_bytes(m)) and the
+// fold of the ranges' walk statuses into their patterns'.  The launchers return a hipError_t as int; `stream` a hipStream_t.
+size_t class_ranges_scratch_bytes(int32_t n);
+int64_t *class_ranges_counts(void *scratch);
+int launch_class_range_offsets(void *scratch, size_t scratch_bytes, int32_t n, int64_t *range_off, void *stream);
+int launch_class_hit_offsets(const int32_t *ranges, int32_t m, const int64_t *range_off, int32_t n, int64_t *range_hit_off,
+                             int64_t *hit_off, void *scratch, size_t scratch_bytes, void *stream);
+int launch_class_fold_status(const int64_t *range_off, int32_t n, int32_t m, const int32_t *range_status, int32_t *status, void *stream);
+// fmx_api.cpp, for fmx_class_api.cpp: the resident FM image behind a handle, after the checks of every FM device entry point
+// (their return value; 0 = *view is filled)
+struct ClassView {
+    const DevIndex *dev;
+    int n_cu, device;
+    bool compact;
+};
+int class_view(const ::fmx_index *idx, ClassView *view);
+// ... a block of the host forms' recycling cache (*bytes becomes its size class; returns a hipError_t as int, *p = nullptr on
+// failure), its way back, and the calling thread's kernel stream on a device (a hipStream_t; FMX_OK or an FMX_E_* code)
+int class_scratch_take(size_t *bytes, int *device, void **p);
+void class_scratch_give(int device, size_t bytes, void *p);
+int class_call_stream(int device, void **stream);
 
 // fmx_hit_lines.hip — the line table of a resident index and packed hits -> packed distinct lines (fmx_line_table_build,
 // fmx_line_bounds_*, fmx_lines_of_hits_dev).  Compiled once, like fmx_hit_offsets.hip.  The launchers return a hipError_t as int;

@@ -53,6 +53,89 @@ def pack_patterns(patterns):
     return np.ascontiguousarray(chars, dtype=np.uint16), off
 
 
+CLASS_RANGES_MAX = 1024  # FMX_CLASS_RANGES_MAX
+CLASS_ALTS_MAX = 64  # FMX_CLASS_ALTS_MAX
+CLASS_RANGES_DEFAULT = 256  # max_ranges where the caller names none: two frontiers of 4 KiB per pattern
+
+
+def pack_class_patterns(patterns):
+    """list of class patterns -> (alt, pos_off, pat_off) in the layout fmx_count_class_batch takes.  A class pattern is a list
+    of positions; a position is its alternatives: a str (every UTF-16 code unit of it is one) or an iterable of code units /
+    one-unit strs.  ignore_case() and parse_classes() make such lists."""
+    alts, pos_off, pat_off = [], [0], [0]
+    total = 0
+    for pattern in patterns:
+        for position in pattern:
+            a = as_chars(position) if isinstance(position, str) else as_chars([ord(x) if isinstance(x, str) else x for x in position])
+            alts.append(a)
+            total += len(a)
+            pos_off.append(total)
+        pat_off.append(len(pos_off) - 1)
+    alt = np.concatenate(alts) if alts else np.zeros(0, dtype=np.uint16)
+    return np.ascontiguousarray(alt, dtype=np.uint16), np.array(pos_off, dtype=np.int32), np.array(pat_off, dtype=np.int32)
+
+
+def ignore_case(text):
+    """str / uint16 array -> the class pattern that matches it in any case (grep -i): per code unit {c, lower(c), upper(c)},
+    keeping only results that are one UTF-16 code unit ('ß' stays alone: its upper case is two)"""
+    out = []
+    for u in as_chars(text).tolist():
+        ch = chr(u)
+        units = [u]
+        for other in (ch.lower(), ch.upper()):
+            if len(other) == 1 and ord(other) < 0x10000 and ord(other) not in units:
+                units.append(ord(other))
+        out.append("".join(chr(v) for v in units))
+    return out
+
+
+_ignore_case = ignore_case  # (the methods below have a keyword of that name)
+
+
+def parse_classes(expr):
+    """"blk_[0-9a-f]x\\[" -> a class pattern: a character stands for itself, [...] for its members (a-z: the code units from a
+    to z), a backslash takes the next character literally, inside brackets too.  ValueError for [^...], an unclosed bracket, an
+    empty class, a range that runs backwards and a trailing backslash."""
+    units = as_chars(expr).tolist()
+    out, i, n = [], 0, len(units)
+    BS, OPEN, CLOSE, DASH, NOT = ord("\\"), ord("["), ord("]"), ord("-"), ord("^")
+
+    def take(at):  # (code unit, next index) of the possibly escaped character at `at`
+        if units[at] == BS:
+            if at + 1 >= n:
+                raise ValueError("a backslash ends the expression")
+            return units[at + 1], at + 2
+        return units[at], at + 1
+
+    while i < n:
+        if units[i] != OPEN:
+            u, i = take(i)
+            out.append(chr(u))
+            continue
+        i += 1
+        if i < n and units[i] == NOT:
+            raise ValueError("negated classes ([^...]) are not supported")
+        members = []
+        while True:
+            if i >= n:
+                raise ValueError("unclosed bracket")
+            if units[i] == CLOSE:
+                i += 1
+                break
+            lo, i = take(i)
+            if i + 1 < n and units[i] == DASH and units[i + 1] != CLOSE:
+                hi, i = take(i + 1)
+                if hi < lo:
+                    raise ValueError("range runs backwards")
+                members.extend(range(lo, hi + 1))
+            else:
+                members.append(lo)
+        if not members:
+            raise ValueError("empty class")
+        out.append("".join(chr(v) for v in dict.fromkeys(members)))
+    return out
+
+
 class FmIndexBuilder:
     """fm/FmIndexBuilder.java: defaults sampleRate=32, enableExtraction=true (FMB:21-22)."""
 
@@ -331,6 +414,64 @@ class FmIndex:
             lib.fmx_free_buffer(buf)
         return (lines, line_off, status, line_count, occurrences) if want_counts else (lines, line_off, status)
 
+    # ---- patterns of character classes (fmx.h "PATTERNS OF CHARACTER CLASSES"; pack_class_patterns, ignore_case, parse_classes) ----
+    @staticmethod
+    def _class_arrays(alt, pos_off, pat_off):
+        alt = np.ascontiguousarray(alt, dtype=np.uint16)
+        pos_off = np.ascontiguousarray(pos_off, dtype=np.int32)
+        pat_off = np.ascontiguousarray(pat_off, dtype=np.int32)
+        return alt, pos_off, pat_off, len(pos_off) - 1, len(pat_off) - 1
+
+    def count_class_batch(self, alt, pos_off, pat_off, max_ranges=CLASS_RANGES_DEFAULT):
+        """count() of every class pattern: the sum over the literal strings it spells (fmx_count_class_batch).  (counts, status)"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        counts = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        check(lib.fmx_count_class_batch(self._h, alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, int(max_ranges),
+                                        counts.ctypes.data, status.ctypes.data), "fmx_count_class_batch")
+        return counts, status
+
+    def locate_all_class_batch(self, alt, pos_off, pat_off, max_ranges=CLASS_RANGES_DEFAULT):
+        """every hit of every class pattern, packed (fmx_locate_all_class_batch): those of pattern i are
+        locs[hit_off[i]:hit_off[i + 1]], range after range (every literal's locate() list intact).  (locs, hit_off, status)"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        hit_off = np.zeros(n + 1, dtype=np.int64)
+        status = np.zeros(n, dtype=np.int32)
+        buf = C.c_void_p()
+        check(lib.fmx_locate_all_class_batch(self._h, alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, int(max_ranges),
+                                             hit_off.ctypes.data, C.byref(buf), status.ctypes.data), "fmx_locate_all_class_batch")
+        total = int(hit_off[n])
+        try:  # the library's buffer is copied into an array of NumPy's own and handed back
+            locs = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_int32)), shape=(total,)).copy() if total else np.zeros(0, np.int32)
+        finally:
+            lib.fmx_free_buffer(buf)
+        return locs, hit_off, status
+
+    def match_query_class_batch(self, alt, pos_off, pat_off, query_off, term_kind, max_lines=0, want_counts=False,
+                                max_ranges=CLASS_RANGES_DEFAULT):
+        """match_query_batch with class patterns as terms (fmx_match_query_class_batch); same returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        query_off = np.ascontiguousarray(query_off, dtype=np.int32)
+        term_kind = np.ascontiguousarray(term_kind, dtype=np.uint8)
+        q = len(query_off) - 1
+        if len(term_kind) != n:
+            raise ValueError("term_kind has %d entries for %d terms" % (len(term_kind), n))
+        line_off = np.zeros(q + 1, dtype=np.int64)
+        line_count = np.zeros(q, dtype=np.int32)
+        occurrences = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        buf = C.c_void_p()
+        check(lib.fmx_match_query_class_batch(self._h, alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, int(max_ranges),
+                                              query_off.ctypes.data, term_kind.ctypes.data, q, int(max_lines), line_off.ctypes.data,
+                                              C.byref(buf), line_count.ctypes.data, occurrences.ctypes.data, status.ctypes.data),
+              "fmx_match_query_class_batch")
+        total = int(line_off[q])
+        try:  # the library's buffer is copied into an array of NumPy's own and handed back
+            lines = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_int32)), shape=(total,)).copy() if total else np.zeros(0, np.int32)
+        finally:
+            lib.fmx_free_buffer(buf)
+        return (lines, line_off, status, line_count, occurrences) if want_counts else (lines, line_off, status)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -428,13 +569,17 @@ class FmIndex:
         return self._pipeline(chars, offsets, max_matches, dst_len, boundary, mode, fill)
 
     # ---- scalar API, as in the reference ----
-    def count(self, pattern, offset=0, length=None):  # FM:443-474
+    def count(self, pattern, offset=0, length=None, ignore_case=False):  # FM:443-474
         p = as_chars(pattern)
         if length is None:
             length = len(p)
         if length <= 0 or offset < 0 or offset + length > len(p):
             raise IndexError("ArrayIndexOutOfBoundsException")  # pattern[i] out of range, FM:456-457
         sub = p[offset:offset + length]
+        if ignore_case:  # (the count of every spelling, summed on the device)
+            counts, status = self.count_class_batch(*pack_class_patterns([_ignore_case(sub)]))
+            raise_for_status(status[0])
+            return int(counts[0])
         counts, status = self.count_batch(sub, np.array([0, len(sub)], dtype=np.int32))
         raise_for_status(status[0])
         return int(counts[0])
@@ -454,30 +599,40 @@ class FmIndex:
         raise_for_status(status[0])
         return int(found[0])
 
-    def locate_all(self, pattern, offset=0, length=None, maxMatches=-1):  # FM:487-552
-        """all occurrences as an int32 array of the library's making: locate() without the caller's `locations`"""
+    def locate_all(self, pattern, offset=0, length=None, maxMatches=-1, ignore_case=False):  # FM:487-552
+        """all occurrences as an int32 array of the library's making: locate() without the caller's `locations`.  ignore_case:
+        the occurrences of every spelling, one spelling after the other (no limit: maxMatches must be -1 or 0)"""
         p = as_chars(pattern)
         if length is None:
             length = len(p)
         if length <= 0 or offset < 0 or offset + length > len(p):
             raise IndexError("ArrayIndexOutOfBoundsException")
         sub = p[offset:offset + length]
+        if ignore_case:
+            if maxMatches > 0:
+                raise ValueError("ignore_case locates every occurrence: maxMatches must be -1 or 0")
+            locs, hit_off, status = self.locate_all_class_batch(*pack_class_patterns([_ignore_case(sub)]))
+            raise_for_status(status[0])
+            return locs
         locs, hit_off, status = self.locate_all_batch(sub, np.array([0, len(sub)], dtype=np.int32), maxMatches)
         raise_for_status(status[0])
         return locs
 
-    def match_lines(self, pattern, max_lines=0):
+    def match_lines(self, pattern, max_lines=0, ignore_case=False):
         """the ids of the lines that hold `pattern`, each once, ascending (grep -n); at most max_lines of them for max_lines > 0"""
         p = as_chars(pattern)
         if len(p) == 0:
             raise IndexError("ArrayIndexOutOfBoundsException")
+        if ignore_case:
+            return self.match_query(all=[p], max_lines=max_lines, ignore_case=True)
         lines, line_off, status = self.match_lines_batch(p, np.array([0, len(p)], dtype=np.int32), max_lines)
         raise_for_status(status[0])
         return lines
 
-    def match_query(self, all=(), any=(), none=(), max_lines=0):  # noqa: A002 (the words of the query)
+    def match_query(self, all=(), any=(), none=(), max_lines=0, ignore_case=False):  # noqa: A002 (the words of the query)
         """the ids of the lines that hold every pattern of `all`, at least one of `any` (if given) and none of `none`, each once,
-        ascending; at most max_lines of them for max_lines > 0.  Without `all` and `any` there are no lines (`none` filters)."""
+        ascending; at most max_lines of them for max_lines > 0.  Without `all` and `any` there are no lines (`none` filters).
+        ignore_case: every term in any case (class patterns: match_query_class_batch)."""
         terms, kinds = [], []
         for kind, group in enumerate((all, any, none)):  # (a lone str is one term)
             for p in ([group] if isinstance(group, str) else group):
@@ -485,8 +640,12 @@ class FmIndex:
                 kinds.append(kind)
         if min((len(t) for t in terms), default=1) == 0:
             raise IndexError("ArrayIndexOutOfBoundsException")
-        chars, offsets = pack_patterns(terms)
-        lines, line_off, status = self.match_query_batch(chars, offsets, [0, len(terms)], np.array(kinds, np.uint8), max_lines)
+        if ignore_case:
+            packed = pack_class_patterns([_ignore_case(t) for t in terms])
+            lines, line_off, status = self.match_query_class_batch(*packed, [0, len(terms)], np.array(kinds, np.uint8), max_lines)
+        else:
+            chars, offsets = pack_patterns(terms)
+            lines, line_off, status = self.match_query_batch(chars, offsets, [0, len(terms)], np.array(kinds, np.uint8), max_lines)
         for st in status:
             raise_for_status(st)
         return lines
@@ -498,15 +657,15 @@ class FmIndex:
             raise_for_status(st)
         return [chars[a:b].tobytes().decode("utf-16-le", "surrogatepass") for a, b in zip(text_off[:-1], text_off[1:])]
 
-    def grep(self, pattern=None, all=(), any=(), none=(), max_lines=0):  # noqa: A002 (the words of the query)
+    def grep(self, pattern=None, all=(), any=(), none=(), max_lines=0, ignore_case=False):  # noqa: A002 (the words of the query)
         """[(line id, line)] of the lines that hold `pattern` — or, without one, that match the query of all / any / none
         (match_query) — ascending, at most max_lines of them for max_lines > 0: match_lines / match_query, then line_text_batch"""
         if pattern is not None:
             if all or any or none:
                 raise ValueError("a pattern or a query, not both")
-            ids = self.match_lines(pattern, max_lines)
+            ids = self.match_lines(pattern, max_lines, ignore_case=ignore_case)
         else:
-            ids = self.match_query(all, any, none, max_lines)
+            ids = self.match_query(all, any, none, max_lines, ignore_case=ignore_case)
         return list(zip(ids.tolist(), self.line_text(ids)))
 
     def extract(self, start, stop, destination, offset=0):  # FM:564-608

@@ -251,7 +251,7 @@ int require_device(const fmx_index *idx, bool rrr_handle = false) {
 }
 
 constexpr int kWsPlan = 0, kWsBoundary = 1, kWsWalk = 2, kWsSegRange = 3, kWsSegCounts = 4;  // (kWsWalk: the walk order of locate, a plan-like head; kWsSegRange: a segment set's second {found, status, range} buffers)
-constexpr int kWsHitCounts = 5, kWsHitWindow = 6;  // fmx_locate_all_*: the hit counts and the scan's scratch; the host form's window of packed hits
+constexpr int kWsHitCounts = 5;  // fmx_locate_all_*: the hit counts and the scan's scratch
 
 // the side stream of `stream` with at least n_events events (nullptr: could not be made — the caller stays on one stream)
 fmx_index::SideLane *side_lane(const fmx_index *idx, void *stream, size_t n_events) {
@@ -305,6 +305,17 @@ int check_offsets(const int32_t *pat_off, int32_t n) {
     if (pat_off[0] < 0) return fail(FMX_E_ARG, "pattern offsets start below 0");
     for (int32_t i = 0; i < n; ++i)
         if (pat_off[i + 1] < pat_off[i]) return fail(FMX_E_ARG, "pattern offsets decrease");
+    return FMX_OK;
+}
+// ... and of a batch of class patterns: pos_off (n_pos + 1) cuts the alternatives into positions, pat_off (n + 1) the positions
+// into patterns
+int check_class_offsets(const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n) {
+    if (pos_off[0] < 0 || pat_off[0] < 0) return fail(FMX_E_ARG, "offsets start below 0");
+    for (int32_t j = 0; j < n_pos; ++j)
+        if (pos_off[j + 1] < pos_off[j]) return fail(FMX_E_ARG, "position offsets decrease");
+    for (int32_t i = 0; i < n; ++i)
+        if (pat_off[i + 1] < pat_off[i]) return fail(FMX_E_ARG, "pattern offsets decrease");
+    if (pat_off[n] > n_pos) return fail(FMX_E_ARG, "pattern offsets end behind the positions");
     return FMX_OK;
 }
 
@@ -372,6 +383,14 @@ struct DevBuf {
         return static_cast<T *>(p);
     }
 };
+int alloc_for_hits(DevBuf &b, size_t bytes) {  // scratch that grows with a batch's hits: running out of it is FMX_E_NOMEM
+    const hipError_t e = b.alloc(bytes);
+    if (e == hipSuccess) return FMX_OK;
+    (void)hipGetLastError();
+    b.p = nullptr;
+    if (e == hipErrorOutOfMemory) return fail(FMX_E_NOMEM, "out of device memory for " + std::to_string(bytes) + " bytes of scratch");
+    return fail(FMX_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+}
 
 // Pinned host staging of the pipelined host-buffer entry points, recycled like the device blocks (hipHostMalloc costs
 // more than a batch).
@@ -587,7 +606,9 @@ int pipe_streams(int device, PipeStreams **out) {
 
 // A host-buffer entry point runs its kernels on a stream of the calling thread's own — not the default stream, whose work the
 // plain copies around the kernels would wait behind (fmx_locate_lines_batch: 9.7 -> 6.9 ms per call) — and waits for that stream
-// whichever way it leaves: declare it AFTER the call's device buffers and scratch, so that they return to their caches later.
+// whichever way it leaves.  THE RULE that lets any number of host threads call these forms: declare it BEHIND every device block
+// (DevBuf, Scratch) the stream's work touches, so that the wait comes first and only then the blocks return to the recycling
+// cache, where another thread may take them at once.
 struct HostCallStream {
     hipStream_t s = nullptr;
     int init(int device) {
@@ -596,8 +617,20 @@ struct HostCallStream {
         if (rc == FMX_OK) s = ps->s[1];
         return rc;
     }
-    ~HostCallStream() {
+    void wait() {
         if (s) (void)hipStreamSynchronize(s);
+    }
+    ~HostCallStream() { wait(); }
+};
+// The malloc'ed answer of a host form (fmx_free_buffer is free): one that was not handed over is freed.
+struct HostResult {
+    void *p = nullptr;
+    ~HostResult() { free(p); }
+    bool alloc(size_t bytes) { return (p = malloc(bytes)) != nullptr; }
+    template <typename T>
+    void hand_over(T **to) {
+        *to = static_cast<T *>(p);
+        p = nullptr;
     }
 };
 
@@ -664,6 +697,14 @@ struct Scratch {
         HIP_TRY(owned.back()->alloc(bytes));
         *out = owned.back()->p;
         return FMX_OK;
+    }
+    // a per-call block whatever the entry point's kind, by alloc_for_hits's rule (the packed host forms)
+    template <typename T>
+    int block(size_t bytes, T **out) {
+        owned.emplace_back(new DevBuf());
+        const int rc = alloc_for_hits(*owned.back(), bytes);
+        *out = static_cast<T *>(owned.back()->p);
+        return rc;
     }
 };
 
@@ -1665,24 +1706,6 @@ int class_view(const fmx_index *idx, ClassView *view) {  // fmx_class_api.cpp: w
     *view = {&idx->dev, idx->n_cu, idx->device, image_is_compact(idx)};
     return FMX_OK;
 }
-int class_scratch_take(size_t *bytes, int *device, void **p) {  // a block of the host forms' recycling cache (DevBuf's rule)
-    DevBuf b;
-    const hipError_t e = b.alloc(*bytes);
-    *bytes = b.bytes;
-    *device = b.device;
-    *p = e == hipSuccess ? b.p : nullptr;
-    b.p = nullptr;
-    return (int)e;
-}
-void class_scratch_give(int device, size_t bytes, void *p) {
-    if (p && !g_scratch.give(device, bytes, p)) (void)hipFree(p);
-}
-int class_call_stream(int device, void **stream) {  // the calling thread's kernel stream on that device
-    PipeStreams *ps = nullptr;
-    const int rc = pipe_streams(device, &ps);
-    if (rc == FMX_OK) *stream = ps->s[1];
-    return rc;
-}
 }  // namespace fmx
 }
 
@@ -1735,6 +1758,222 @@ int fmx_locate_all_fill_dev(const fmx_index *idx, int32_t n, const int64_t *d_hi
     });
 }
 
+// ---- the packed host forms: ONE sequence for literal and class patterns --------------------------------------------------------
+// fmx_locate_all_batch, fmx_match_lines_batch, fmx_match_query_batch and their class forms (fmx_count_class_batch,
+// fmx_locate_all_class_batch, fmx_match_query_class_batch) check their own arguments and then run
+//   a range stage   literal_ranges / class_ranges: the batch goes up, the SA ranges and the packed hit layout are made, ONE 8-byte
+//                   read and wait brings the hit total down (class patterns: one more before it, for the number of ranges);
+//   the fill        fill_hits: k_locate_all over the ranges, hits [first, first + count) into a device block;
+//   a way down      hits_down (the result malloc'ed to the total, windows of kLocateAllWindow hits, each copied into its place) or
+//                   lines_down (every hit at once: the sort wants them all; the line stage, ONE 8-byte read and wait for the
+//                   number of lines, the result malloc'ed to that size);
+//   packed_finish   the per-pattern arrays come down, the last wait, and only then the result is the caller's.
+// Every device block of the call belongs to PackedCall::blocks.  Nothing of the caller's is written before the last wait has
+// succeeded; *locs / *lines stay NULL on every failure.
+namespace {
+struct PackedCall {  // (the members' order is HostCallStream's rule: the stream is waited for, then the result and the blocks go)
+    Scratch blocks;
+    HostResult result;
+    HostCallStream stream;
+    explicit PackedCall(const fmx_index *idx) : blocks(idx, nullptr, true) {}
+    // ... and the blocks go back last taken first, as locals would: the hit-sized ones ahead of the small ones.  The cache keeps what
+    // fits under its limit in the order it is given, so the order decides which large blocks the next call finds there.
+    ~PackedCall() {
+        stream.wait();
+        while (!blocks.owned.empty()) blocks.owned.pop_back();
+    }
+    int open() {  // the calling thread's stream on the index's device
+        const int rc = stream.init(blocks.idx->device);
+        blocks.stream = stream.s;
+        return rc;
+    }
+};
+
+// what a range stage leaves on the device
+struct RangeStage {
+    int32_t n = 0, n_ranges = 0;       // patterns; SA ranges: n for literal patterns, m for class patterns
+    int32_t *ranges = nullptr;         // n_ranges {start, end} pairs
+    int64_t *range_hit_off = nullptr;  // n_ranges + 1: where the hits of each range begin (literal patterns: hit_off itself)
+    int64_t *hit_off = nullptr;        // n + 1: where the hits of each pattern begin
+    int64_t total = 0;                 // hit_off[n], read once
+    int32_t *counts = nullptr, *lf_steps = nullptr, *status = nullptr;  // per pattern, where the stage was asked for them
+    int64_t *range_off = nullptr;      // class patterns: n + 1, the ranges of each pattern ...
+    int32_t *range_status = nullptr;   // ... and, where the caller wants statuses, the walk status of each range (fill_hits folds them)
+};
+
+constexpr int64_t kLocateAllWindow = (int64_t)1 << 24;  // 64 MiB of positions
+}  // namespace
+
+static int read_hit_total(PackedCall &call, RangeStage &r) {
+    HIP_TRY(hipMemcpyAsync(&r.total, r.hit_off + r.n, 8, hipMemcpyDeviceToHost, call.stream.s));
+    HIP_TRY(hipStreamSynchronize(call.stream.s));
+    return FMX_OK;
+}
+
+// n > 0 literal patterns (the handle checked): pat_off is judged, pat and pat_off go up, locate_all_ranges_impl, the total
+static int literal_ranges(PackedCall &call, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t max_matches, bool want_counts,
+                          bool want_steps, bool want_status, RangeStage &r) {
+    const fmx_index *idx = call.blocks.idx;
+    HIP_TRY(hipSetDevice(idx->device));
+    int rc = check_offsets(pat_off, n);
+    if (rc) return rc;
+    const size_t chars = (size_t)(pat_off[n] > 0 ? pat_off[n] : 0), first = first_char(pat_off);
+    if (chars > first && !pat) return fail(FMX_E_ARG, "bad arguments");
+    if ((rc = call.open())) return rc;
+    Scratch &b = call.blocks;
+    const hipStream_t st = call.stream.s;
+    uint16_t *d_pat = nullptr;
+    int32_t *d_off = nullptr;
+    if ((rc = b.block(chars * 2 + 8, &d_pat)) || (rc = b.block((size_t)(n + 1) * 4, &d_off)) || (rc = b.block((size_t)(n + 1) * 8, &r.hit_off)) ||
+        (rc = b.block((size_t)n * 8, &r.ranges)) || (want_counts && (rc = b.block((size_t)n * 4, &r.counts))) ||
+        (want_steps && (rc = b.block((size_t)n * 4, &r.lf_steps))) || (want_status && (rc = b.block((size_t)n * 4, &r.status))))
+        return rc;
+    if (chars > first) HIP_TRY(hipMemcpyAsync(d_pat + first, pat + first, (chars - first) * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off, pat_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
+    if ((rc = locate_all_ranges_impl(idx, d_pat, d_off, n, max_matches, r.hit_off, r.lf_steps, r.status, r.ranges, b, r.counts))) return rc;
+    r.n = r.n_ranges = n;
+    r.range_hit_off = r.hit_off;
+    return read_hit_total(call, r);
+}
+
+// the HOST arrays of a class batch and the handle (the arrays first: they are judged on any handle)
+static int class_args(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n,
+                      int32_t max_ranges) {
+    if (!idx || n < 0 || n_pos < 0 || !pos_off || !pat_off || max_ranges < 1 || max_ranges > FMX_CLASS_RANGES_MAX)
+        return fail(FMX_E_ARG, "bad arguments");
+    if (const int rc = check_class_offsets(pos_off, n_pos, pat_off, n)) return rc;
+    if (pos_off[n_pos] > 0 && !alt) return fail(FMX_E_ARG, "bad arguments");
+    return require_fm_device(idx);
+}
+
+// n > 0 class patterns (class_args passed): the arrays go up and fmx_class_ranges_count_dev counts — what fmx_count_class_batch
+// wants; with want_ranges the number of ranges m comes down, fmx_class_ranges_fill_dev, fmx_class_hit_offsets_dev, the total
+static int class_ranges(PackedCall &call, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n,
+                        int32_t max_ranges, bool want_ranges, bool want_status, RangeStage &r) {
+    const fmx_index *idx = call.blocks.idx;
+    HIP_TRY(hipSetDevice(idx->device));
+    int rc = call.open();
+    if (rc) return rc;
+    Scratch &b = call.blocks;
+    const hipStream_t st = call.stream.s;
+    const size_t alts = (size_t)pos_off[n_pos], ws_bytes = fmx_class_ranges_scratch_bytes(n);
+    uint16_t *d_alt = nullptr;
+    int32_t *d_pos = nullptr, *d_pat = nullptr;
+    void *ws = nullptr;
+    if ((rc = b.block(alts * 2 + 8, &d_alt)) || (rc = b.block(((size_t)n_pos + 1) * 4, &d_pos)) || (rc = b.block(((size_t)n + 1) * 4, &d_pat)) ||
+        (rc = b.block(((size_t)n + 1) * 8, &r.range_off)) || (rc = b.block((size_t)n * 4, &r.counts)) ||
+        (rc = b.block((size_t)n * 4, &r.status)) || (rc = b.block(ws_bytes, &ws)))
+        return rc;
+    if (alts) HIP_TRY(hipMemcpyAsync(d_alt, alt, alts * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_pos, pos_off, ((size_t)n_pos + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_pat, pat_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
+    r.n = n;
+    rc = fmx_class_ranges_count_dev(idx, d_alt, d_pos, d_pat, n, max_ranges, r.range_off, r.counts, r.status, ws, ws_bytes, st);
+    if (rc || !want_ranges) return rc;
+    int64_t m = 0;
+    HIP_TRY(hipMemcpyAsync(&m, r.range_off + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (m > INT32_MAX) return fail(FMX_E_ARG, "more than 2^31 - 1 ranges in one batch");
+    r.n_ranges = (int32_t)m;
+    const size_t hit_ws_bytes = fmx_class_hit_offsets_scratch_bytes(m);
+    void *hit_ws = nullptr;
+    if ((rc = b.block((size_t)m * 8, &r.ranges)) || (rc = b.block(((size_t)m + 1) * 8, &r.range_hit_off)) ||
+        (rc = b.block(((size_t)n + 1) * 8, &r.hit_off)) || (rc = b.block(hit_ws_bytes, &hit_ws)) ||
+        (want_status && (rc = b.block((size_t)m * 4, &r.range_status))))
+        return rc;
+    if ((rc = fmx_class_ranges_fill_dev(idx, d_alt, d_pos, d_pat, n, max_ranges, r.range_off, r.ranges, st)) ||
+        (rc = fmx_class_hit_offsets_dev(idx, n, r.range_off, r.ranges, m, r.range_hit_off, r.hit_off, hit_ws, hit_ws_bytes, st)))
+        return rc;
+    return read_hit_total(call, r);
+}
+
+// hits [first, first + count) of the stage's total into d_locs.  Class ranges whose caller wants statuses: the walks' go to the
+// ranges — zeroed before the first hit, folded into their patterns' after the last.
+static int fill_hits(PackedCall &call, RangeStage &r, int64_t first, int64_t count, int32_t *d_locs) {
+    if (count <= 0) return FMX_OK;
+    const fmx_index *idx = call.blocks.idx;
+    const hipStream_t st = call.stream.s;
+    if (r.range_status && first == 0) HIP_TRY(hipMemsetAsync(r.range_status, 0, (size_t)r.n_ranges * 4, st));
+    const int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, r.ranges, r.range_hit_off, r.n_ranges, first, count, d_locs, r.lf_steps,
+                                      r.range_off ? r.range_status : r.status, st);
+    if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
+    if (r.range_status && first + count == r.total)
+        return fmx_class_fold_status_dev(idx, r.n, r.range_off, r.n_ranges, r.range_status, r.status, st);
+    return FMX_OK;
+}
+
+// the hits themselves: the result malloc'ed to the total, one window of device scratch filled and copied into its place over and over
+static int hits_down(PackedCall &call, RangeStage &r, int64_t *hit_off) {
+    const hipStream_t st = call.stream.s;
+    if (r.total > 0) {
+        if ((uint64_t)r.total > SIZE_MAX / 4) return fail(FMX_E_NOMEM, "the batch's hits do not fit this host's address space");
+        if (!call.result.alloc((size_t)r.total * 4)) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(r.total) + " hits");
+        const int64_t window = r.total < kLocateAllWindow ? r.total : kLocateAllWindow;
+        int32_t *d_win = nullptr;
+        int rc = call.blocks.block((size_t)window * 4, &d_win);
+        if (rc) return rc;
+        for (int64_t at = 0; at < r.total; at += window) {
+            const int64_t hits = r.total - at < window ? r.total - at : window;
+            if ((rc = fill_hits(call, r, at, hits, d_win))) return rc;
+            HIP_TRY(hipMemcpyAsync(static_cast<int32_t *>(call.result.p) + at, d_win, (size_t)hits * 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(hit_off, r.hit_off, (size_t)(r.n + 1) * 8, hipMemcpyDeviceToHost, st));
+    return FMX_OK;
+}
+
+// the lines of the hits: of every pattern (query_off == NULL: launch_lines_of_hits, n groups) or of the q queries that query_off
+// and term_kind make of the patterns (launch_query_lines, q groups).  line_off gets groups + 1 entries, line_count groups.
+static int lines_down(PackedCall &call, RangeStage &r, const int32_t *query_off, const uint8_t *term_kind, int32_t q, int32_t max_lines,
+                      int64_t *line_off, int32_t *line_count) {
+    const fmx_index *idx = call.blocks.idx;
+    Scratch &b = call.blocks;
+    const hipStream_t st = call.stream.s;
+    const int32_t n = r.n, groups = query_off ? q : n;
+    if (r.total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
+    int64_t *d_loff = nullptr, n_out = 0;
+    int32_t *d_lcnt = nullptr, *d_locs = nullptr, *d_lines = nullptr;
+    int rc;
+    if ((rc = b.block((size_t)(groups + 1) * 8, &d_loff)) || (rc = b.block((size_t)groups * 4 + 4, &d_lcnt))) return rc;
+    if (r.total > 0 && groups > 0) {
+        const size_t ws_bytes = query_off ? fmx::query_lines_scratch_bytes(n, q, r.total) : fmx::lines_of_hits_scratch_bytes(n, r.total);
+        void *ws = nullptr;
+        if ((rc = b.block((size_t)r.total * 4, &d_locs)) || (rc = b.block((size_t)r.total * 4, &d_lines)) || (rc = b.block(ws_bytes, &ws)) ||
+            (rc = fill_hits(call, r, 0, r.total, d_locs)))
+            return rc;
+        const int32_t *table = static_cast<const int32_t *>(idx->d_line_table);
+        const int e = query_off ? fmx::launch_query_lines(table, idx->line_count, idx->n_cu, n, q, query_off, term_kind, r.hit_off, d_locs, r.total,
+                                                          max_lines, d_loff, d_lines, d_lcnt, ws, ws_bytes, st)
+                                : fmx::launch_lines_of_hits(table, idx->line_count, idx->n_cu, n, r.hit_off, d_locs, r.total, max_lines, d_loff,
+                                                            d_lines, d_lcnt, ws, ws_bytes, st);
+        if (e) return fail(FMX_E_HIP, std::string(query_off ? "lines of queries: " : "lines of hits: ") + hipGetErrorString((hipError_t)e));
+        HIP_TRY(hipMemcpyAsync(&n_out, d_loff + groups, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        HIP_TRY(hipMemsetAsync(d_loff, 0, (size_t)(groups + 1) * 8, st));
+        HIP_TRY(hipMemsetAsync(d_lcnt, 0, (size_t)groups * 4 + 4, st));
+    }
+    if (n_out > 0) {
+        if (!call.result.alloc((size_t)n_out * 4)) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(n_out) + " lines");
+        HIP_TRY(hipMemcpyAsync(call.result.p, d_lines, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(line_off, d_loff, (size_t)(groups + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (line_count && groups > 0) HIP_TRY(hipMemcpyAsync(line_count, d_lcnt, (size_t)groups * 4, hipMemcpyDeviceToHost, st));
+    return FMX_OK;
+}
+
+// the per-pattern arrays the caller wants, the last wait, the result handed over (a form without one: result == NULL)
+static int packed_finish(PackedCall &call, RangeStage &r, int32_t *counts, int32_t *lf_steps, int32_t *status, int32_t **result) {
+    const hipStream_t st = call.stream.s;
+    const size_t bytes = (size_t)r.n * 4;
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, r.counts, bytes, hipMemcpyDeviceToHost, st));
+    if (lf_steps) HIP_TRY(hipMemcpyAsync(lf_steps, r.lf_steps, bytes, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, r.status, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (result) call.result.hand_over(result);
+    return FMX_OK;
+}
+
 // ---- lines: the line table of a resident index, packed hits -> packed distinct lines (fmx_hit_lines.hip) ------------------------
 static int require_line_table(const fmx_index *idx) {
     if (!idx->d_line_table) return fail(FMX_E_ARG, "the index has no line table (call fmx_line_table_build)");
@@ -1742,20 +1981,6 @@ static int require_line_table(const fmx_index *idx) {
 }
 // the text as the caller handed it over: getInputLength() counts the terminator the constructor appends (FM:300-305)
 static int32_t line_text_length(const fmx_index *idx) { return idx->hdr.length > 0 ? (int32_t)idx->hdr.length - 1 : 0; }
-// whatever leaves a host-synchronous call first waits for its stream; declared BEHIND the call's device blocks, so that they
-// return to their cache only afterwards
-struct StreamWait {
-    hipStream_t s;
-    ~StreamWait() { (void)hipStreamSynchronize(s); }
-};
-static int alloc_for_hits(DevBuf &b, size_t bytes) {  // scratch that grows with a batch's hits: running out of it is FMX_E_NOMEM
-    const hipError_t e = b.alloc(bytes);
-    if (e == hipSuccess) return FMX_OK;
-    (void)hipGetLastError();
-    b.p = nullptr;
-    if (e == hipErrorOutOfMemory) return fail(FMX_E_NOMEM, "out of device memory for " + std::to_string(bytes) + " bytes of scratch");
-    return fail(FMX_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-}
 
 int fmx_line_table_build(fmx_index *idx, uint16_t boundary, int64_t *n_lines) {
     return guarded([&]() -> int {
@@ -1766,62 +1991,44 @@ int fmx_line_table_build(fmx_index *idx, uint16_t boundary, int64_t *n_lines) {
         if (n_lines) *n_lines = idx->n_lines;
         return FMX_OK;
     }
-    HIP_TRY(hipSetDevice(idx->device));
-    PipeStreams *ps = nullptr;
-    rc = pipe_streams(idx->device, &ps);
-    if (rc) return rc;
-    hipStream_t st = ps->s[1];
-    DevBuf d_pat, d_off, d_hit, d_ws, d_locs, d_sort;
-    HIP_TRY(d_pat.alloc(16));
-    HIP_TRY(d_off.alloc(8));
-    HIP_TRY(d_hit.alloc(16));
-    HIP_TRY(d_ws.alloc(8));
-    Scratch scratch(idx, st, true);
-    void *table = nullptr;
-    struct Leave {  // the stream first, then a table that was not handed over
-        hipStream_t s;
-        void **table;
-        ~Leave() {
-            (void)hipStreamSynchronize(s);
-            if (*table) (void)hipFree(*table);
+    struct DeviceTable {  // a table that was not handed over; in front of the call: freed after the stream has been waited for
+        void *p = nullptr;
+        ~DeviceTable() {
+            if (p) (void)hipFree(p);
         }
-    } leave{st, &table};
-    // T = what locate(new char[]{boundary}, locations) returns: the range search and k_locate_all for the one-character pattern
-    const int32_t off_h[2] = {0, 1};
-    H2D(d_pat.p, &boundary, 2);
-    H2D(d_off.p, off_h, 8);
-    rc = locate_all_ranges_impl(idx, d_pat.as<uint16_t>(), d_off.as<int32_t>(), 1, -1, d_hit.as<int64_t>(), nullptr, nullptr,
-                                d_ws.as<int32_t>(), scratch);
-    if (rc) return rc;
-    int64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_hit.as<int64_t>() + 1, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    } made;
+    PackedCall call(idx);
+    RangeStage r;
+    // T = what locate(new char[]{boundary}, locations) returns: the range stage and the fill for the one-character pattern
+    const int32_t one[2] = {0, 1};
+    if ((rc = literal_ranges(call, &boundary, one, 1, -1, false, false, false, r))) return rc;
+    const hipStream_t st = call.stream.s;
+    const int64_t total = r.total;
     if (total < 0 || total > 0x7fffffff) return fail(FMX_E_UNSUPPORTED, "more boundaries than an int32 line id holds");
     const size_t bytes = (((size_t)total * 4 + 63) & ~(size_t)63) + 64;
-    if (hipMalloc(&table, bytes) != hipSuccess) {
+    if (hipMalloc(&made.p, bytes) != hipSuccess) {
         (void)hipGetLastError();
-        table = nullptr;
+        made.p = nullptr;
         return fail(FMX_E_NOMEM, "out of device memory for a line table of " + std::to_string(total) + " boundaries");
     }
+    void *const table = made.p;
     const size_t sort_bytes = fmx::line_table_scratch_bytes((int32_t)total);
-    if ((rc = alloc_for_hits(d_locs, (size_t)total * 4 + 8))) return rc;
-    if ((rc = alloc_for_hits(d_sort, sort_bytes))) return rc;
-    if (total > 0) {
-        int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_ws.as<int32_t>(), d_hit.as<int64_t>(), 1, (int64_t)0, total,
-                                    d_locs.as<int32_t>(), nullptr, nullptr, st);
-        if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
-    }
+    int32_t *d_locs = nullptr;
+    void *d_sort = nullptr;
+    if ((rc = call.blocks.block((size_t)total * 4 + 8, &d_locs)) || (rc = call.blocks.block(sort_bytes, &d_sort)) ||
+        (rc = fill_hits(call, r, 0, total, d_locs)))
+        return rc;
     // (the line count lands behind the hits, in a slot of the same block)
     int64_t *d_lines_total = reinterpret_cast<int64_t *>(static_cast<uint8_t *>(table) + bytes - 64);
-    int e = fmx::launch_line_table(d_locs.as<int32_t>(), (int32_t)total, line_text_length(idx), static_cast<int32_t *>(table), d_lines_total,
-                                   d_sort.p, sort_bytes, st);
+    int e = fmx::launch_line_table(d_locs, (int32_t)total, line_text_length(idx), static_cast<int32_t *>(table), d_lines_total, d_sort,
+                                   sort_bytes, st);
     if (e) return fail(FMX_E_HIP, std::string("line table sort: ") + hipGetErrorString((hipError_t)e));
     int64_t lines = 0;
     HIP_TRY(hipMemcpyAsync(&lines, d_lines_total, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (idx->d_line_table) (void)hipFree(idx->d_line_table);  // another boundary's
     idx->d_line_table = table;
-    table = nullptr;
+    made.p = nullptr;
     idx->line_table_bytes = bytes;
     idx->line_boundary = (int32_t)boundary;
     idx->line_count = (int32_t)total;
@@ -1863,15 +2070,13 @@ int fmx_line_bounds_batch(const fmx_index *idx, const int32_t *lines, int32_t n,
     if ((rc = require_line_table(idx))) return rc;
     if (n == 0) return FMX_OK;
     HIP_TRY(hipSetDevice(idx->device));
-    PipeStreams *ps = nullptr;
-    rc = pipe_streams(idx->device, &ps);
-    if (rc) return rc;
-    hipStream_t st = ps->s[1];
     DevBuf d_in, d_start, d_stop;
     HIP_TRY(d_in.alloc((size_t)n * 4));
     HIP_TRY(d_start.alloc((size_t)n * 4));
     HIP_TRY(d_stop.alloc((size_t)n * 4));
-    StreamWait wait{st};
+    HostCallStream stream;
+    if ((rc = stream.init(idx->device))) return rc;
+    const hipStream_t st = stream.s;
     HIP_TRY(hipMemcpyAsync(d_in.p, lines, (size_t)n * 4, hipMemcpyHostToDevice, st));
     int e = fmx::launch_line_bounds(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_lines, line_text_length(idx),
                                     idx->n_cu, d_in.as<int32_t>(), n, d_start.as<int32_t>(), d_stop.as<int32_t>(), st);
@@ -3031,10 +3236,7 @@ int fmx_locate_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *p
     });
 }
 
-// The host form of "all occurrences": stage 1, ONE 8-byte copy and wait for the batch's total, the result malloc'ed to that size
-// (fmx_free_buffer is free), then stage 2 in windows of kLocateAllWindow hits of device scratch, each copied straight into its
-// place in the result.
-constexpr int64_t kLocateAllWindow = (int64_t)1 << 24;  // 64 MiB of positions
+// ---- the packed host forms (the sequence: "the packed host forms" above) ---------------------------------------------------------
 int fmx_locate_all_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t max_matches,
                          int64_t *hit_off, int32_t **locs, int32_t *lf_steps, int32_t *status) {
     return guarded([&]() -> int {
@@ -3046,69 +3248,16 @@ int fmx_locate_all_batch(const fmx_index *idx, const uint16_t *pat, const int32_
         hit_off[0] = 0;
         return FMX_OK;
     }
-    HIP_TRY(hipSetDevice(idx->device));
-    rc = check_offsets(pat_off, n);
-    if (rc) return rc;
-    const size_t chars = (size_t)(pat_off[n] > 0 ? pat_off[n] : 0), first = first_char(pat_off);
-    if (chars > first && !pat) return fail(FMX_E_ARG, "bad arguments");
-    DevBuf d_pat, d_off, d_hit, d_lf, d_st, d_ws;
-    HIP_TRY(d_pat.alloc(chars * 2 + 8));
-    HIP_TRY(d_off.alloc((size_t)(n + 1) * 4));
-    HIP_TRY(d_hit.alloc((size_t)(n + 1) * 8));
-    if (lf_steps) HIP_TRY(d_lf.alloc((size_t)n * 4));
-    if (status) HIP_TRY(d_st.alloc((size_t)n * 4));
-    HIP_TRY(d_ws.alloc((size_t)n * 8));
-    PipeStreams *ps = nullptr;
-    rc = pipe_streams(idx->device, &ps);
-    if (rc) return rc;
-    hipStream_t st = ps->s[1];
-    Scratch scratch(idx, st, true);
-    struct Result {  // what leaves this function first waits for the stream, THEN the per-call blocks (declared above) return to their
-        hipStream_t s;  // cache; a result that was not handed over is freed
-        int32_t *p = nullptr;
-        ~Result() {
-            (void)hipStreamSynchronize(s);
-            free(p);
-        }
-    } result{st};
-    if (chars > first) HIP_TRY(hipMemcpyAsync(d_pat.as<uint16_t>() + first, pat + first, (chars - first) * 2, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_off.p, pat_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
-    int32_t *dlf = lf_steps ? d_lf.as<int32_t>() : nullptr, *dst_ = status ? d_st.as<int32_t>() : nullptr;
-    rc = locate_all_ranges_impl(idx, d_pat.as<uint16_t>(), d_off.as<int32_t>(), n, max_matches, d_hit.as<int64_t>(), dlf, dst_,
-                                d_ws.as<int32_t>(), scratch);
-    if (rc) return rc;
-    int64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_hit.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (total > 0) {
-        if ((uint64_t)total > SIZE_MAX / 4) return fail(FMX_E_NOMEM, "the batch's hits do not fit this host's address space");
-        result.p = static_cast<int32_t *>(malloc((size_t)total * 4));
-        if (!result.p) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(total) + " hits");
-        const int64_t window = total < kLocateAllWindow ? total : kLocateAllWindow;
-        void *d_win = nullptr;
-        rc = scratch.get(kWsHitWindow, (size_t)window * 4, &d_win);
-        if (rc) return rc;
-        for (int64_t at = 0; at < total; at += window) {
-            const int64_t hits = total - at < window ? total - at : window;
-            int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_ws.as<int32_t>(), d_hit.as<int64_t>(), n, at, hits,
-                                        static_cast<int32_t *>(d_win), dlf, dst_, st);
-            if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
-            HIP_TRY(hipMemcpyAsync(result.p + at, d_win, (size_t)hits * 4, hipMemcpyDeviceToHost, st));
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(hit_off, d_hit.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (lf_steps) HIP_TRY(hipMemcpyAsync(lf_steps, d_lf.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *locs = result.p;
-    result.p = nullptr;
-    return FMX_OK;
+    PackedCall call(idx);
+    RangeStage r;
+    if ((rc = literal_ranges(call, pat, pat_off, n, max_matches, false, lf_steps != nullptr, status != nullptr, r)) ||
+        (rc = hits_down(call, r, hit_off)))
+        return rc;
+    return packed_finish(call, r, nullptr, lf_steps, status, locs);
     });
 }
 
-// The host form of "which lines match": stage 1 and stage 2 of "all occurrences" (every hit, no limit, no windows: the sort wants
-// them all at once), fmx_lines_of_hits_dev's stages, ONE 8-byte copy and wait for the number of lines, the result malloc'ed to
-// that size.  What comes down is the lines, not the hits.
+// what comes down is the lines, not the hits (every hit, no limit on them)
 int fmx_match_lines_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, int32_t max_lines,
                           int64_t *line_off, int32_t **lines, int32_t *line_count, int32_t *occurrences, int32_t *status) {
     return guarded([&]() -> int {
@@ -3121,81 +3270,20 @@ int fmx_match_lines_batch(const fmx_index *idx, const uint16_t *pat, const int32
         line_off[0] = 0;
         return FMX_OK;
     }
-    HIP_TRY(hipSetDevice(idx->device));
-    rc = check_offsets(pat_off, n);
-    if (rc) return rc;
-    const size_t chars = (size_t)(pat_off[n] > 0 ? pat_off[n] : 0), first = first_char(pat_off);
-    if (chars > first && !pat) return fail(FMX_E_ARG, "bad arguments");
-    DevBuf d_pat, d_off, d_hit, d_cnt, d_st, d_rng, d_loff, d_lcnt, d_locs, d_lines, d_ws;
-    HIP_TRY(d_pat.alloc(chars * 2 + 8));
-    HIP_TRY(d_off.alloc((size_t)(n + 1) * 4));
-    HIP_TRY(d_hit.alloc((size_t)(n + 1) * 8));
-    HIP_TRY(d_loff.alloc((size_t)(n + 1) * 8));
-    HIP_TRY(d_cnt.alloc((size_t)n * 4));
-    HIP_TRY(d_lcnt.alloc((size_t)n * 4));
-    if (status) HIP_TRY(d_st.alloc((size_t)n * 4));
-    HIP_TRY(d_rng.alloc((size_t)n * 8));
-    PipeStreams *ps = nullptr;
-    rc = pipe_streams(idx->device, &ps);
-    if (rc) return rc;
-    hipStream_t st = ps->s[1];
-    Scratch scratch(idx, st, true);
-    struct Result {  // (as in fmx_locate_all_batch)
-        hipStream_t s;
-        int32_t *p = nullptr;
-        ~Result() {
-            (void)hipStreamSynchronize(s);
-            free(p);
-        }
-    } result{st};
-    if (chars > first) HIP_TRY(hipMemcpyAsync(d_pat.as<uint16_t>() + first, pat + first, (chars - first) * 2, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_off.p, pat_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
-    int32_t *dst_ = status ? d_st.as<int32_t>() : nullptr;
-    rc = locate_all_ranges_impl(idx, d_pat.as<uint16_t>(), d_off.as<int32_t>(), n, -1, d_hit.as<int64_t>(), nullptr, dst_, d_rng.as<int32_t>(),
-                                scratch, d_cnt.as<int32_t>());
-    if (rc) return rc;
-    int64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_hit.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
-    int64_t n_out = 0;
-    if (total > 0) {
-        const size_t ws_bytes = fmx::lines_of_hits_scratch_bytes(n, total);
-        if ((rc = alloc_for_hits(d_locs, (size_t)total * 4))) return rc;
-        if ((rc = alloc_for_hits(d_lines, (size_t)total * 4))) return rc;
-        if ((rc = alloc_for_hits(d_ws, ws_bytes))) return rc;
-        int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_rng.as<int32_t>(), d_hit.as<int64_t>(), n, (int64_t)0, total,
-                                    d_locs.as<int32_t>(), nullptr, dst_, st);
-        if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
-        e = fmx::launch_lines_of_hits(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_cu, n, d_hit.as<int64_t>(),
-                                      d_locs.as<int32_t>(), total, max_lines, d_loff.as<int64_t>(), d_lines.as<int32_t>(), d_lcnt.as<int32_t>(),
-                                      d_ws.p, d_ws.bytes, st);
-        if (e) return fail(FMX_E_HIP, std::string("lines of hits: ") + hipGetErrorString((hipError_t)e));
-        HIP_TRY(hipMemcpyAsync(&n_out, d_loff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    } else {
-        HIP_TRY(hipMemsetAsync(d_loff.p, 0, (size_t)(n + 1) * 8, st));
-        HIP_TRY(hipMemsetAsync(d_lcnt.p, 0, (size_t)n * 4, st));
-    }
-    if (n_out > 0) {
-        result.p = static_cast<int32_t *>(malloc((size_t)n_out * 4));
-        if (!result.p) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(n_out) + " lines");
-        HIP_TRY(hipMemcpyAsync(result.p, d_lines.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(line_off, d_loff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (line_count) HIP_TRY(hipMemcpyAsync(line_count, d_lcnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (occurrences) HIP_TRY(hipMemcpyAsync(occurrences, d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *lines = result.p;
-    result.p = nullptr;
-    return FMX_OK;
+    PackedCall call(idx);
+    RangeStage r;
+    if ((rc = literal_ranges(call, pat, pat_off, n, -1, true, false, status != nullptr, r)) ||
+        (rc = lines_down(call, r, nullptr, nullptr, 0, max_lines, line_off, line_count)))
+        return rc;
+    return packed_finish(call, r, occurrences, nullptr, status, lines);
     });
 }
 
-// The host form of "which lines match each QUERY": fmx_match_lines_batch's sequence with the query stage in place of
-// launch_lines_of_hits — the range stage, ONE 8-byte read of the hit total, the fill, fmx_query_lines_of_hits_dev's stages, ONE 8-byte
-// read of the line total, the result malloc'ed to that size.  What comes down is the lines of the queries.
+static void no_terms_no_lines(int32_t q, int64_t *line_off, int32_t *line_count) {  // queries without terms
+    for (int32_t i = 0; i <= q; ++i) line_off[i] = 0;
+    for (int32_t i = 0; i < q && line_count; ++i) line_count[i] = 0;
+}
+
 int fmx_match_query_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const int32_t *query_off,
                           const uint8_t *term_kind, int32_t q, int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t *line_count,
                           int32_t *occurrences, int32_t *status) {
@@ -3208,80 +3296,76 @@ int fmx_match_query_batch(const fmx_index *idx, const uint16_t *pat, const int32
     if ((rc = require_fm_device(idx))) return rc;
     if ((rc = require_line_table(idx))) return rc;
     if ((rc = check_query_key_width(idx, q, query_off))) return rc;
-    if (n == 0) {  // queries without terms: no lines
-        for (int32_t i = 0; i <= q; ++i) line_off[i] = 0;
-        for (int32_t i = 0; i < q && line_count; ++i) line_count[i] = 0;
+    if (n == 0) {
+        no_terms_no_lines(q, line_off, line_count);
         return FMX_OK;
     }
-    HIP_TRY(hipSetDevice(idx->device));
-    rc = check_offsets(pat_off, n);
+    PackedCall call(idx);
+    RangeStage r;
+    if ((rc = literal_ranges(call, pat, pat_off, n, -1, true, false, status != nullptr, r)) ||
+        (rc = lines_down(call, r, query_off, term_kind, q, max_lines, line_off, line_count)))
+        return rc;
+    return packed_finish(call, r, occurrences, nullptr, status, lines);
+    });
+}
+
+// stage 1 of the class search alone: the counts and the statuses come down, no range is stored
+int fmx_count_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n,
+                          int32_t max_ranges, int32_t *counts, int32_t *status) {
+    return guarded([&]() -> int {
+    if (n > 0 && !counts) return fail(FMX_E_ARG, "bad arguments");
+    int rc = class_args(idx, alt, pos_off, n_pos, pat_off, n, max_ranges);
+    if (rc || n == 0) return rc;
+    PackedCall call(idx);
+    RangeStage r;
+    if ((rc = class_ranges(call, alt, pos_off, n_pos, pat_off, n, max_ranges, false, false, r))) return rc;
+    return packed_finish(call, r, counts, nullptr, status, nullptr);
+    });
+}
+
+int fmx_locate_all_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                               int32_t n, int32_t max_ranges, int64_t *hit_off, int32_t **locs, int32_t *status) {
+    return guarded([&]() -> int {
+    if (locs) *locs = nullptr;
+    if (!hit_off || !locs) return fail(FMX_E_ARG, "bad arguments");
+    int rc = class_args(idx, alt, pos_off, n_pos, pat_off, n, max_ranges);
     if (rc) return rc;
-    const size_t chars = (size_t)(pat_off[n] > 0 ? pat_off[n] : 0), first = first_char(pat_off);
-    if (chars > first && !pat) return fail(FMX_E_ARG, "bad arguments");
-    DevBuf d_pat, d_off, d_hit, d_cnt, d_st, d_rng, d_loff, d_lcnt, d_locs, d_lines, d_ws;
-    HIP_TRY(d_pat.alloc(chars * 2 + 8));
-    HIP_TRY(d_off.alloc((size_t)(n + 1) * 4));
-    HIP_TRY(d_hit.alloc((size_t)(n + 1) * 8));
-    HIP_TRY(d_loff.alloc((size_t)(q + 1) * 8));
-    HIP_TRY(d_cnt.alloc((size_t)n * 4));
-    HIP_TRY(d_lcnt.alloc((size_t)q * 4 + 4));
-    if (status) HIP_TRY(d_st.alloc((size_t)n * 4));
-    HIP_TRY(d_rng.alloc((size_t)n * 8));
-    PipeStreams *ps = nullptr;
-    rc = pipe_streams(idx->device, &ps);
-    if (rc) return rc;
-    hipStream_t st = ps->s[1];
-    Scratch scratch(idx, st, true);
-    struct Result {  // (as in fmx_locate_all_batch)
-        hipStream_t s;
-        int32_t *p = nullptr;
-        ~Result() {
-            (void)hipStreamSynchronize(s);
-            free(p);
-        }
-    } result{st};
-    if (chars > first) HIP_TRY(hipMemcpyAsync(d_pat.as<uint16_t>() + first, pat + first, (chars - first) * 2, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_off.p, pat_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
-    int32_t *dst_ = status ? d_st.as<int32_t>() : nullptr;
-    rc = locate_all_ranges_impl(idx, d_pat.as<uint16_t>(), d_off.as<int32_t>(), n, -1, d_hit.as<int64_t>(), nullptr, dst_, d_rng.as<int32_t>(),
-                                scratch, d_cnt.as<int32_t>());
-    if (rc) return rc;
-    int64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_hit.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
-    int64_t n_out = 0;
-    if (total > 0 && q > 0) {
-        const size_t ws_bytes = fmx::query_lines_scratch_bytes(n, q, total);
-        if ((rc = alloc_for_hits(d_locs, (size_t)total * 4))) return rc;
-        if ((rc = alloc_for_hits(d_lines, (size_t)total * 4))) return rc;
-        if ((rc = alloc_for_hits(d_ws, ws_bytes))) return rc;
-        int e = k_launch_locate_all(idx, idx->dev, idx->n_cu, d_rng.as<int32_t>(), d_hit.as<int64_t>(), n, (int64_t)0, total,
-                                    d_locs.as<int32_t>(), nullptr, dst_, st);
-        if (e) return fail(FMX_E_HIP, std::string("k_locate_all launch: ") + hipGetErrorString((hipError_t)e));
-        e = fmx::launch_query_lines(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_cu, n, q, query_off, term_kind,
-                                    d_hit.as<int64_t>(), d_locs.as<int32_t>(), total, max_lines, d_loff.as<int64_t>(), d_lines.as<int32_t>(),
-                                    d_lcnt.as<int32_t>(), d_ws.p, d_ws.bytes, st);
-        if (e) return fail(FMX_E_HIP, std::string("lines of queries: ") + hipGetErrorString((hipError_t)e));
-        HIP_TRY(hipMemcpyAsync(&n_out, d_loff.as<int64_t>() + q, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    } else {
-        HIP_TRY(hipMemsetAsync(d_loff.p, 0, (size_t)(q + 1) * 8, st));
-        HIP_TRY(hipMemsetAsync(d_lcnt.p, 0, (size_t)q * 4 + 4, st));
+    if (n == 0) {
+        hit_off[0] = 0;
+        return FMX_OK;
     }
-    if (n_out > 0) {
-        result.p = static_cast<int32_t *>(malloc((size_t)n_out * 4));
-        if (!result.p) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(n_out) + " lines");
-        HIP_TRY(hipMemcpyAsync(result.p, d_lines.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+    PackedCall call(idx);
+    RangeStage r;
+    if ((rc = class_ranges(call, alt, pos_off, n_pos, pat_off, n, max_ranges, true, status != nullptr, r)) || (rc = hits_down(call, r, hit_off)))
+        return rc;
+    return packed_finish(call, r, nullptr, nullptr, status, locs);
+    });
+}
+
+// (a query set whose key does not fit is turned away once the ranges are there, a batch without hits included: where
+// fmx_query_lines_of_hits_dev would judge it for a caller of the device stages)
+int fmx_match_query_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                int32_t n, int32_t max_ranges, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t *line_count, int32_t *occurrences,
+                                int32_t *status) {
+    return guarded([&]() -> int {
+    if (lines) *lines = nullptr;
+    if (q < 0 || !line_off || !lines || !query_off || (n > 0 && !term_kind)) return fail(FMX_E_ARG, "bad arguments");
+    int rc;
+    if ((rc = class_args(idx, alt, pos_off, n_pos, pat_off, n, max_ranges)) || (rc = check_queries(n, q, query_off, term_kind)) ||
+        (rc = require_line_table(idx)))
+        return rc;
+    if (n == 0) {
+        no_terms_no_lines(q, line_off, line_count);
+        return FMX_OK;
     }
-    HIP_TRY(hipMemcpyAsync(line_off, d_loff.p, (size_t)(q + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (line_count && q > 0) HIP_TRY(hipMemcpyAsync(line_count, d_lcnt.p, (size_t)q * 4, hipMemcpyDeviceToHost, st));
-    if (occurrences) HIP_TRY(hipMemcpyAsync(occurrences, d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *lines = result.p;
-    result.p = nullptr;
-    return FMX_OK;
+    PackedCall call(idx);
+    RangeStage r;
+    if ((rc = class_ranges(call, alt, pos_off, n_pos, pat_off, n, max_ranges, true, status != nullptr, r)) ||
+        (rc = check_query_key_width(idx, q, query_off)) ||
+        (rc = lines_down(call, r, query_off, term_kind, q, max_lines, line_off, line_count)))
+        return rc;
+    return packed_finish(call, r, occurrences, nullptr, status, lines);
     });
 }
 
@@ -3344,52 +3428,44 @@ constexpr int64_t kExtractPackedMaxChars = (int64_t)1 << 35;  // 64 GiB of chara
 static thread_local int64_t g_extract_packed_redo = -1;
 int64_t fmx_extract_packed_last_redo(void) { return g_extract_packed_redo; }
 
-// d_start / d_stop: the ranges, on the device already (lines: made there from the ids)
-static int extract_packed_host(const fmx_index *idx, const int32_t *d_start, const int32_t *d_stop, int32_t n, hipStream_t st,
-                               int64_t *text_off, uint16_t **chars, int32_t *status) {
-    DevBuf d_toff, d_poff, d_st, d_ws, d_chars;
-    HIP_TRY(d_toff.alloc((size_t)(n + 1) * 8));
-    HIP_TRY(d_poff.alloc((size_t)(n + 1) * 8));
-    HIP_TRY(d_st.alloc((size_t)n * 4));
+// d_start / d_stop: the ranges, on the device already (lines: made there from the ids), in blocks of the call's
+static int extract_packed_host(PackedCall &call, const int32_t *d_start, const int32_t *d_stop, int32_t n, int64_t *text_off, uint16_t **chars,
+                               int32_t *status) {
+    const fmx_index *idx = call.blocks.idx;
+    Scratch &b = call.blocks;
+    const hipStream_t st = call.stream.s;
     const size_t ws_bytes = fmx::extract_packed_scratch_bytes(n);
+    int64_t *d_toff = nullptr, *d_poff = nullptr;
+    int32_t *d_st = nullptr;
+    uint16_t *d_chars = nullptr;
+    void *ws = nullptr;
     int rc;
-    if ((rc = alloc_for_hits(d_ws, ws_bytes))) return rc;
-    struct Result {  // (as in fmx_locate_all_batch)
-        hipStream_t s;
-        uint16_t *p = nullptr;
-        ~Result() {
-            (void)hipStreamSynchronize(s);
-            free(p);
-        }
-    } result{st};
-    int e = fmx::launch_extract_packed_offsets(idx->dev, d_start, d_stop, n, d_toff.as<int64_t>(), d_poff.as<int64_t>(), d_st.as<int32_t>(),
-                                               d_ws.p, d_ws.bytes, st);
+    if ((rc = b.block((size_t)(n + 1) * 8, &d_toff)) || (rc = b.block((size_t)(n + 1) * 8, &d_poff)) || (rc = b.block((size_t)n * 4, &d_st)) ||
+        (rc = b.block(ws_bytes, &ws)))
+        return rc;
+    int e = fmx::launch_extract_packed_offsets(idx->dev, d_start, d_stop, n, d_toff, d_poff, d_st, ws, ws_bytes, st);
     if (e) return fail(FMX_E_HIP, std::string("extract packed offsets: ") + hipGetErrorString((hipError_t)e));
     int64_t total = 0, pieces = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_toff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&pieces, d_poff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&total, d_toff + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&pieces, d_poff + n, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (total > kExtractPackedMaxChars)
         return fail(FMX_E_ARG, "the batch's ranges hold " + std::to_string(total) + " characters, more than one answer's " +
                                    std::to_string(kExtractPackedMaxChars));
     int32_t redo = 0;
     if (total > 0) {
-        if ((rc = alloc_for_hits(d_chars, (size_t)total * 2 + 8))) return rc;
-        result.p = static_cast<uint16_t *>(malloc((size_t)total * 2));
-        if (!result.p) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(total) + " characters");
-        rc = extract_packed_fill_impl(idx, d_start, d_stop, n, d_toff.as<int64_t>(), d_poff.as<int64_t>(), pieces, d_chars.as<uint16_t>(),
-                                      d_st.as<int32_t>(), d_ws.p, st);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(result.p, d_chars.p, (size_t)total * 2, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&redo, fmx::extract_packed_redo(d_ws.p), 4, hipMemcpyDeviceToHost, st));
+        if ((rc = b.block((size_t)total * 2 + 8, &d_chars))) return rc;
+        if (!call.result.alloc((size_t)total * 2)) return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(total) + " characters");
+        if ((rc = extract_packed_fill_impl(idx, d_start, d_stop, n, d_toff, d_poff, pieces, d_chars, d_st, ws, st))) return rc;
+        HIP_TRY(hipMemcpyAsync(call.result.p, d_chars, (size_t)total * 2, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&redo, fmx::extract_packed_redo(ws), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    HIP_TRY(hipMemcpyAsync(text_off, d_toff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(text_off, d_toff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_st, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     g_extract_packed_redo = redo;
-    *chars = result.p;
-    result.p = nullptr;
+    call.result.hand_over(chars);
     return FMX_OK;
 }
 
@@ -3406,17 +3482,12 @@ int fmx_extract_packed_batch(const fmx_index *idx, const int32_t *start, const i
         return FMX_OK;
     }
     HIP_TRY(hipSetDevice(idx->device));
-    PipeStreams *ps = nullptr;
-    rc = pipe_streams(idx->device, &ps);
-    if (rc) return rc;
-    hipStream_t st = ps->s[1];
-    DevBuf d_start, d_stop;
-    HIP_TRY(d_start.alloc((size_t)n * 4));
-    HIP_TRY(d_stop.alloc((size_t)n * 4));
-    StreamWait wait{st};
-    HIP_TRY(hipMemcpyAsync(d_start.p, start, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_stop.p, stop, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    return extract_packed_host(idx, d_start.as<int32_t>(), d_stop.as<int32_t>(), n, st, text_off, chars, status);
+    PackedCall call(idx);
+    int32_t *d_start = nullptr, *d_stop = nullptr;
+    if ((rc = call.open()) || (rc = call.blocks.block((size_t)n * 4, &d_start)) || (rc = call.blocks.block((size_t)n * 4, &d_stop))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_start, start, (size_t)n * 4, hipMemcpyHostToDevice, call.stream.s));
+    HIP_TRY(hipMemcpyAsync(d_stop, stop, (size_t)n * 4, hipMemcpyHostToDevice, call.stream.s));
+    return extract_packed_host(call, d_start, d_stop, n, text_off, chars, status);
     });
 }
 
@@ -3433,21 +3504,17 @@ int fmx_line_text_batch(const fmx_index *idx, const int32_t *lines, int32_t n, i
         return FMX_OK;
     }
     HIP_TRY(hipSetDevice(idx->device));
-    PipeStreams *ps = nullptr;
-    rc = pipe_streams(idx->device, &ps);
-    if (rc) return rc;
-    hipStream_t st = ps->s[1];
-    DevBuf d_in, d_start, d_stop;
-    HIP_TRY(d_in.alloc((size_t)n * 4));
-    HIP_TRY(d_start.alloc((size_t)n * 4));
-    HIP_TRY(d_stop.alloc((size_t)n * 4));
-    StreamWait wait{st};
-    HIP_TRY(hipMemcpyAsync(d_in.p, lines, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    PackedCall call(idx);
+    int32_t *d_in = nullptr, *d_start = nullptr, *d_stop = nullptr;
+    if ((rc = call.open()) || (rc = call.blocks.block((size_t)n * 4, &d_in)) || (rc = call.blocks.block((size_t)n * 4, &d_start)) ||
+        (rc = call.blocks.block((size_t)n * 4, &d_stop)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_in, lines, (size_t)n * 4, hipMemcpyHostToDevice, call.stream.s));
     // the ids become ranges where they are (an id that is no line: start = stop = -1, FMX_ST_POS_NEGATIVE below)
     int e = fmx::launch_line_bounds(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_lines, line_text_length(idx),
-                                    idx->n_cu, d_in.as<int32_t>(), n, d_start.as<int32_t>(), d_stop.as<int32_t>(), st);
+                                    idx->n_cu, d_in, n, d_start, d_stop, call.stream.s);
     if (e) return fail(FMX_E_HIP, std::string("k_line_bounds launch: ") + hipGetErrorString((hipError_t)e));
-    return extract_packed_host(idx, d_start.as<int32_t>(), d_stop.as<int32_t>(), n, st, text_off, chars, status);
+    return extract_packed_host(call, d_start, d_stop, n, text_off, chars, status);
     });
 }
 

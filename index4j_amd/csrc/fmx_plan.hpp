@@ -78,11 +78,6 @@ struct ClassView {
     bool compact;
 };
 int class_view(const ::fmx_index *idx, ClassView *view);
-// ... a block of the host forms' recycling cache (*bytes becomes its size class; returns a hipError_t as int, *p = nullptr on
-// failure), its way back, and the calling thread's kernel stream on a device (a hipStream_t; FMX_OK or an FMX_E_* code)
-int class_scratch_take(size_t *bytes, int *device, void **p);
-void class_scratch_give(int device, size_t bytes, void *p);
-int class_call_stream(int device, void **stream);
 
 // fmx_hit_lines.hip — the line table of a resident index and packed hits -> packed distinct lines (fmx_line_table_build,
 // fmx_line_bounds_*, fmx_lines_of_hits_dev).  Compiled once, like fmx_hit_offsets.hip.  The launchers return a hipError_t as int;

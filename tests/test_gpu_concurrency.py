@@ -62,6 +62,131 @@ def test_host_entry_points_from_many_threads_on_one_index():
     fm.close()
 
 
+class PackedBatch:
+    """a batch of words for the packed host forms and what the TEXT answers for it, literally and in any case: per word the
+    positions (str.find) and their distinct lines (bisect over the newlines), the words cut into queries of ALL / ANY / NONE
+    terms, and the lines of those queries by the set formula of fmx.h.  Made once, before the threads start; read-only."""
+    KINDS = ((0,), (1, 1), (0, 1, 2), (), (0, 2))  # ALL; ANY ANY; ALL ANY NONE; no terms; ALL NONE — over and over
+
+    def __init__(self, words, low, newlines):
+        self.words, self.n = words, len(words)
+        self.literal = ia.pack_patterns(words)
+        self.classes = ia.pack_class_patterns([ia.ignore_case(w) for w in words])
+        kinds, query_off = [], [0]
+        while len(kinds) < self.n:
+            kinds += self.KINDS[(len(query_off) - 1) % len(self.KINDS)]
+            query_off.append(min(len(kinds), self.n))
+        self.kinds, self.query_off = np.array(kinds[: self.n], np.uint8), np.array(query_off, np.int32)
+        self.exact = self.answers(HD, words, newlines)
+        self.any_case = self.answers(low, [w.lower() for w in words], newlines)
+
+    def answers(self, hay, words, newlines):
+        import bisect
+
+        pos = []
+        for w in words:
+            at, mine = hay.find(w), []
+            while at >= 0:
+                mine.append(at)
+                at = hay.find(w, at + 1)
+            pos.append(np.array(mine, np.int32))
+        lines = [sorted({bisect.bisect_left(newlines, p) for p in mine.tolist()}) for mine in pos]
+        per_query = []
+        for Q in range(len(self.query_off) - 1):
+            terms = range(self.query_off[Q], self.query_off[Q + 1])
+            alls, anys, nones = ([set(lines[t]) for t in terms if self.kinds[t] == k] for k in (0, 1, 2))
+            res = set()
+            if alls or anys:
+                res = set.intersection(*alls) if alls else set.union(*anys)
+                if alls and anys:
+                    res &= set.union(*anys)
+                res = res.difference(*nones)
+            per_query.append(sorted(res))
+        return dict(pos=pos, lines=lines, queries=per_query, occurrences=np.array([len(p) for p in pos], np.int32))
+
+    @staticmethod
+    def packed(lists):
+        off = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int64)
+        return np.array([v for x in lists for v in x], np.int32), off
+
+    def check(self, fm, text_lines, who):
+        zeros = np.zeros(self.n, np.int32)
+
+        def hits(got, want, what):
+            locs, hit_off, status = got
+            assert (status == zeros).all() and (np.diff(hit_off) == want["occurrences"]).all() and hit_off[0] == 0, (what, who)
+            for i, p in enumerate(want["pos"]):
+                assert (np.sort(locs[hit_off[i]:hit_off[i + 1]]) == p).all(), (what, who, self.words[i])
+
+        def lines_of(got, want_lists, want, what):
+            lines, line_off, status, line_count, occurrences = got
+            want_lines, want_off = self.packed(want_lists)
+            assert (line_off == want_off).all() and (lines == want_lines).all(), (what, who)
+            assert (line_count == np.diff(want_off)).all() and (occurrences == want["occurrences"]).all() and (status == zeros).all(), (what, who)
+            return lines
+
+        hits(fm.locate_all_batch(*self.literal), self.exact, "locate_all")
+        lines = lines_of(fm.match_lines_batch(*self.literal, want_counts=True), self.exact["lines"], self.exact, "match_lines")
+        lines_of(fm.match_query_batch(*self.literal, self.query_off, self.kinds, want_counts=True), self.exact["queries"], self.exact, "match_query")
+        hits(fm.locate_all_class_batch(*self.classes), self.any_case, "locate_all, any case")
+        lines_of(fm.match_query_class_batch(*self.classes, self.query_off, self.kinds, want_counts=True), self.any_case["queries"], self.any_case,
+                 "match_query, any case")
+        lines = lines[:300]
+        chars, text_off, status = fm.line_text_batch(lines)
+        want = [text_lines[k] for k in lines.tolist()]
+        assert ia.chars_to_str(chars) == "".join(want) and (np.diff(text_off) == [len(s) for s in want]).all() and (status == 0).all(), ("line_text", who)
+
+
+def test_packed_host_forms_from_many_threads_on_one_index():
+    """fmx_locate_all_batch, fmx_match_lines_batch, fmx_match_query_batch, fmx_locate_all_class_batch, fmx_match_query_class_batch
+    and fmx_line_text_batch from four threads on one index at once, three rounds each: every call takes blocks of the recycling
+    cache that return only after its stream has been waited for — a block handed on too early shows as another thread's answer.
+    Each thread has a batch of its own size; judged against the text itself (PackedBatch)."""
+    newlines = [i for i, c in enumerate(HD) if c == "\n"]
+    text_lines = HD.split("\n")
+    low = "".join(c.lower() if len(c.lower()) == 1 else c for c in HD)
+    assert len(low) == len(HD)
+    rnd = random.Random(77)
+
+    def sample(k):  # k pieces of single lines, 3 .. 12 characters
+        out = []
+        while len(out) < k:
+            ln = rnd.choice(text_lines)
+            if len(ln) >= 12:
+                at = rnd.randrange(len(ln) - 12)
+                out.append(ln[at:at + rnd.randrange(3, 13)])
+        return out
+
+    special = [" ", "block", "zzqqzz"]  # a character with many hits; spellings with different counts; no hit at all
+    batches = [[PackedBatch(special + sample(n - len(special)), low, newlines)] for n in (24, 40, 72, 96)]
+    batches[0].append(PackedBatch(["zzqq%d" % i for i in range(7)], low, newlines))  # no hit in the whole batch: nothing is filled
+    first, miss = batches[0]
+    assert len(first.exact["pos"][0]) > 10_000 and len(first.exact["pos"][2]) == 0 == len(first.any_case["pos"][2])
+    assert len(first.exact["pos"][1]) == 1554 and len(first.any_case["pos"][1]) == 2662
+    assert miss.exact["occurrences"].sum() == 0 == miss.any_case["occurrences"].sum()
+    fm = ia.FmIndex(HD, 16, True, device=0)
+    assert fm.build_line_table("\n") == 2000
+    errors = []
+    barrier = threading.Barrier(len(batches))
+
+    def run(k):
+        try:
+            barrier.wait()
+            for _ in range(3):
+                for b in batches[k]:
+                    b.check(fm, text_lines, "thread %d" % k)
+        except BaseException as e:  # noqa: BLE001 - reported to the main thread
+            errors.append(e)
+
+    threads = [threading.Thread(target=run, args=(k,)) for k in range(len(batches))]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not errors, errors[0]
+    fm.close()
+
+
 def test_a_stale_plan_is_harmless():
     """fmx_count_plan_dev -> (another call plans on the same stream, or the plan scratch grows) ->
     fmx_count_ordered_dev with the old perm: correct counts of the NEW batch order semantics aside — results are

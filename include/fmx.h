@@ -279,6 +279,28 @@ int fmx_match_query_class_batch(const fmx_index *idx, const uint16_t *alt, const
                                 int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t *line_count, int32_t *occurrences,
                                 int32_t *status);
 
+/* THE LINES THAT HOLD A SEQUENCE OF TERMS IN ORDER (grep 'A.*B') — the host forms of the two packed stages (literal or class
+ * patterns, every hit, no limit) + fmx_sequence_lines_of_hits_dev (below: what a sequence is, the rule, the spans).  The batch
+ * holds n TERMS, packed as everywhere, cut into q SEQUENCES by query_off (q + 1 ints, the rule of fmx_match_query_batch); the
+ * terms of a sequence must occur on the line in the order they stand in the batch, without overlap.  The length of a term is
+ * pat_off[t + 1] - pat_off[t]: its characters (literal) or its positions (class).  Needs a line table (fmx_line_table_build).
+ * line_off = q + 1 int64 (out); *lines = line_off[q] ints owned by the library until fmx_free_buffer((uint8_t *)*lines) (NULL
+ * when no line matches, and on every failure): the line ids of sequence Q, ascending, each once — with a limit the smallest
+ * max_lines of them; line_count[Q] (nullable, q entries) = ALL lines of sequence Q whatever the limit; occurrences[t] and
+ * status[t] (nullable, n entries) per TERM as in fmx_match_query_batch (an empty term: status 9, no hits — its sequence has no
+ * lines).  spans (nullable): *spans = *lines + line_off[q], 2 * line_off[q] ints IN THE SAME ALLOCATION behind the lines (free
+ * *lines only; NULL when *lines is): {span_start, span_stop} of every stored line, in the order of *lines.
+ * A ONE-TERM sequence is fmx_match_lines_batch of that term LESS the hits that run over the line's end: the pattern "\n" (the
+ * boundary) has no lines here, and a pattern that holds the boundary matches nowhere.
+ * Errors as fmx_match_query_batch (no kinds, no key-width limit: the key term | position always fits). */
+int fmx_match_sequence_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const int32_t *query_off,
+                             int32_t q, int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t **spans, int32_t *line_count,
+                             int32_t *occurrences, int32_t *status);
+int fmx_match_sequence_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos,
+                                   const int32_t *pat_off, int32_t n, int32_t max_ranges, const int32_t *query_off, int32_t q,
+                                   int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t **spans, int32_t *line_count,
+                                   int32_t *occurrences, int32_t *status);
+
 /* THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY (extract, FM:564-608, batched) — the host form of
  * fmx_extract_packed_offsets_dev + fmx_extract_packed_fill_dev (below: the layout, the statuses, how the work is cut).
  * host buffers, synchronous: text_off = n + 1 int64 (out), text_off[0] = 0; *chars = text_off[n] UTF-16 code units owned by the
@@ -478,6 +500,36 @@ int fmx_query_lines_of_hits_dev(const fmx_index *idx, int32_t n, int32_t q, cons
                                 const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int32_t max_lines,
                                 int64_t *d_line_off, int32_t *d_lines, int32_t *d_line_count, void *d_ws, size_t ws_bytes,
                                 void *stream);
+/* A SEQUENCE OF TERMS IN ORDER over device pointers, after the two packed stages of the literal or the class search: (d_hit_off,
+ * d_locs) hold the hits of n TERMS; query_off (q + 1 ints, the rule above) cuts them into q SEQUENCES: sequence Q is the terms
+ * t_0 .. t_{k-1} = query_off[Q] .. query_off[Q + 1] - 1 IN THAT ORDER; term_len[t] >= 0 is the length of term t.  The hits of a
+ * term are exactly what the locate stage reports for it (the reference's answers, quirk rows included).  With [start, stop) the
+ * bounds of line L (fmx_line_bounds_batch), L belongs to sequence Q iff there are hits h_0 .. h_{k-1}, h_j a hit of t_j, with
+ *     start <= h_0,   h_j + len_j <= h_{j+1} for every j,   h_{k-1} + len_{k-1} <= stop:
+ * the occurrences lie inside the line, in order, without overlap — for literals the regular expression t_0.*t_1.* ... on a line.
+ * A sequence without terms has no lines; neither has one with a term without hits.  A ONE-TERM sequence is fmx_lines_of_hits_dev
+ * of that term LESS the hits that run over the line's end (the boundary pattern itself has no lines here).
+ * query_off and term_len are HOST arrays: validated, and copied into d_ws before the call returns.
+ * d_line_count (nullable, q entries), d_line_off (q + 1 int64), d_lines: as fmx_query_lines_of_hits_dev, per sequence.  d_spans
+ * (nullable, 2 ints per stored line, in the order of d_lines): span_start = the smallest hit of t_0 in the line, span_stop = the
+ * end of the chain that takes, term by term, the EARLIEST hit that still fits — what the non-greedy t_0.*?t_1.*? ... matches at
+ * its leftmost start: the leftmost start and, from there, the earliest end; NOT the tightest window of the line.
+ * That earliest-fit chain from the line's first t_0 hit is also the membership test, and it is exact: any other chain starts
+ * later, and every later bound only moves right.  The stages hand lanes to hits (a key term | position per hit, ONE device-wide
+ * radix sort — term t's positions then stand ascending in [hit_off[t], hit_off[t + 1]) —, a lane per sorted hit that chains where
+ * it opens a line of a first term, a scan, a compaction); integers only, no atomics: the result does not depend on scheduling.
+ * d_ws: at least fmx_sequence_lines_scratch_bytes(n, q, n_hits) bytes (36 per hit — two key arrays 8 each, positions, flags,
+ * their scan, lines and chain ends 4 each — plus the tables and rocPRIM's temporary storage; 0 for an empty call).  The grids are
+ * fmx_hit_lines_geometry's.  n_hits may exceed hit_off[n] (the slots behind are ignored).  q == 0 or n_hits == 0 (n == 0 among
+ * them): the q + 1 offsets are zeroed and nothing else is written.  FMX_E_ARG for null or negative arguments, a bad query_off, a
+ * negative term_len, a workspace that is too small (nothing is launched, nothing is written), an index without a line table
+ * (fmx_last_error names fmx_line_table_build), n_hits > 2^31 - 1, a SuffixArray / RrrVector / stand-alone wavelet handle;
+ * FMX_E_NO_DEVICE for a handle that is not resident. */
+size_t fmx_sequence_lines_scratch_bytes(int32_t n, int32_t q, int64_t n_hits);
+int fmx_sequence_lines_of_hits_dev(const fmx_index *idx, int32_t n, int32_t q, const int32_t *query_off, const int32_t *term_len,
+                                   const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int32_t max_lines,
+                                   int64_t *d_line_off, int32_t *d_lines, int32_t *d_line_count, int32_t *d_spans, void *d_ws,
+                                   size_t ws_bytes, void *stream);
 /* CLASS PATTERNS over device pointers (d_alt, d_pos_off, d_pat_off: the three packed arrays of fmx_count_class_batch, in device
  * memory and trusted as the literal device forms trust theirs); asynchronous on `stream`, nothing is allocated or synchronised.
  * THE SEARCH keeps, per pattern, a frontier of SA ranges: the last position gives {C[c], C[c + 1]} of each of its codes, every

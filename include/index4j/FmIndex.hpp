@@ -261,6 +261,50 @@ public:
         return matchQueryBatch({query}, maxLines).lines;
     }
 
+    // the lines that hold a SEQUENCE of terms in order, without overlap (fmx.h "THE LINES THAT HOLD A SEQUENCE OF TERMS IN ORDER":
+    // grep 'A.*B').  matchSequenceBatch: lines[offsets[Q] .. offsets[Q + 1]) are those of sequence Q, ascending; lineCount per
+    // sequence, occurrences per term; wantSpans: spans[2 * i], spans[2 * i + 1] = [start, stop) of the non-greedy match on lines[i]
+    // (the leftmost start and from there the earliest end).  A sequence without terms has no lines.
+    struct SequenceLines : Lines {
+        std::vector<int32_t> spans;
+    };
+    SequenceLines matchSequenceBatch(const std::vector<std::vector<std::u16string>> &sequences, int maxLines = 0, bool wantSpans = false) const {
+        std::vector<std::u16string> terms;
+        std::vector<int32_t> queryOff{0};
+        for (const std::vector<std::u16string> &sq : sequences) {
+            terms.insert(terms.end(), sq.begin(), sq.end());
+            queryOff.push_back((int32_t)terms.size());
+        }
+        std::vector<uint16_t> chars;
+        std::vector<int32_t> off;
+        pack(terms, chars, off);
+        const int32_t n = (int32_t)terms.size(), q = (int32_t)sequences.size();
+        SequenceLines out;
+        out.offsets.assign((size_t)q + 1, 0);
+        out.lineCount.assign(sequences.size(), 0);
+        out.occurrences.assign(terms.size(), 0);
+        std::vector<int32_t> status(terms.size());
+        int32_t *buf = nullptr, *spans = nullptr;
+        detail::check(fmx_match_sequence_batch(h_, chars.data(), off.data(), n, queryOff.data(), q, maxLines, out.offsets.data(), &buf,
+                                               wantSpans ? &spans : nullptr, out.lineCount.data(), out.occurrences.data(), status.data()),
+                      "fmx_match_sequence_batch");
+        try {  // (the spans lie in the lines' buffer, behind them)
+            if (buf) out.lines.assign(buf, buf + out.offsets[(size_t)q]);
+            if (spans) out.spans.assign(spans, spans + 2 * out.offsets[(size_t)q]);
+        } catch (...) {
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+            throw;
+        }
+        fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+        for (int s : status) detail::raise_for_status(s);
+        return out;
+    }
+    std::vector<int32_t> matchSequence(const std::vector<std::u16string> &terms, int maxLines = 0) const {
+        for (const std::u16string &t : terms)
+            if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        return matchSequenceBatch({terms}, maxLines).lines;
+    }
+
     // patterns of character classes (fmx.h "PATTERNS OF CHARACTER CLASSES"): a ClassPattern is its positions, a position the code
     // units it may hold; the answer is the union over the literal strings the pattern spells.  A pattern that keeps more than
     // maxRanges SA ranges throws std::runtime_error (FMX_ST_TOO_MANY_RANGES).  ignoreCase: per ASCII letter both cases.

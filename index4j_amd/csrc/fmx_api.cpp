@@ -1962,6 +1962,49 @@ static int lines_down(PackedCall &call, RangeStage &r, const int32_t *query_off,
     return FMX_OK;
 }
 
+static int32_t line_text_length(const fmx_index *idx);
+// the lines of the q SEQUENCES that query_off makes of the patterns (launch_sequence_lines), term t of the length term_len[t]; with
+// want_spans the result holds, behind the n_out lines, their 2 * n_out span ints
+static int sequence_down(PackedCall &call, RangeStage &r, const int32_t *query_off, const int32_t *term_len, int32_t q, int32_t max_lines,
+                         bool want_spans, int64_t *line_off, int32_t *line_count) {
+    const fmx_index *idx = call.blocks.idx;
+    Scratch &b = call.blocks;
+    const hipStream_t st = call.stream.s;
+    const int32_t n = r.n;
+    if (r.total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
+    int64_t *d_loff = nullptr, n_out = 0;
+    int32_t *d_lcnt = nullptr, *d_locs = nullptr, *d_lines = nullptr, *d_spans = nullptr;
+    int rc;
+    if ((rc = b.block((size_t)(q + 1) * 8, &d_loff)) || (rc = b.block((size_t)q * 4 + 4, &d_lcnt))) return rc;
+    if (r.total > 0 && q > 0) {
+        const size_t ws_bytes = fmx::sequence_lines_scratch_bytes(n, q, r.total);
+        void *ws = nullptr;
+        if ((rc = b.block((size_t)r.total * 4, &d_locs)) || (rc = b.block((size_t)r.total * 4, &d_lines)) ||
+            (want_spans && (rc = b.block((size_t)r.total * 8, &d_spans))) || (rc = b.block(ws_bytes, &ws)) ||
+            (rc = fill_hits(call, r, 0, r.total, d_locs)))
+            return rc;
+        const int e = fmx::launch_sequence_lines(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_lines,
+                                                 line_text_length(idx), idx->n_cu, n, q, query_off, term_len, r.hit_off, d_locs, r.total, max_lines,
+                                                 d_loff, d_lines, d_lcnt, d_spans, ws, ws_bytes, st);
+        if (e) return fail(FMX_E_HIP, std::string("lines of sequences: ") + hipGetErrorString((hipError_t)e));
+        HIP_TRY(hipMemcpyAsync(&n_out, d_loff + q, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        HIP_TRY(hipMemsetAsync(d_loff, 0, (size_t)(q + 1) * 8, st));
+        HIP_TRY(hipMemsetAsync(d_lcnt, 0, (size_t)q * 4 + 4, st));
+    }
+    if (n_out > 0) {
+        if (!call.result.alloc((size_t)n_out * (want_spans ? 12 : 4)))
+            return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(n_out) + " lines");
+        HIP_TRY(hipMemcpyAsync(call.result.p, d_lines, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+        if (want_spans)
+            HIP_TRY(hipMemcpyAsync(static_cast<int32_t *>(call.result.p) + n_out, d_spans, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(line_off, d_loff, (size_t)(q + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (line_count && q > 0) HIP_TRY(hipMemcpyAsync(line_count, d_lcnt, (size_t)q * 4, hipMemcpyDeviceToHost, st));
+    return FMX_OK;
+}
+
 // the per-pattern arrays the caller wants, the last wait, the result handed over (a form without one: result == NULL)
 static int packed_finish(PackedCall &call, RangeStage &r, int32_t *counts, int32_t *lf_steps, int32_t *status, int32_t **result) {
     const hipStream_t st = call.stream.s;
@@ -2123,12 +2166,17 @@ int fmx_lines_of_hits_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_
 
 // ---- a query of several terms: packed hits -> the lines of each query (fmx_query_lines.hip) -------------------------------------
 // the HOST arrays that describe the queries: query_off (q + 1) starts at 0, never decreases, ends at n; every kind is 0, 1 or 2
-static int check_queries(int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind) {
-    if (n < 0 || q < 0 || !query_off || (n > 0 && !term_kind)) return fail(FMX_E_ARG, "bad arguments");
+static int check_query_off(int32_t n, int32_t q, const int32_t *query_off) {
+    if (n < 0 || q < 0 || !query_off) return fail(FMX_E_ARG, "bad arguments");
     if (query_off[0] != 0) return fail(FMX_E_ARG, "query_off does not start at 0");
     for (int32_t i = 0; i < q; ++i)
         if (query_off[i + 1] < query_off[i]) return fail(FMX_E_ARG, "query_off decreases at query " + std::to_string(i));
     if (query_off[q] != n) return fail(FMX_E_ARG, "query_off does not end at the number of terms");
+    return FMX_OK;
+}
+static int check_queries(int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind) {
+    if (n < 0 || q < 0 || !query_off || (n > 0 && !term_kind)) return fail(FMX_E_ARG, "bad arguments");
+    if (const int rc = check_query_off(n, q, query_off)) return rc;
     for (int32_t t = 0; t < n; ++t)
         if (term_kind[t] > 2) return fail(FMX_E_ARG, "term " + std::to_string(t) + " has a kind above 2");
     return FMX_OK;
@@ -2164,6 +2212,43 @@ int fmx_query_lines_of_hits_dev(const fmx_index *idx, int32_t n, int32_t q, cons
     int e = fmx::launch_query_lines(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_cu, n, q, query_off, term_kind,
                                     d_hit_off, d_locs, n_hits, max_lines, d_line_off, d_lines, d_line_count, d_ws, ws_bytes, stream);
     if (e) return fail(FMX_E_HIP, std::string("lines of queries: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+    });
+}
+
+// ---- a sequence of terms in order: packed hits -> the lines of each sequence (fmx_sequence_lines.hip) ---------------------------
+static int check_term_len(int32_t n, const int32_t *term_len) {
+    for (int32_t t = 0; t < n; ++t)
+        if (term_len[t] < 0) return fail(FMX_E_ARG, "term " + std::to_string(t) + " has a negative length");
+    return FMX_OK;
+}
+
+size_t fmx_sequence_lines_scratch_bytes(int32_t n, int32_t q, int64_t n_hits) { return fmx::sequence_lines_scratch_bytes(n, q, n_hits); }
+
+int fmx_sequence_lines_of_hits_dev(const fmx_index *idx, int32_t n, int32_t q, const int32_t *query_off, const int32_t *term_len,
+                                   const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int32_t max_lines, int64_t *d_line_off,
+                                   int32_t *d_lines, int32_t *d_line_count, int32_t *d_spans, void *d_ws, size_t ws_bytes, void *stream) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || q < 0 || n_hits < 0 || !d_line_off || !query_off || (n > 0 && (!d_hit_off || !term_len)) ||
+        (n > 0 && q > 0 && n_hits > 0 && (!d_locs || !d_lines)))
+        return fail(FMX_E_ARG, "bad arguments");
+    if (n_hits > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one call");
+    int rc = check_query_off(n, q, query_off);
+    if (rc) return rc;
+    if ((rc = check_term_len(n, term_len))) return rc;
+    if ((rc = require_fm_device(idx))) return rc;
+    if ((rc = require_line_table(idx))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (q == 0 || n == 0 || n_hits == 0) {
+        HIP_TRY(hipMemsetAsync(d_line_off, 0, ((size_t)q + 1) * sizeof(int64_t), st));
+        return FMX_OK;
+    }
+    if (!d_ws || ws_bytes < fmx::sequence_lines_scratch_bytes(n, q, n_hits))
+        return fail(FMX_E_ARG, "the workspace is smaller than fmx_sequence_lines_scratch_bytes");
+    int e = fmx::launch_sequence_lines(static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_lines, line_text_length(idx),
+                                       idx->n_cu, n, q, query_off, term_len, d_hit_off, d_locs, n_hits, max_lines, d_line_off, d_lines,
+                                       d_line_count, d_spans, d_ws, ws_bytes, stream);
+    if (e) return fail(FMX_E_HIP, std::string("lines of sequences: ") + hipGetErrorString((hipError_t)e));
     return FMX_OK;
     });
 }
@@ -3366,6 +3451,71 @@ int fmx_match_query_class_batch(const fmx_index *idx, const uint16_t *alt, const
         (rc = lines_down(call, r, query_off, term_kind, q, max_lines, line_off, line_count)))
         return rc;
     return packed_finish(call, r, occurrences, nullptr, status, lines);
+    });
+}
+
+// the lines that hold the terms of a sequence in order: the length of term t is its characters (literal) or positions (class),
+// pat_off[t + 1] - pat_off[t] either way.  *spans (nullable) points INTO *lines' allocation, behind the lines.
+static void sequence_hand_over(int32_t q, const int64_t *line_off, int32_t **lines, int32_t **spans) {
+    if (spans) *spans = *lines ? *lines + line_off[q] : nullptr;
+}
+static std::vector<int32_t> lengths_of(const int32_t *pat_off, int32_t n) {
+    std::vector<int32_t> len((size_t)n);
+    for (int32_t t = 0; t < n; ++t) len[(size_t)t] = pat_off[t + 1] - pat_off[t];
+    return len;
+}
+
+int fmx_match_sequence_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const int32_t *query_off, int32_t q,
+                             int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t **spans, int32_t *line_count, int32_t *occurrences,
+                             int32_t *status) {
+    return guarded([&]() -> int {
+    if (lines) *lines = nullptr;
+    if (spans) *spans = nullptr;
+    if (!idx || n < 0 || q < 0 || !line_off || !lines || !query_off || (n > 0 && !pat_off)) return fail(FMX_E_ARG, "bad arguments");
+    int rc = check_query_off(n, q, query_off);
+    if (rc) return rc;
+    if ((rc = require_fm_device(idx))) return rc;
+    if ((rc = require_line_table(idx))) return rc;
+    if (n == 0) {
+        no_terms_no_lines(q, line_off, line_count);
+        return FMX_OK;
+    }
+    PackedCall call(idx);
+    RangeStage r;
+    if ((rc = literal_ranges(call, pat, pat_off, n, -1, true, false, status != nullptr, r))) return rc;
+    const std::vector<int32_t> len = lengths_of(pat_off, n);  // (pat_off has been judged)
+    if ((rc = sequence_down(call, r, query_off, len.data(), q, max_lines, spans != nullptr, line_off, line_count)) ||
+        (rc = packed_finish(call, r, occurrences, nullptr, status, lines)))
+        return rc;
+    sequence_hand_over(q, line_off, lines, spans);
+    return FMX_OK;
+    });
+}
+
+int fmx_match_sequence_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                   int32_t n, int32_t max_ranges, const int32_t *query_off, int32_t q, int32_t max_lines, int64_t *line_off,
+                                   int32_t **lines, int32_t **spans, int32_t *line_count, int32_t *occurrences, int32_t *status) {
+    return guarded([&]() -> int {
+    if (lines) *lines = nullptr;
+    if (spans) *spans = nullptr;
+    if (q < 0 || !line_off || !lines || !query_off) return fail(FMX_E_ARG, "bad arguments");
+    int rc;
+    if ((rc = check_query_off(n, q, query_off)) || (rc = class_args(idx, alt, pos_off, n_pos, pat_off, n, max_ranges)) ||
+        (rc = require_line_table(idx)))
+        return rc;
+    if (n == 0) {
+        no_terms_no_lines(q, line_off, line_count);
+        return FMX_OK;
+    }
+    PackedCall call(idx);
+    RangeStage r;
+    const std::vector<int32_t> len = lengths_of(pat_off, n);
+    if ((rc = class_ranges(call, alt, pos_off, n_pos, pat_off, n, max_ranges, true, status != nullptr, r)) ||
+        (rc = sequence_down(call, r, query_off, len.data(), q, max_lines, spans != nullptr, line_off, line_count)) ||
+        (rc = packed_finish(call, r, occurrences, nullptr, status, lines)))
+        return rc;
+    sequence_hand_over(q, line_off, lines, spans);
+    return FMX_OK;
     });
 }
 

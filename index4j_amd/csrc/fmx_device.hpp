@@ -2291,6 +2291,75 @@ FMX_HD int64_t fm_query_first_group(const uint64_t *group_key, int64_t n_groups,
     return lo;
 }
 
+// A SEQUENCE OF TERMS IN ORDER (fmx_sequence_lines_of_hits_dev; fmx_sequence_lines.hip): the n patterns of a batch are TERMS, cut
+// into q SEQUENCES by query_off; sequence Q is the terms t_0 .. t_{k-1} = query_off[Q] .. query_off[Q + 1] - 1 in that order, term t
+// has the length term_len[t].  Line L = [start, stop) (fm_line_bounds) belongs to Q iff there are hits h_0 .. h_{k-1}, h_j one of
+// t_j, with start <= h_0, h_j + len_j <= h_{j+1} and h_{k-1} + len_{k-1} <= stop: inside the line, in order, without overlap — for
+// literals the regular expression t_0.*t_1.* ... on a line.  THE RULE the kernel runs: from the line's smallest hit of t_0 take,
+// term by term, the earliest hit that still fits.  It is exact: any other chain starts later, and every later bound only moves
+// right.  The end of that chain is the span's stop (what the non-greedy t_0.*?t_1.*? ... matches at its leftmost start).
+//
+// The sort key of one packed hit: term | position, the term most significant, so that ONE device-wide sort leaves the positions
+// of term t ascending in [hit_off[t], hit_off[t + 1]) — the offsets of the packed layout itself.  The position is ordered as a
+// SIGNED int32 (a quirk row may report any int32): it is biased by 2^31.  term in [0, n], n marks a slot behind hit_off[n]: last.
+FMX_HHD int32_t fm_seq_key_width(int32_t n) { return fm_bits((uint32_t)n) + 32; }
+FMX_HD uint64_t fm_seq_key(int32_t term, int32_t loc) { return ((uint64_t)(uint32_t)term << 32) | ((uint32_t)loc ^ 0x80000000u); }
+FMX_HD int32_t fm_seq_key_term(uint64_t key) { return (int32_t)(key >> 32); }
+FMX_HD int32_t fm_seq_key_loc(uint64_t key) { return (int32_t)((uint32_t)key ^ 0x80000000u); }
+// the first index in [lo, hi) with pos[i] >= at (hi: none), pos ascending there
+FMX_HD int64_t fm_seq_lower_bound(const int32_t *pos, int64_t lo, int64_t hi, int64_t at) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (pos[mid] < at)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+// sorted hit i of a FIRST term, whose segment of pos begins at `first` (= hit_off[t]): its line and the line's start; true iff it
+// is the line's first hit of the term — i is `first`, or the hit in front of it lies before the line.  Equal positions do not open
+// twice.  One fm_line_of, one read of T.
+FMX_HD bool fm_seq_head(const int32_t *pos, int64_t i, int64_t first, const int32_t *T, int32_t count, const int32_t *fences, int32_t n_fences,
+                        int32_t shift, int32_t &line, int32_t &start) {
+    line = fm_line_of(T, count, fences, n_fences, shift, pos[i]);
+    start = line == 0 ? 0 : T[line - 1] + 1;
+    return i <= first || pos[i - 1] < start;
+}
+// the earliest-fit walk of the sequence whose terms are [t_first, t_stop), from the hit h0 of t_first in a line that ends at
+// `stop`: per further term ONE lower bound inside that term's own segment [hit_off[t], hit_off[t + 1]) of pos (both cut at
+// `total`, the number of sorted hits).  Returns the end of the chain, or -1 as soon as a term has no hit at or behind the bound or
+// a hit's end passes `stop`.
+FMX_HD int64_t fm_seq_chain(const int32_t *pos, const int64_t *hit_off, int64_t total, const int32_t *term_len, int32_t t_first, int32_t t_stop,
+                            int32_t h0, int32_t stop) {
+    int64_t at = (int64_t)h0 + term_len[t_first];
+    if (at > stop) return -1;
+    for (int32_t t = t_first + 1; t < t_stop; ++t) {
+        const int64_t lo = hit_off[t] < total ? hit_off[t] : total, hi = hit_off[t + 1] < total ? hit_off[t + 1] : total;
+        const int64_t j = fm_seq_lower_bound(pos, lo, hi, at);
+        if (j >= hi) return -1;
+        at = (int64_t)pos[j] + term_len[t];
+        if (at > stop) return -1;
+    }
+    return at;
+}
+// one sorted hit i of term t (the key's): 1 with its line and the chain's end iff t is its sequence's first term, the hit opens
+// its line, the line is one of the text's n_lines, and the chain fits; else 0.
+FMX_HD int32_t fm_seq_flag(const int32_t *pos, int64_t i, int32_t t, const int64_t *hit_off, int64_t total, const int32_t *term_seq,
+                           const int32_t *query_off, const int32_t *term_len, const int32_t *T, int32_t count, int64_t n_lines, int32_t text_len,
+                           const int32_t *fences, int32_t n_fences, int32_t shift, int32_t &line, int32_t &end) {
+    const int32_t seq = term_seq[t];
+    if (t != query_off[seq]) return 0;
+    int32_t start;
+    if (!fm_seq_head(pos, i, hit_off[t], T, count, fences, n_fences, shift, line, start)) return 0;
+    const int32_t h0 = pos[i];
+    if (line >= n_lines || h0 < start) return 0;
+    const int64_t e = fm_seq_chain(pos, hit_off, total, term_len, t, query_off[seq + 1], h0, line < count ? T[line] : text_len);
+    if (e < 0) return 0;
+    end = (int32_t)e;
+    return 1;
+}
+
 // up to four characters of one aligned 8-byte group of a destination row (mask: which of them): one store when all four are there
 FMX_HD void fm_flush_chars(uint16_t *group_at, uint64_t group, uint32_t mask) {
     if (mask == 0xfu) {

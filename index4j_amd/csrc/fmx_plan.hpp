@@ -108,4 +108,15 @@ int launch_query_lines(const int32_t *T, int32_t count, int n_cu, int32_t n, int
                        const int64_t *hit_off, const int32_t *locs, int64_t n_hits, int32_t max_lines, int64_t *line_off, int32_t *lines,
                        int32_t *line_count, void *ws, size_t ws_bytes, void *stream);
 
+// fmx_sequence_lines.hip — packed hits of a batch of terms -> the packed lines of each SEQUENCE of terms in order
+// (fmx_sequence_lines_of_hits_dev).  Compiled once.  query_off (q + 1) and term_len (n, none negative) are HOST arrays the caller
+// has validated; the tables made from them are copied into the workspace before the launcher returns.  n_lines, text_len: the
+// line bounds' (fm_line_bounds).  spans (nullable): two ints per stored line.  The grids are hit_lines_geometry's.
+// hipErrorInvalidValue before anything is launched or written: too small a workspace, n_hits beyond 2^31 - 1.
+size_t sequence_lines_scratch_bytes(int32_t n, int32_t q, int64_t n_hits);
+int launch_sequence_lines(const int32_t *T, int32_t count, int64_t n_lines, int32_t text_len, int n_cu, int32_t n, int32_t q,
+                          const int32_t *query_off, const int32_t *term_len, const int64_t *hit_off, const int32_t *locs, int64_t n_hits,
+                          int32_t max_lines, int64_t *line_off, int32_t *lines, int32_t *line_count, int32_t *spans, void *ws, size_t ws_bytes,
+                          void *stream);
+
 }  // namespace fmx

@@ -472,6 +472,52 @@ class FmIndex:
             lib.fmx_free_buffer(buf)
         return (lines, line_off, status, line_count, occurrences) if want_counts else (lines, line_off, status)
 
+    # ---- the lines that hold a sequence of terms in order (fmx.h "THE LINES THAT HOLD A SEQUENCE OF TERMS IN ORDER") ----
+    def _sequence_call(self, call, where, args, n, query_off, max_lines, want_counts, want_spans):
+        query_off = np.ascontiguousarray(query_off, dtype=np.int32)
+        q = len(query_off) - 1
+        line_off = np.zeros(q + 1, dtype=np.int64)
+        line_count = np.zeros(q, dtype=np.int32)
+        occurrences = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        buf, spans_at = C.c_void_p(), C.c_void_p()
+        check(call(self._h, *args, query_off.ctypes.data, q, int(max_lines), line_off.ctypes.data, C.byref(buf),
+                   C.byref(spans_at) if want_spans else None, line_count.ctypes.data, occurrences.ctypes.data, status.ctypes.data), where)
+        total = int(line_off[q])
+        try:  # the library's buffer (the lines, the spans behind them) is copied into arrays of NumPy's own and handed back
+            both = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_int32)), shape=(total * (3 if want_spans else 1),)).copy() if total \
+                else np.zeros(0, np.int32)
+        finally:
+            lib.fmx_free_buffer(buf)
+        out = (both[:total], line_off, status)
+        if want_counts:
+            out += (line_count, occurrences)
+        if want_spans:
+            out += (both[total:].reshape(total, 2),)
+        return out
+
+    def match_sequence_batch(self, chars, offsets, query_off, max_lines=0, want_counts=False, want_spans=False):
+        """the lines of every SEQUENCE of terms, packed and ascending (fmx_match_sequence_batch; grep 'A.*B'): the patterns (chars,
+        offsets) are terms, query_off (q + 1 entries, from 0 to the number of terms) cuts them into sequences; a line belongs to
+        a sequence iff it holds occurrences of its terms in the order they stand in, inside the line, without overlap.  Those of
+        sequence Q are lines[line_off[Q]:line_off[Q + 1]], at most max_lines of them for max_lines > 0.  Returns (lines, line_off,
+        status[, line_count, occurrences][, spans]): status and occurrences per TERM, line_count per sequence (all its lines
+        whatever the limit), spans[i] = (start, stop) for lines[i]: the leftmost start and from there the earliest end (what the
+        non-greedy A.*?B matches), not the tightest window."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        return self._sequence_call(lib.fmx_match_sequence_batch, "fmx_match_sequence_batch", (chars.ctypes.data, offsets.ctypes.data, len(offsets) - 1),
+                                   len(offsets) - 1, query_off, max_lines, want_counts, want_spans)
+
+    def match_sequence_class_batch(self, alt, pos_off, pat_off, query_off, max_lines=0, want_counts=False, want_spans=False,
+                                   max_ranges=CLASS_RANGES_DEFAULT):
+        """match_sequence_batch with class patterns as terms (fmx_match_sequence_class_batch; a term's length is its number of
+        positions); same returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        return self._sequence_call(lib.fmx_match_sequence_class_batch, "fmx_match_sequence_class_batch",
+                                   (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, int(max_ranges)), n, query_off, max_lines,
+                                   want_counts, want_spans)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -650,6 +696,22 @@ class FmIndex:
             raise_for_status(st)
         return lines
 
+    def match_sequence(self, terms, max_lines=0, ignore_case=False, want_spans=False):
+        """the ids of the lines that hold the terms in this order, without overlap (grep 'A.*B.*C'), each once, ascending; at most
+        max_lines of them for max_lines > 0.  No terms: no lines.  want_spans: (lines, spans), spans[i] = (start, stop) of the
+        non-greedy match on lines[i].  ignore_case: every term in any case (class patterns: match_sequence_class_batch)."""
+        terms = [as_chars(p) for p in ([terms] if isinstance(terms, str) else terms)]
+        if min((len(t) for t in terms), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        if ignore_case:
+            out = self.match_sequence_class_batch(*pack_class_patterns([_ignore_case(t) for t in terms]), [0, len(terms)], max_lines,
+                                                  want_spans=want_spans)
+        else:
+            out = self.match_sequence_batch(*pack_patterns(terms), [0, len(terms)], max_lines, want_spans=want_spans)
+        for st in out[2]:
+            raise_for_status(st)
+        return (out[0], out[3]) if want_spans else out[0]
+
     def line_text(self, lines):
         """the lines with these ids as a list of str (the boundary excluded); raises for an id that is no line"""
         chars, text_off, status = self.line_text_batch(lines)
@@ -657,10 +719,15 @@ class FmIndex:
             raise_for_status(st)
         return [chars[a:b].tobytes().decode("utf-16-le", "surrogatepass") for a, b in zip(text_off[:-1], text_off[1:])]
 
-    def grep(self, pattern=None, all=(), any=(), none=(), max_lines=0, ignore_case=False):  # noqa: A002 (the words of the query)
+    def grep(self, pattern=None, all=(), any=(), none=(), max_lines=0, ignore_case=False, sequence=None):  # noqa: A002 (the words of the query)
         """[(line id, line)] of the lines that hold `pattern` — or, without one, that match the query of all / any / none
-        (match_query) — ascending, at most max_lines of them for max_lines > 0: match_lines / match_query, then line_text_batch"""
-        if pattern is not None:
+        (match_query), or that hold the terms of `sequence` in order (match_sequence; not together with the others: ValueError)
+        — ascending, at most max_lines of them for max_lines > 0: match_lines / match_query / match_sequence, then line_text_batch"""
+        if sequence is not None:
+            if pattern is not None or all or any or none:
+                raise ValueError("a sequence, or a pattern, or a query: one of them")
+            ids = self.match_sequence(sequence, max_lines, ignore_case=ignore_case)
+        elif pattern is not None:
             if all or any or none:
                 raise ValueError("a pattern or a query, not both")
             ids = self.match_lines(pattern, max_lines, ignore_case=ignore_case)

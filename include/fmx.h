@@ -301,6 +301,33 @@ int fmx_match_sequence_class_batch(const fmx_index *idx, const uint16_t *alt, co
                                    int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t **spans, int32_t *line_count,
                                    int32_t *occurrences, int32_t *status);
 
+/* THE VALUES THAT FOLLOW A PATTERN, WITH COUNTS (grep -o 'blk_[^ ]*' | sort | uniq -c; a terms aggregation) — the host forms of the
+ * two packed stages (literal or class patterns, every hit, no limit) + fmx_values_of_hits_dev / fmx_values_fill_dev (below: the
+ * definition of a value, the order, the stages).  One stop set (n_stop UTF-16 code units, 0 .. 64, duplicates allowed) and one
+ * max_len in [1, 64] for the batch.  The length of a pattern is pat_off[i + 1] - pat_off[i]: its characters (literal) or its
+ * positions (class).  No line table is needed.
+ * val_off = n + 1 int64 (out), val_off[0] = 0: the values of pattern i are val_off[i] .. val_off[i + 1] - 1, ascending by UTF-16
+ * code unit, a value in front of its extensions; G = val_off[n].  The result is ONE allocation owned by the library until
+ * fmx_free_buffer((uint8_t *)*counts): *counts = G ints, the hits that have each value (the counts of a pattern add up to its
+ * hits); *text_off = G + 1 int64 and *chars = (*text_off)[G] code units point INTO that allocation (free *counts only): value g is
+ * (*chars)[(*text_off)[g] .. (*text_off)[g + 1]).  All three are NULL when there are no values, and on every failure.
+ * occurrences[i] and status[i] (nullable, n entries) per pattern as in fmx_match_lines_batch: an empty pattern keeps
+ * FMX_ST_JAVA_AIOOBE and has no values; on an index built without extraction every pattern gets FMX_ST_NOT_ENABLED and no values
+ * (occurrences is still filled); a class pattern with FMX_ST_TOO_MANY_RANGES has none either.  Values are never merged across
+ * patterns.  Only the groups come down: the hits and their windows stay on the device.  Device scratch grows with the HITS, no
+ * windows over the answer in this version: 4 bytes per hit for the positions, 12 for the groups' counts and offsets, and
+ * fmx_values_of_hits_scratch_bytes (about 170 + 2 * max_len per hit).  FMX_E_NOMEM when the scratch or the result cannot be
+ * allocated (nothing is left behind); FMX_E_ARG for null or negative arguments, max_len or n_stop outside their intervals, more
+ * than 2^31 - 1 hits or hits * max_len above 2^35, and a SuffixArray, RrrVector or stand-alone wavelet handle; FMX_E_NO_DEVICE for
+ * a handle that is not resident.  n == 0: FMX_OK, val_off[0] = 0. */
+int fmx_field_values_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *stop,
+                           int32_t n_stop, int32_t max_len, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
+                           int32_t *occurrences, int32_t *status);
+int fmx_field_values_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos,
+                                 const int32_t *pat_off, int32_t n, int32_t max_ranges, const uint16_t *stop, int32_t n_stop,
+                                 int32_t max_len, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
+                                 int32_t *occurrences, int32_t *status);
+
 /* THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY (extract, FM:564-608, batched) — the host form of
  * fmx_extract_packed_offsets_dev + fmx_extract_packed_fill_dev (below: the layout, the statuses, how the work is cut).
  * host buffers, synchronous: text_off = n + 1 int64 (out), text_off[0] = 0; *chars = text_off[n] UTF-16 code units owned by the
@@ -315,8 +342,9 @@ int fmx_extract_packed_batch(const fmx_index *idx, const int32_t *start, const i
 /* ... of LINES: the ids go through the resident line table on the device (fmx_line_table_build; fmx_line_bounds_batch's rule)
  * and nothing in between comes down.  An id that is no line gets FMX_ST_POS_NEGATIVE and length 0.  FMX_E_ARG without a table. */
 int fmx_line_text_batch(const fmx_index *idx, const int32_t *lines, int32_t n, int64_t *text_off, uint16_t **chars, int32_t *status);
-/* how many ranges the calling thread's last fmx_extract_packed_batch / fmx_line_text_batch ran literally (the redo list below);
- * -1 before the first such call.  0 on an index without quirk rows. */
+/* how many ranges the calling thread's last fmx_extract_packed_batch / fmx_line_text_batch — or windows its last
+ * fmx_field_values_batch / fmx_field_values_class_batch — ran literally (the redo list below); -1 before the first such call.  0 on
+ * an index without quirk rows. */
 int64_t fmx_extract_packed_last_redo(void);
 
 /* int extract(int start, int stop, char[] destination, int offset) FM:564-608.  dst is n rows of
@@ -530,6 +558,41 @@ int fmx_sequence_lines_of_hits_dev(const fmx_index *idx, int32_t n, int32_t q, c
                                    const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int32_t max_lines,
                                    int64_t *d_line_off, int32_t *d_lines, int32_t *d_line_count, int32_t *d_spans, void *d_ws,
                                    size_t ws_bytes, void *stream);
+/* THE VALUES THAT FOLLOW A PATTERN over device pointers, after the two packed stages of the literal or the class search:
+ * (d_hit_off, d_locs) hold the hits of n patterns, exactly what the locate stage reports (quirk rows included); term_len[i] >= 0
+ * is the length of pattern i.  With textLength = getInputLength() - 1, a hit h of pattern i has
+ *     s = min(max(h + term_len[i], 0), textLength),   e = min(s + max_len, textLength),
+ *     window = what extract(s, e, destination, 0) stores (fmx_extract_packed_*'s answer, its quirks included),
+ *     value  = the window up to, not including, its first code unit that is in the stop set; the whole window if there is none.
+ * The empty string is a value (the pattern followed at once by a stop unit, or by the end of the text).  The answer of pattern i
+ * is its distinct values, ascending by UTF-16 code unit, a value in front of its extensions ("1" < "10" < "2"), each with the
+ * number of hits that have it.  term_len and stop are HOST arrays: validated, and copied into d_ws before the call returns.
+ * stage 1, fmx_values_of_hits_dev: d_val_off (n + 1 int64) = where the groups of each pattern begin, d_val_off[n] = G; d_count
+ * (room for n_hits ints) = the hits of group g; d_text_off (room for n_hits + 1 int64) = where its code units begin, d_text_off[G]
+ * = all of them; d_status (nullable, n ints, read-modify-write: the locate stage's): a window the packed extract ran literally
+ * (its redo list) hands the status of that run to its pattern (windows of one pattern with different such statuses: one of them).  Entries behind d_val_off[n], d_count[G - 1] and d_text_off[G] keep
+ * the caller's values.  The caller reads G and d_text_off[G] between the stages and gives d_chars that many code units.
+ * stage 2, fmx_values_fill_dev: the code units of the G groups into d_chars, from the same d_ws, untouched in between.
+ * The stages hand lanes to hits, runs or groups: the windows (a lane per hit), the packed extract over them (lanes per piece),
+ * the values' lengths (the stop set in LDS), RUNS of neighbouring hits with one value — the hits of a pattern stand in SA-row
+ * order, that is ordered by the text behind the pattern —, then the exact grouping of the runs by stable radix-sort passes over
+ * (length; chunks of four code units, last to first, padded with 0; pattern), heads, scans.  Integers only, no atomics, no
+ * hashes: the result does not depend on scheduling.  On an index built without extraction: no values, every d_status entry
+ * FMX_ST_NOT_ENABLED.
+ * d_ws: at least fmx_values_of_hits_scratch_bytes(n, n_hits, max_len) bytes (about 170 + 2 * max_len per hit: the windows' ranges,
+ * offsets and text, the packed extract's own workspace, lengths, runs, two permutations and two key arrays, the heads' scans —
+ * plus rocPRIM's temporary storage; 0 for an empty call or a shape the call refuses).  The grids are fmx_hit_lines_geometry's; the
+ * extract's honour the options "block" and "groups_per_cu".  n_hits may exceed d_hit_off[n] (the slots behind are ignored).
+ * n == 0 or n_hits == 0: the n + 1 offsets and d_text_off[0] are zeroed and nothing else is written.  FMX_E_ARG for null or negative
+ * arguments, max_len outside [1, 64], n_stop outside [0, 64], a negative term_len, n_hits > 2^31 - 1, n_hits * max_len > 2^35, a
+ * workspace that is too small (nothing is launched, nothing is written), a SuffixArray / RrrVector / stand-alone wavelet handle;
+ * FMX_E_NO_DEVICE for a handle that is not resident. */
+size_t fmx_values_of_hits_scratch_bytes(int32_t n, int64_t n_hits, int32_t max_len);
+int fmx_values_of_hits_dev(const fmx_index *idx, int32_t n, const int32_t *term_len, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                           const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int64_t *d_val_off, int32_t *d_count,
+                           int64_t *d_text_off, int32_t *d_status, void *d_ws, size_t ws_bytes, void *stream);
+int fmx_values_fill_dev(const fmx_index *idx, int64_t n_groups, const int64_t *d_text_off, uint16_t *d_chars, const void *d_ws,
+                        size_t ws_bytes, void *stream);
 /* CLASS PATTERNS over device pointers (d_alt, d_pos_off, d_pat_off: the three packed arrays of fmx_count_class_batch, in device
  * memory and trusted as the literal device forms trust theirs); asynchronous on `stream`, nothing is allocated or synchronised.
  * THE SEARCH keeps, per pattern, a frontier of SA ranges: the last position gives {C[c], C[c + 1]} of each of its codes, every

@@ -12,6 +12,7 @@
 // *Batch methods are the intended production surface.  bindings/java holds the equivalent JNI shim.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <stdexcept>
@@ -388,6 +389,59 @@ public:
         return out;
     }
 
+    // the distinct VALUES that follow a pattern, with the number of hits that have each (fmx.h "THE VALUES THAT FOLLOW A PATTERN, WITH
+    // COUNTS": grep -o 'blk_[^ ]*' | sort | uniq -c).  The value of a hit is the text behind the pattern up to, not including, the
+    // first code unit of `stop` (at most 64 units), at most maxLen (1 .. 64) units.  fieldValuesBatch: the values of pattern i are
+    // the groups offsets[i] .. offsets[i + 1] - 1, ascending by code unit, a value in front of its extensions; group g is
+    // chars[textOffsets[g] .. textOffsets[g + 1]) and counts[g] hits have it; status[i] is the pattern's own (not thrown: one empty
+    // pattern does not hide the others).  fieldValues: one pattern as (value, count) pairs; top > 0: the `top` entries with the
+    // largest counts, ties by value (sorted on the host over the groups); ignoreCase: the pattern in any case, one answer.
+    struct FieldValues {
+        std::vector<int64_t> offsets, textOffsets;
+        std::vector<int32_t> counts, occurrences, status;
+        std::u16string chars;
+        std::u16string operator[](size_t g) const { return chars.substr((size_t)textOffsets[g], (size_t)(textOffsets[g + 1] - textOffsets[g])); }
+    };
+    FieldValues fieldValuesBatch(const std::vector<std::u16string> &patterns, const std::u16string &stop, int maxLen) const {
+        std::vector<uint16_t> chars;
+        std::vector<int32_t> off;
+        pack(patterns, chars, off);
+        const int32_t n = (int32_t)patterns.size();
+        FieldValues out = emptyFieldValues(patterns.size());
+        int32_t *counts = nullptr;
+        int64_t *textOff = nullptr;
+        uint16_t *units = nullptr;
+        detail::check(fmx_field_values_batch(h_, chars.data(), off.data(), n, reinterpret_cast<const uint16_t *>(stop.data()), (int32_t)stop.size(),
+                                             maxLen, out.offsets.data(), &counts, &textOff, &units, out.occurrences.data(), out.status.data()),
+                      "fmx_field_values_batch");
+        return takeFieldValues(out, counts, textOff, units);
+    }
+    FieldValues fieldValuesClass(const std::vector<ClassPattern> &patterns, const std::u16string &stop, int maxLen, int maxRanges = 256) const {
+        ClassArrays a(patterns);
+        FieldValues out = emptyFieldValues(patterns.size());
+        int32_t *counts = nullptr;
+        int64_t *textOff = nullptr;
+        uint16_t *units = nullptr;
+        detail::check(fmx_field_values_class_batch(h_, a.alt.data(), a.posOff.data(), a.nPos(), a.patOff.data(), a.n(), maxRanges,
+                                                   reinterpret_cast<const uint16_t *>(stop.data()), (int32_t)stop.size(), maxLen, out.offsets.data(),
+                                                   &counts, &textOff, &units, out.occurrences.data(), out.status.data()),
+                      "fmx_field_values_class_batch");
+        return takeFieldValues(out, counts, textOff, units);
+    }
+    std::vector<std::pair<std::u16string, int32_t>> fieldValues(const std::u16string &pattern, const std::u16string &stop = u" \t\r\n",
+                                                                 int maxLen = 32, int top = 0, bool ignoreCaseOfPattern = false) const {
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const FieldValues v = ignoreCaseOfPattern ? fieldValuesClass({ignoreCase(pattern)}, stop, maxLen) : fieldValuesBatch({pattern}, stop, maxLen);
+        detail::raise_for_status(v.status[0]);
+        std::vector<std::pair<std::u16string, int32_t>> out;
+        for (size_t g = 0; g < v.counts.size(); ++g) out.emplace_back(v[g], v.counts[g]);
+        if (top > 0) {  // (a stable sort: equal counts keep the order of the values)
+            std::stable_sort(out.begin(), out.end(), [](const auto &a, const auto &b) { return a.second > b.second; });
+            if (out.size() > (size_t)top) out.resize((size_t)top);
+        }
+        return out;
+    }
+
     // the text of ranges and of lines in ONE packed array (fmx.h "THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY"): range / line
     // i is chars[offsets[i] .. offsets[i + 1]) — what extract(start, stop, destination, 0) leaves in destination; memory follows
     // the sum of the lengths.  status[i] is the range's own (not thrown: one range out of the text does not hide the others);
@@ -529,6 +583,30 @@ private:
         if (chars.empty()) chars.push_back(0);
     }
     // the three packed arrays of a batch of class patterns (fmx_count_class_batch)
+    static FieldValues emptyFieldValues(size_t n) {
+        FieldValues out;
+        out.offsets.assign(n + 1, 0);
+        out.textOffsets.assign(1, 0);
+        out.occurrences.assign(n, 0);
+        out.status.assign(n, 0);
+        return out;
+    }
+    // the library's ONE buffer {counts | text offsets | code units} into the vectors, then freed (counts owns it)
+    static FieldValues takeFieldValues(FieldValues &out, int32_t *counts, const int64_t *textOff, const uint16_t *units) {
+        const size_t groups = (size_t)out.offsets.back();
+        try {
+            if (counts) {
+                out.counts.assign(counts, counts + groups);
+                out.textOffsets.assign(textOff, textOff + groups + 1);
+                out.chars.assign(reinterpret_cast<const char16_t *>(units), (size_t)textOff[groups]);
+            }
+        } catch (...) {
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(counts));
+            throw;
+        }
+        fmx_free_buffer(reinterpret_cast<uint8_t *>(counts));
+        return out;
+    }
     struct ClassArrays {
         std::vector<uint16_t> alt;
         std::vector<int32_t> posOff{0}, patOff{0};

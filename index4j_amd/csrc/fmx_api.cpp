@@ -4,6 +4,7 @@
 #include "../../include/fmx.h"
 #include "fmx_device.hpp"
 #include "fmx_build_stage.hpp"
+#include "fmx_hit_values.hpp"
 #include "fmx_model.hpp"
 #include "fmx_options.hpp"
 #include "fmx_plan.hpp"
@@ -3665,6 +3666,211 @@ int fmx_line_text_batch(const fmx_index *idx, const int32_t *lines, int32_t n, i
                                     idx->n_cu, d_in, n, d_start, d_stop, call.stream.s);
     if (e) return fail(FMX_E_HIP, std::string("k_line_bounds launch: ") + hipGetErrorString((hipError_t)e));
     return extract_packed_host(call, d_start, d_stop, n, text_off, chars, status);
+    });
+}
+
+// ---- the values that follow a pattern, with counts (fmx_hit_values.hip): grep -o | sort | uniq -c ---------------------------------
+static int check_values_shape(const uint16_t *stop, int32_t n_stop, int32_t max_len) {
+    if (max_len < 1 || max_len > fmx::kValuesMaxLen) return fail(FMX_E_ARG, "max_len is outside [1, 64]");
+    if (n_stop < 0 || n_stop > fmx::kValuesMaxStop || (n_stop > 0 && !stop)) return fail(FMX_E_ARG, "the stop set is outside [0, 64] code units");
+    return FMX_OK;
+}
+static int check_values_hits(int64_t n_hits, int32_t max_len) {
+    if (n_hits > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one call");
+    if (n_hits * max_len > fmx::kValuesMaxUnits) return fail(FMX_E_ARG, "the windows of the hits hold more than 2^35 code units");
+    return FMX_OK;
+}
+
+size_t fmx_values_of_hits_scratch_bytes(int32_t n, int64_t n_hits, int32_t max_len) { return fmx::values_of_hits_scratch_bytes(n, n_hits, max_len); }
+
+// the three steps behind the arguments' checks (n > 0, n_hits > 0, the workspace large enough): the windows, their text, the groups.
+// An index without extraction: no values, FMX_ST_NOT_ENABLED for every pattern.
+static int values_of_hits_impl(const fmx_index *idx, int32_t n, const int32_t *term_len, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                               const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int64_t *d_val_off, int32_t *d_count,
+                               int64_t *d_text_off, int32_t *d_status, void *d_ws, size_t ws_bytes, hipStream_t st) {
+    if (!idx->dev.enable_extract) {
+        HIP_TRY(hipMemsetAsync(d_val_off, 0, ((size_t)n + 1) * sizeof(int64_t), st));
+        HIP_TRY(hipMemsetAsync(d_text_off, 0, sizeof(int64_t), st));
+        const int e = fmx::launch_values_status_all(idx->n_cu, d_status, n, FMX_ST_NOT_ENABLED, st);
+        if (e) return fail(FMX_E_HIP, std::string("values of hits: ") + hipGetErrorString((hipError_t)e));
+        return FMX_OK;
+    }
+    fmx::ValuesWindows w;
+    if (!fmx::values_windows(d_ws, ws_bytes, n, n_hits, max_len, &w)) return fail(FMX_E_ARG, "the workspace is smaller than fmx_values_of_hits_scratch_bytes");
+    int e = fmx::launch_values_ranges(line_text_length(idx), idx->n_cu, n, term_len, stop, n_stop, max_len, d_hit_off, d_locs, n_hits, d_ws, ws_bytes, st);
+    if (e) return fail(FMX_E_HIP, std::string("windows of hits: ") + hipGetErrorString((hipError_t)e));
+    e = fmx::launch_extract_packed_offsets(idx->dev, w.start, w.stop, (int32_t)n_hits, w.text_off, w.piece_off, w.status, w.scratch, w.scratch_bytes, st);
+    if (e) return fail(FMX_E_HIP, std::string("extract packed offsets: ") + hipGetErrorString((hipError_t)e));
+    if (const int rc = extract_packed_fill_impl(idx, w.start, w.stop, (int32_t)n_hits, w.text_off, w.piece_off, -1, w.chars, w.status, w.scratch, st))
+        return rc;
+    e = fmx::launch_values_groups(idx->n_cu, n, n_stop, max_len, n_hits, d_hit_off, d_val_off, d_count, d_text_off, d_status, d_ws, ws_bytes, st);
+    if (e) return fail(FMX_E_HIP, std::string("values of hits: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+}
+
+int fmx_values_of_hits_dev(const fmx_index *idx, int32_t n, const int32_t *term_len, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                           const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int64_t *d_val_off, int32_t *d_count,
+                           int64_t *d_text_off, int32_t *d_status, void *d_ws, size_t ws_bytes, void *stream) {
+    return guarded([&]() -> int {
+    if (!idx || n < 0 || n_hits < 0 || !d_val_off || !d_text_off || (n > 0 && (!d_hit_off || !term_len)) ||
+        (n > 0 && n_hits > 0 && (!d_locs || !d_count)))
+        return fail(FMX_E_ARG, "bad arguments");
+    int rc = check_values_shape(stop, n_stop, max_len);
+    if (rc) return rc;
+    if ((rc = check_values_hits(n_hits, max_len))) return rc;
+    if ((rc = check_term_len(n, term_len))) return rc;
+    if ((rc = require_fm_device(idx))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0 || n_hits == 0) {
+        HIP_TRY(hipMemsetAsync(d_val_off, 0, ((size_t)n + 1) * sizeof(int64_t), st));
+        HIP_TRY(hipMemsetAsync(d_text_off, 0, sizeof(int64_t), st));
+        return FMX_OK;
+    }
+    if (!d_ws || ws_bytes < fmx::values_of_hits_scratch_bytes(n, n_hits, max_len))
+        return fail(FMX_E_ARG, "the workspace is smaller than fmx_values_of_hits_scratch_bytes");
+    return values_of_hits_impl(idx, n, term_len, stop, n_stop, max_len, d_hit_off, d_locs, n_hits, d_val_off, d_count, d_text_off, d_status, d_ws,
+                               ws_bytes, st);
+    });
+}
+
+int fmx_values_fill_dev(const fmx_index *idx, int64_t n_groups, const int64_t *d_text_off, uint16_t *d_chars, const void *d_ws, size_t ws_bytes,
+                        void *stream) {
+    return guarded([&]() -> int {
+    if (!idx || n_groups < 0 || n_groups > 0x7fffffff || (n_groups > 0 && (!d_text_off || !d_chars || !d_ws)))
+        return fail(FMX_E_ARG, "bad arguments");
+    int rc = require_fm_device(idx);
+    if (rc) return rc;
+    if (n_groups == 0) return FMX_OK;
+    if (ws_bytes < (size_t)n_groups * sizeof(void *)) return fail(FMX_E_ARG, "the workspace is smaller than fmx_values_of_hits_scratch_bytes");
+    const int e = fmx::launch_values_fill(idx->n_cu, n_groups, d_text_off, d_chars, d_ws, stream);
+    if (e) return fail(FMX_E_HIP, std::string("k_val_fill launch: ") + hipGetErrorString((hipError_t)e));
+    return FMX_OK;
+    });
+}
+
+// The host forms: a range stage, every hit into one device block, the stages above, ONE wait for the number of groups and one for
+// their code units, the fill, and only the groups come down — into ONE allocation {counts | text_off | chars}.
+namespace {
+struct ValuesShape {
+    int64_t groups = 0, units = 0, redo = 0;  // redo: the windows the packed extract ran literally
+    size_t text_off_at = 0, chars_at = 0;  // inside the result
+};
+}  // namespace
+static int values_down(PackedCall &call, RangeStage &r, const int32_t *term_len, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                       int64_t *val_off, ValuesShape &shape) {
+    const fmx_index *idx = call.blocks.idx;
+    Scratch &b = call.blocks;
+    const hipStream_t st = call.stream.s;
+    const int32_t n = r.n;
+    int rc = check_values_hits(r.total, max_len);
+    if (rc) return rc;
+    int64_t *d_voff = nullptr, *d_toff = nullptr;
+    int32_t *d_locs = nullptr, *d_count = nullptr;
+    uint16_t *d_chars = nullptr;
+    if ((rc = b.block((size_t)(n + 1) * 8, &d_voff))) return rc;
+    if (!idx->dev.enable_extract || r.total == 0) {
+        HIP_TRY(hipMemsetAsync(d_voff, 0, (size_t)(n + 1) * 8, st));
+        if (!idx->dev.enable_extract) {
+            const int e = fmx::launch_values_status_all(idx->n_cu, r.status, n, FMX_ST_NOT_ENABLED, st);
+            if (e) return fail(FMX_E_HIP, std::string("values of hits: ") + hipGetErrorString((hipError_t)e));
+        }
+    } else {
+        const size_t ws_bytes = fmx::values_of_hits_scratch_bytes(n, r.total, max_len);
+        void *ws = nullptr;
+        if ((rc = b.block((size_t)r.total * 4, &d_locs)) || (rc = b.block((size_t)r.total * 4, &d_count)) ||
+            (rc = b.block(((size_t)r.total + 1) * 8, &d_toff)) || (rc = b.block(ws_bytes, &ws)) || (rc = fill_hits(call, r, 0, r.total, d_locs)) ||
+            (rc = values_of_hits_impl(idx, n, term_len, stop, n_stop, max_len, r.hit_off, d_locs, r.total, d_voff, d_count, d_toff, r.status, ws,
+                                      ws_bytes, st)))
+            return rc;
+        fmx::ValuesWindows w;
+        int32_t redo = 0;
+        (void)fmx::values_windows(ws, ws_bytes, n, r.total, max_len, &w);
+        HIP_TRY(hipMemcpyAsync(&shape.groups, d_voff + n, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&redo, fmx::extract_packed_redo(w.scratch), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        shape.redo = redo;
+        if (shape.groups > 0) {
+            HIP_TRY(hipMemcpyAsync(&shape.units, d_toff + shape.groups, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            const size_t G = (size_t)shape.groups, T = (size_t)shape.units;
+            shape.text_off_at = (G * 4 + 7) / 8 * 8;
+            shape.chars_at = shape.text_off_at + (G + 1) * 8;
+            if (!call.result.alloc(shape.chars_at + T * 2 + 2))
+                return fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(shape.groups) + " values");
+            uint8_t *out = static_cast<uint8_t *>(call.result.p);
+            if (T > 0) {
+                if ((rc = b.block(T * 2 + 8, &d_chars))) return rc;
+                const int e = fmx::launch_values_fill(idx->n_cu, shape.groups, d_toff, d_chars, ws, st);
+                if (e) return fail(FMX_E_HIP, std::string("k_val_fill launch: ") + hipGetErrorString((hipError_t)e));
+                HIP_TRY(hipMemcpyAsync(out + shape.chars_at, d_chars, T * 2, hipMemcpyDeviceToHost, st));
+            }
+            HIP_TRY(hipMemcpyAsync(out, d_count, G * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out + shape.text_off_at, d_toff, (G + 1) * 8, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(val_off, d_voff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    return FMX_OK;
+}
+static void values_hand_over(const ValuesShape &shape, int32_t **counts, int64_t **text_off, uint16_t **chars) {
+    g_extract_packed_redo = shape.redo;
+    if (!*counts) return;
+    uint8_t *out = reinterpret_cast<uint8_t *>(*counts);
+    *text_off = reinterpret_cast<int64_t *>(out + shape.text_off_at);
+    *chars = reinterpret_cast<uint16_t *>(out + shape.chars_at);
+}
+
+int fmx_field_values_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *stop, int32_t n_stop,
+                           int32_t max_len, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars, int32_t *occurrences,
+                           int32_t *status) {
+    return guarded([&]() -> int {
+    if (counts) *counts = nullptr;
+    if (text_off) *text_off = nullptr;
+    if (chars) *chars = nullptr;
+    if (!idx || n < 0 || !val_off || !counts || !text_off || !chars || (n > 0 && !pat_off)) return fail(FMX_E_ARG, "bad arguments");
+    int rc = check_values_shape(stop, n_stop, max_len);
+    if (rc) return rc;
+    if ((rc = require_fm_device(idx))) return rc;
+    if (n == 0) {
+        val_off[0] = 0;
+        return FMX_OK;
+    }
+    PackedCall call(idx);
+    RangeStage r;
+    ValuesShape shape;
+    if ((rc = literal_ranges(call, pat, pat_off, n, -1, true, false, status != nullptr, r))) return rc;
+    const std::vector<int32_t> len = lengths_of(pat_off, n);  // (pat_off has been judged)
+    if ((rc = values_down(call, r, len.data(), stop, n_stop, max_len, val_off, shape)) ||
+        (rc = packed_finish(call, r, occurrences, nullptr, status, counts)))
+        return rc;
+    values_hand_over(shape, counts, text_off, chars);
+    return FMX_OK;
+    });
+}
+
+int fmx_field_values_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                 int32_t n, int32_t max_ranges, const uint16_t *stop, int32_t n_stop, int32_t max_len, int64_t *val_off,
+                                 int32_t **counts, int64_t **text_off, uint16_t **chars, int32_t *occurrences, int32_t *status) {
+    return guarded([&]() -> int {
+    if (counts) *counts = nullptr;
+    if (text_off) *text_off = nullptr;
+    if (chars) *chars = nullptr;
+    if (!val_off || !counts || !text_off || !chars) return fail(FMX_E_ARG, "bad arguments");
+    int rc;
+    if ((rc = check_values_shape(stop, n_stop, max_len)) || (rc = class_args(idx, alt, pos_off, n_pos, pat_off, n, max_ranges))) return rc;
+    if (n == 0) {
+        val_off[0] = 0;
+        return FMX_OK;
+    }
+    PackedCall call(idx);
+    RangeStage r;
+    ValuesShape shape;
+    const std::vector<int32_t> len = lengths_of(pat_off, n);
+    if ((rc = class_ranges(call, alt, pos_off, n_pos, pat_off, n, max_ranges, true, status != nullptr, r)) ||
+        (rc = values_down(call, r, len.data(), stop, n_stop, max_len, val_off, shape)) ||
+        (rc = packed_finish(call, r, occurrences, nullptr, status, counts)))
+        return rc;
+    values_hand_over(shape, counts, text_off, chars);
+    return FMX_OK;
     });
 }
 

@@ -119,4 +119,30 @@ int launch_sequence_lines(const int32_t *T, int32_t count, int64_t n_lines, int3
                           int32_t max_lines, int64_t *line_off, int32_t *lines, int32_t *line_count, int32_t *spans, void *ws, size_t ws_bytes,
                           void *stream);
 
+// fmx_hit_values.hip — packed hits of a batch of patterns -> the distinct values that follow each pattern, with counts
+// (fmx_values_of_hits_dev / fmx_values_fill_dev; fmx_hit_values.hpp has the definition).  Compiled once.  term_len (n, none
+// negative) and stop (n_stop units) are HOST arrays the caller has validated; they are copied into the workspace before
+// launch_values_ranges returns.  The C-ABI layer runs three steps on one stream over one workspace:
+//   launch_values_ranges   pattern and window [s, e) of every hit, into the regions values_windows names;
+//   the packed extract     launch_extract_packed_offsets and the image form's launch_extract_packed_fill over those n_hits ranges;
+//   launch_values_groups   lengths, runs, the sorting passes, heads: val_off (n + 1), count and text_off (one per group, text_off one
+//                          more), status (nullable: a window the extract ran literally hands its status to its pattern).
+// launch_values_fill: the groups' code units into chars (groups = val_off[n], read by the caller).  The grids are hit_lines_geometry's.  hipErrorInvalidValue
+// before anything is launched or written: too small a workspace, a shape outside values_of_hits_scratch_bytes' (which is 0 then).
+struct ValuesWindows {
+    int32_t *start, *stop, *status;
+    int64_t *text_off, *piece_off;
+    uint16_t *chars;
+    void *scratch;
+    size_t scratch_bytes;
+};
+size_t values_of_hits_scratch_bytes(int32_t n, int64_t n_hits, int32_t max_len);
+bool values_windows(void *ws, size_t ws_bytes, int32_t n, int64_t n_hits, int32_t max_len, ValuesWindows *out);
+int launch_values_ranges(int32_t text_len, int n_cu, int32_t n, const int32_t *term_len, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                         const int64_t *hit_off, const int32_t *locs, int64_t n_hits, void *ws, size_t ws_bytes, void *stream);
+int launch_values_groups(int n_cu, int32_t n, int32_t n_stop, int32_t max_len, int64_t n_hits, const int64_t *hit_off,
+                         int64_t *val_off, int32_t *count, int64_t *text_off, int32_t *status, void *ws, size_t ws_bytes, void *stream);
+int launch_values_fill(int n_cu, int64_t groups, const int64_t *text_off, uint16_t *chars, const void *ws, void *stream);
+int launch_values_status_all(int n_cu, int32_t *status, int32_t n, int32_t value, void *stream);  // status[0, n) = value
+
 }  // namespace fmx

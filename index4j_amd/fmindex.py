@@ -518,6 +518,46 @@ class FmIndex:
                                    (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, int(max_ranges)), n, query_off, max_lines,
                                    want_counts, want_spans)
 
+    # ---- the values that follow a pattern, with counts (fmx.h "THE VALUES THAT FOLLOW A PATTERN, WITH COUNTS") ----
+    def _values_call(self, call, where, args, n, stop, max_len):
+        stop = as_chars(stop)
+        val_off = np.zeros(n + 1, dtype=np.int64)
+        occurrences = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        buf, toff_at, chars_at = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(call(self._h, *args, stop.ctypes.data, len(stop), int(max_len), val_off.ctypes.data, C.byref(buf), C.byref(toff_at),
+                   C.byref(chars_at), occurrences.ctypes.data, status.ctypes.data), where)
+        groups = int(val_off[n])
+        try:  # the library's buffer (counts, offsets and code units in one block) is copied into arrays of NumPy's own
+            if groups:
+                counts = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_int32)), shape=(groups,)).copy()
+                text_off = np.ctypeslib.as_array(C.cast(toff_at, C.POINTER(C.c_int64)), shape=(groups + 1,)).copy()
+                units = int(text_off[groups])
+                chars = np.ctypeslib.as_array(C.cast(chars_at, C.POINTER(C.c_uint16)), shape=(units,)).copy() if units else np.zeros(0, np.uint16)
+            else:
+                counts, text_off, chars = np.zeros(0, np.int32), np.zeros(1, np.int64), np.zeros(0, np.uint16)
+        finally:
+            lib.fmx_free_buffer(buf)
+        return chars, text_off, counts, val_off, status, occurrences
+
+    def field_values_batch(self, chars, offsets, stop, max_len):
+        """the distinct VALUES that follow every pattern, with the number of hits that have each (fmx_field_values_batch; grep -o |
+        sort | uniq -c): the value of a hit is the text behind the pattern up to, not including, the first code unit of `stop`
+        (str or code units, at most 64), at most max_len (1 .. 64) units.  Returns (chars, text_off, counts, val_off, status,
+        occurrences): the values of pattern i are the groups val_off[i] .. val_off[i + 1] - 1, ascending by code unit, a value in
+        front of its extensions; group g is chars[text_off[g]:text_off[g + 1]] and counts[g] hits have it."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        n = len(offsets) - 1
+        return self._values_call(lib.fmx_field_values_batch, "fmx_field_values_batch", (chars.ctypes.data, offsets.ctypes.data, n), n, stop, max_len)
+
+    def field_values_class_batch(self, alt, pos_off, pat_off, stop, max_len, max_ranges=CLASS_RANGES_DEFAULT):
+        """field_values_batch with class patterns (fmx_field_values_class_batch; a pattern's length is its number of positions): the
+        values behind ALL spellings of a pattern make one answer; same returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        return self._values_call(lib.fmx_field_values_class_batch, "fmx_field_values_class_batch",
+                                 (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, int(max_ranges)), n, stop, max_len)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -711,6 +751,25 @@ class FmIndex:
         for st in out[2]:
             raise_for_status(st)
         return (out[0], out[3]) if want_spans else out[0]
+
+    def field_values(self, pattern, stop=" \t\r\n", max_len=32, top=None, ignore_case=False):
+        """[(value, count)] of the distinct values that follow `pattern` (grep -o 'pattern[^stop]*' | sort | uniq -c): ascending by
+        UTF-16 code unit, a value in front of its extensions; with top=k the k entries with the largest counts, ties by value
+        (sorted on the host over the groups).  ignore_case: the pattern in any case, one answer for all spellings."""
+        p = as_chars(pattern)
+        if len(p) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        if ignore_case:
+            out = self.field_values_class_batch(*pack_class_patterns([_ignore_case(p)]), stop, max_len)
+        else:
+            out = self.field_values_batch(*pack_patterns([p]), stop, max_len)
+        chars, text_off, counts, _, status, _ = out
+        raise_for_status(status[0])
+        values = [chars[a:b].tobytes().decode("utf-16-le", "surrogatepass") for a, b in zip(text_off[:-1], text_off[1:])]
+        pairs = list(zip(values, counts.tolist()))
+        if top is not None:  # (a stable sort: equal counts keep the order of the values)
+            pairs = sorted(pairs, key=lambda vc: -vc[1])[:max(int(top), 0)]
+        return pairs
 
     def line_text(self, lines):
         """the lines with these ids as a list of str (the boundary excluded); raises for an id that is no line"""

@@ -110,7 +110,14 @@ __global__ __launch_bounds__(kKeyBlock) void k_val_lengths(const uint16_t *__res
         const int64_t at = win_off[t];
         vlen[t] = fm_val_length<kBitmap>(win + at, (int32_t)(win_off[t + 1] - at), s_set, n_stop);
         const int32_t ws = win_status[t];
-        if (status && ws != ST_OK) status[p] = ws;  // (a window the redo pass ran: the literal extract's status)
+        // (a window the redo pass ran: the literal extract's status.)  Several lanes may store to one status[p], and the value does
+        // not depend on which of them is last: every non-OK status here is ST_JAVA_AIOOBE.  A window is [s, e) with 0 <= s <= e <=
+        // textLength < ix.length on an index with extraction (one without never gets here: fmx_values_of_hits_dev answers
+        // ST_NOT_ENABLED for all patterns itself), so fm_extract_packed_status is ST_OK for it, and of fm_extract's statuses
+        // neither the range checks (FM:566-576), nor ST_DEST_TOO_SMALL (dst_len = e - s, offset 0), nor the destination index
+        // (remaining - 1 in [0, dst_len)) can fire; what is left is the status of an LF-step, and fm_lf_step and what it calls set
+        // no other than ST_JAVA_AIOOBE.
+        if (status && ws != ST_OK) status[p] = ws;
     }
 }
 

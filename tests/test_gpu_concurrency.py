@@ -65,8 +65,11 @@ def test_host_entry_points_from_many_threads_on_one_index():
 class PackedBatch:
     """a batch of words for the packed host forms and what the TEXT answers for it, literally and in any case: per word the
     positions (str.find) and their distinct lines (bisect over the newlines), the words cut into queries of ALL / ANY / NONE
-    terms, and the lines of those queries by the set formula of fmx.h.  Made once, before the threads start; read-only."""
+    terms, and the lines of those queries by the set formula of fmx.h; the same cut read as SEQUENCES of terms in order, their lines
+    and spans by re on every line; the values behind every word up to a blank or the line's end, VALUE_LEN units at most, by
+    slicing into a Counter.  Made once, before the threads start; read-only."""
     KINDS = ((0,), (1, 1), (0, 1, 2), (), (0, 2))  # ALL; ANY ANY; ALL ANY NONE; no terms; ALL NONE — over and over
+    VALUE_STOP, VALUE_LEN = " \n", 8
 
     def __init__(self, words, low, newlines):
         self.words, self.n = words, len(words)
@@ -79,6 +82,36 @@ class PackedBatch:
         self.kinds, self.query_off = np.array(kinds[: self.n], np.uint8), np.array(query_off, np.int32)
         self.exact = self.answers(HD, words, newlines)
         self.any_case = self.answers(low, [w.lower() for w in words], newlines)
+        self.sequences, self.spans = self.sequence_answers(words)
+        self.values = [self.values_behind(w, p) for w, p in zip(words, self.exact["pos"])]
+
+    def sequence_answers(self, words):
+        """per sequence (the cut of query_off) its lines and their spans: t_0.*?t_1.*? ... on every line of the text"""
+        import re
+
+        lines, spans = [], []
+        for Q in range(len(self.query_off) - 1):
+            terms = words[self.query_off[Q]:self.query_off[Q + 1]]
+            mine, where, at = [], [], 0
+            rx = re.compile(".*?".join(map(re.escape, terms)))
+            for k, ln in enumerate(HD.split("\n")[:-1] if terms else []):
+                m = rx.search(ln)
+                if m:
+                    mine.append(k)
+                    where.append((at + m.start(), at + m.end()))
+                at += len(ln) + 1
+            lines.append(mine)
+            spans.append(where)
+        return lines, spans
+
+    def values_behind(self, word, pos):
+        """[(value, count)] in code-unit order (the fixture holds no surrogates: the order of str)"""
+        import collections
+        import re
+
+        stop = re.compile("[%s]" % re.escape(self.VALUE_STOP))
+        found = collections.Counter(stop.split(HD[p + len(word):p + len(word) + self.VALUE_LEN], 1)[0] for p in pos.tolist())
+        return sorted(found.items())
 
     def answers(self, hay, words, newlines):
         import bisect
@@ -131,6 +164,15 @@ class PackedBatch:
         hits(fm.locate_all_class_batch(*self.classes), self.any_case, "locate_all, any case")
         lines_of(fm.match_query_class_batch(*self.classes, self.query_off, self.kinds, want_counts=True), self.any_case["queries"], self.any_case,
                  "match_query, any case")
+        got = fm.match_sequence_batch(*self.literal, self.query_off, want_counts=True, want_spans=True)
+        lines_of(got[:5], self.sequences, self.exact, "match_sequence")
+        assert got[5].tolist() == [list(ab) for where in self.spans for ab in where], ("match_sequence, spans", who)
+        chars, text_off, counts, val_off, status, occurrences = fm.field_values_batch(*self.literal, self.VALUE_STOP, self.VALUE_LEN)
+        assert (status == zeros).all() and (occurrences == self.exact["occurrences"]).all(), ("field_values", who)
+        assert (np.diff(val_off) == [len(v) for v in self.values]).all() and val_off[0] == 0 and len(counts) == val_off[-1], ("field_values", who)
+        flat = [vc for v in self.values for vc in v]
+        assert counts.tolist() == [c for _, c in flat] and (np.diff(text_off) == [len(v) for v, _ in flat]).all(), ("field_values, counts", who)
+        assert ia.chars_to_str(chars) == "".join(v for v, _ in flat), ("field_values, code units", who)
         lines = lines[:300]
         chars, text_off, status = fm.line_text_batch(lines)
         want = [text_lines[k] for k in lines.tolist()]
@@ -138,8 +180,8 @@ class PackedBatch:
 
 
 def test_packed_host_forms_from_many_threads_on_one_index():
-    """fmx_locate_all_batch, fmx_match_lines_batch, fmx_match_query_batch, fmx_locate_all_class_batch, fmx_match_query_class_batch
-    and fmx_line_text_batch from four threads on one index at once, three rounds each: every call takes blocks of the recycling
+    """fmx_locate_all_batch, fmx_match_lines_batch, fmx_match_query_batch, fmx_locate_all_class_batch, fmx_match_query_class_batch,
+    fmx_match_sequence_batch, fmx_field_values_batch and fmx_line_text_batch from four threads on one index at once, three rounds each: every call takes blocks of the recycling
     cache that return only after its stream has been waited for — a block handed on too early shows as another thread's answer.
     Each thread has a batch of its own size; judged against the text itself (PackedBatch)."""
     newlines = [i for i, c in enumerate(HD) if c == "\n"]

@@ -75,11 +75,18 @@ double fmx_build_wavelet_seconds(const fmx_index *idx);
  * of 64 slots, in-group slot = low bits of the first character's code XOR hash bits of the rest; at most 0.5 full, 0.7 where
  * only that keeps it inside its limit).  Depth *chars: as deep as a 64-bit key holds (8 codes of 8 bits, 4 of 16; option
  * "suffix_table_chars" caps it) while the table stays below the smaller of the budget (option "suffix_table_mb", default 256; 0
- * = no table) and 1 / "suffix_table_image_fraction" of the image (default an eighth): 5 characters in 8.4 MB on the 256 MiB
- * synthetic log.  count / locate batches start from it: one slot instead of 2 * (k - 1) rank evaluations for a pattern's last k
- * <= *chars characters; a string that is not in it (it does not occur, holds an unknown character, or its search raised a
- * status) is searched by the loop.  Results, statuses and LF-step counts are unchanged (option "suffix_table" = 0 makes
- * launches ignore it, for A/B).  *chars = 0: no table; *bytes = the table's size. */
+ * = no table) and 1 / "suffix_table_image_fraction" of the image (default an eighth).  Where the NEXT level exists but would
+ * pass that limit as hashed slots, it is grown as CHILD LISTS if that fits the same limit (8-bit codes, at most 5 hashed
+ * characters, "suffix_table_chars" permitting): a string X of that level is a string P of the deepest hashed level with one code
+ * appended, and the X of one P lie side by side inside P's rows — so an X takes a code byte and its first row (five bytes,
+ * its end is its neighbour's first row; a terminator per P), sorted under P's slot.  Such a level is complete or absent: every
+ * string of *chars characters that the hashed form would hold is answered.  On the 256 MiB synthetic log: 5 characters hashed
+ * in 8.4 MB, the 6th as lists, 19.7 MB together (limit 21.3).  count / locate batches start from the table: one slot (the
+ * deepest level as lists: slot, codes, rows) instead of 2 * (k - 1) rank evaluations for a pattern's last k <= *chars
+ * characters; a string that is not in it (it does not occur, holds an unknown character, or its search raised a status) is
+ * searched by the loop.  Results, statuses and LF-step counts are unchanged (option "suffix_table" = 0 makes launches ignore
+ * it, for A/B).  *chars = 0: no table; *bytes = the table's size, lists included (a power of two exactly when every level is
+ * hashed). */
 int fmx_suffix_table_info(const fmx_index *idx, int32_t *chars, int64_t *bytes);
 
 /* The window directory of a resident index (grown by fmx_to_device / fmx_attach_device_blob beside the image, like the suffix

@@ -50,6 +50,11 @@ FMX_DISPATCH_FN(launch_suffix_level1)
 FMX_DISPATCH_FN(launch_suffix_expand)
 FMX_DISPATCH_FN(launch_suffix_insert)
 FMX_DISPATCH_FN(launch_suffix_order1)
+FMX_DISPATCH_FN(launch_suffix_child_parents)
+FMX_DISPATCH_FN(launch_suffix_child_scan)
+FMX_DISPATCH_FN(launch_suffix_child_place)
+FMX_DISPATCH_FN(launch_suffix_child_sort)
+FMX_DISPATCH_FN(launch_suffix_child_write)
 FMX_DISPATCH_FN(launch_win_build)
 FMX_DISPATCH_FN(launch_win_other)
 FMX_DISPATCH_FN(launch_win_flat)
@@ -86,6 +91,7 @@ struct fmx_index {
     double wavelet_device_seconds = 0;  // fmx_build_on_device: seconds of the wavelet encode in HBM (0: host encoder)
     void *d_suffix_table = nullptr;     // DevIndex.suffix_table (owned, whoever owns the image)
     void *d_suffix_order1 = nullptr;    // DevIndex.suffix_order1 (owned likewise)
+    void *d_suffix_children = nullptr;  // DevIndex.suffix_child_rows, and behind them suffix_child_codes (owned likewise)
     void *d_self = nullptr;             // DevIndex.self: the resident copy of `dev` the kernels' cold routes read (owned likewise)
     void *d_win = nullptr;              // DevIndex.win: the window directory's cells (owned likewise)
     void *d_win_other = nullptr;        // DevIndex.win_other: ... and the entries of the positions no class holds
@@ -229,6 +235,8 @@ int publish_dev_index(fmx_index *idx) {
     copy.sb_cache = nullptr;
     copy.suffix_table = nullptr;
     copy.suffix_order1 = nullptr;
+    copy.suffix_child_rows = nullptr;
+    copy.suffix_child_codes = nullptr;
     copy.win = nullptr;  // (a cold route is the tree walk itself; the directory is grown from its answers)
     copy.win_other = nullptr;
     copy.win_full = nullptr;
@@ -863,6 +871,7 @@ static void release_device_state(fmx_index *idx) {
     if (idx->owns_device && idx->d_blob) (void)hipFree(idx->d_blob);
     if (idx->d_suffix_table) (void)hipFree(idx->d_suffix_table);
     if (idx->d_suffix_order1) (void)hipFree(idx->d_suffix_order1);
+    if (idx->d_suffix_children) (void)hipFree(idx->d_suffix_children);
     if (idx->d_self) (void)hipFree(idx->d_self);
     if (idx->d_win) (void)hipFree(idx->d_win);
     if (idx->d_win_other) (void)hipFree(idx->d_win_other);
@@ -873,7 +882,7 @@ static void release_device_state(fmx_index *idx) {
     idx->line_boundary = -1;
     idx->line_count = 0;
     idx->n_lines = 0;
-    idx->d_blob = idx->d_suffix_table = idx->d_suffix_order1 = idx->d_self = idx->d_win = idx->d_win_other = idx->d_rows = nullptr;
+    idx->d_blob = idx->d_suffix_table = idx->d_suffix_order1 = idx->d_suffix_children = idx->d_self = idx->d_win = idx->d_win_other = idx->d_rows = nullptr;
     idx->d_len = 0;
     idx->win_bytes = idx->suffix_table_bytes = idx->rows_bytes = 0;
     idx->rows_replay = 0;
@@ -1128,11 +1137,84 @@ int fmx_device_of(const fmx_index *idx) {
     return (idx && idx->d_blob) ? idx->device : -1;
 }
 
+// work of one level = strings x (sigma - 1) rank pairs, most of them of absent characters: bounded, so that a large
+// alphabet (sigma up to 32,767) does not spend tens of seconds on a level that is thrown away in the end
+constexpr uint64_t kLevelWorkMax = 1ull << 35;
+
+// The table's deepest level as child lists (fmx_device.hpp: DevIndex.suffix_child_rows): level `depth` + 1 grown from the
+// `n_parents` strings of the deepest hashed level, COMPLETE or not at all — every string of it whose parent has a slot gets an
+// entry, and the lists together with the hashed table stay inside `limit`.  `hashed`: the finished hashed table (geometry and
+// slots).  Only on success do the parents' key words get the places of their lists; a parent that had no slot (dropped for a
+// status) gets one without an interval either way, which answers nothing.
+struct ChildLists {
+    void *d_lists = nullptr;  // the row words, and at codes_at the codes
+    size_t codes_at = 0, bytes = 0;
+    uint32_t strings = 0;
+};
+static ChildLists grow_child_lists(const fmx_index *idx, const fmx::DevIndex &hashed, const fmx::SuffixSlot *parents, uint32_t n_parents,
+                                   int depth, fmx::SuffixSlot *table, uint32_t slots, uint64_t limit) {
+    const ChildLists none;
+    const uint64_t hashed_bytes = (uint64_t)slots * sizeof(fmx::SuffixSlot);
+    if (n_parents == 0 || limit < hashed_bytes + 4096) return none;
+    if ((uint64_t)n_parents * (uint64_t)(idx->hdr.wt_sigma - 1) > kLevelWorkMax) return none;
+    // a string takes five bytes at least: more strings than the limit leaves room for, and the level is dropped
+    const uint32_t cap = (uint32_t)std::min<uint64_t>((limit - hashed_bytes) / 5, fmx::kSuffixChildMax);
+    std::vector<void *> temps;
+    auto temp = [&](size_t bytes) -> void * {
+        void *p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+        temps.push_back(p);
+        return p;
+    };
+    auto release = [&]() {
+        (void)hipGetLastError();
+        for (void *p : temps) (void)hipFree(p);
+    };
+    auto *kids = static_cast<fmx::SuffixSlot *>(temp((size_t)cap * sizeof(fmx::SuffixSlot)));
+    auto *d_totals = static_cast<uint32_t *>(temp(64));
+    uint32_t n_kids = 0;
+    if (!kids || !d_totals || hipMemset(d_totals, 0, 64) != hipSuccess ||
+        k_launch_suffix_expand(idx, idx->dev, idx->n_cu, parents, n_parents, depth, 8, kids, d_totals, cap, nullptr) != 0 ||
+        hipMemcpy(&n_kids, d_totals, 4, hipMemcpyDeviceToHost) != hipSuccess || n_kids == 0 || n_kids > cap)
+        return release(), none;
+    auto *placed = static_cast<fmx::SuffixSlot *>(temp((size_t)n_kids * sizeof(fmx::SuffixSlot)));
+    auto *kid_slot = static_cast<uint32_t *>(temp((size_t)n_kids * 4));
+    auto *per_slot = static_cast<uint32_t *>(temp((size_t)slots * 4 * 3));  // + each slot's run in `placed`, + its list's place
+    if (!placed || !kid_slot || !per_slot || hipMemset(per_slot, 0, (size_t)slots * 4 * 3) != hipSuccess) return release(), none;
+    uint32_t *run = per_slot + slots, *first = run + slots;
+    uint32_t totals[2] = {0, 0};  // strings that have a parent's slot, entries of all lists
+    if (k_launch_suffix_child_parents(idx, hashed, kids, n_kids, depth + 1, table, kid_slot, per_slot, nullptr) != 0 ||
+        k_launch_suffix_child_scan(idx, per_slot, run, slots, d_totals, nullptr) != 0 ||
+        k_launch_suffix_child_place(idx, kids, n_kids, kid_slot, run, placed, nullptr) != 0 ||
+        k_launch_suffix_child_sort(idx, slots, per_slot, run, placed, first, nullptr) != 0 ||
+        k_launch_suffix_child_scan(idx, first, first, slots, d_totals + 1, nullptr) != 0 ||
+        hipMemcpy(totals, d_totals, 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return release(), none;
+    if (totals[0] == 0 || totals[0] > n_kids || totals[1] <= totals[0] || totals[1] > fmx::kSuffixChildMax) return release(), none;
+    ChildLists lists;
+    lists.codes_at = (size_t)totals[1] * 4;
+    lists.bytes = (lists.codes_at + totals[1] + fmx::kSuffixChildPad + 15) & ~(size_t)15;
+    lists.strings = totals[0];
+    if (hashed_bytes + lists.bytes > limit) return release(), none;
+    if (hipMalloc(&lists.d_lists, lists.bytes) != hipSuccess) return release(), none;
+    if (hipMemset(lists.d_lists, 0, lists.bytes) != hipSuccess ||
+        k_launch_suffix_child_write(idx, slots, per_slot, run, placed, first, table, static_cast<uint32_t *>(lists.d_lists),
+                                    static_cast<uint8_t *>(lists.d_lists) + lists.codes_at, nullptr) != 0 ||
+        hipStreamSynchronize(nullptr) != hipSuccess) {
+        // (slots that already carry a place are then no longer found — their key words differ — and their strings take the loop)
+        (void)hipFree(lists.d_lists);
+        return release(), none;
+    }
+    release();
+    return lists;
+}
+
 // The suffix table of a resident FM-index (fmx_device.hpp): grown level by level on the device — the strings of 2, 3, ... codes
 // that occur in the text, each with its SA interval — and ALL levels hashed into one table of 16-byte slots (a pattern shorter
 // than the deepest level still finds its whole search there).  How deep: option `suffix_table_chars` (default 8; at most what
 // a 64-bit key holds: 8 codes of 8 bits, 4 of 16), cut where the table would pass its size limit = the smaller of the budget
-// `suffix_table_mb` and 1 / `suffix_table_image_fraction` of the image (default an eighth).  Not having one is never an error.
+// `suffix_table_mb` and 1 / `suffix_table_image_fraction` of the image (default an eighth) — and then, where the level that did
+// not fit as slots fits the same limit as child lists (grow_child_lists), one character deeper.  Not having one is never an error.
 static void build_suffix_table(fmx_index *idx) {
     if (idx->d_suffix_table) {
         (void)hipFree(idx->d_suffix_table);
@@ -1143,6 +1225,12 @@ static void build_suffix_table(fmx_index *idx) {
         (void)hipFree(idx->d_suffix_order1);
         idx->d_suffix_order1 = nullptr;
     }
+    if (idx->d_suffix_children) {
+        (void)hipFree(idx->d_suffix_children);
+        idx->d_suffix_children = nullptr;
+    }
+    idx->dev.suffix_child_rows = nullptr;
+    idx->dev.suffix_child_codes = nullptr;
     idx->suffix_table_strings = idx->suffix_table_deepest = 0;
     idx->dev.suffix_table = nullptr;
     idx->dev.suffix_order1 = nullptr;
@@ -1196,13 +1284,11 @@ static void build_suffix_table(fmx_index *idx) {
         cleanup();
         return;
     }
-    // work of one level = strings x (sigma - 1) rank pairs, most of them of absent characters: bounded, so that a large
-    // alphabet (sigma up to 32,767) does not spend tens of seconds on a level that is thrown away in the end
-    constexpr uint64_t kLevelWorkMax = 1ull << 35;
     uint32_t begin[10] = {0};  // strings of `len` codes: all[begin[len] .. begin[len + 1])
     const fmx::SuffixSlot *prev = level1;
     uint32_t total = 0;
     int chars = 1;
+    bool too_large = false;  // the growth stopped at a level that exists and does not fit as hashed slots
     while (chars < max_chars) {
         if ((uint64_t)n_prev * (uint64_t)(idx->hdr.wt_sigma - 1) > kLevelWorkMax) break;
         const uint32_t room = cap - total;
@@ -1215,7 +1301,10 @@ static void build_suffix_table(fmx_index *idx) {
             return;
         }
         // (the next level does not fit, or its table would pass the limit: the levels so far are the table)
-        if (n_next == 0 || n_next > room || slots_for((uint64_t)total + n_next) * sizeof(fmx::SuffixSlot) > limit) break;
+        if (n_next == 0 || n_next > room || slots_for((uint64_t)total + n_next) * sizeof(fmx::SuffixSlot) > limit) {
+            too_large = n_next != 0;
+            break;
+        }
         ++chars;
         begin[chars] = total;
         prev = all + total;
@@ -1249,13 +1338,22 @@ static void build_suffix_table(fmx_index *idx) {
         cleanup();
         return;
     }
+    // One more level, complete, as child lists — where it exists, the hashed form of it passed the limit and this form does not
+    geometry.suffix_table = static_cast<const fmx::SuffixSlot *>(d_slots);
+    ChildLists lists;
+    if (too_large && chars >= 2 && chars + 1 <= max_chars && key_bits == 8 && chars * key_bits <= fmx::kSuffixChildShift)
+        lists = grow_child_lists(idx, geometry, all + begin[chars], begin[chars + 1] - begin[chars], chars,
+                                 static_cast<fmx::SuffixSlot *>(d_slots), slots, limit);
     cleanup();
     idx->d_suffix_table = d_slots;
-    idx->suffix_table_bytes = (size_t)slots * sizeof(fmx::SuffixSlot);
-    idx->suffix_table_strings = total;
-    idx->suffix_table_deepest = begin[chars + 1] - begin[chars];
+    idx->suffix_table_bytes = (size_t)slots * sizeof(fmx::SuffixSlot) + lists.bytes;
+    idx->suffix_table_strings = total + lists.strings;
+    idx->suffix_table_deepest = lists.d_lists ? lists.strings : begin[chars + 1] - begin[chars];
+    idx->d_suffix_children = lists.d_lists;
     idx->dev.suffix_table = static_cast<const fmx::SuffixSlot *>(d_slots);
-    idx->dev.suffix_chars = chars;
+    idx->dev.suffix_chars = lists.d_lists ? chars + 1 : chars;
+    idx->dev.suffix_child_rows = static_cast<const uint32_t *>(lists.d_lists);
+    idx->dev.suffix_child_codes = lists.d_lists ? static_cast<const uint8_t *>(lists.d_lists) + lists.codes_at : nullptr;
     idx->dev.suffix_shift = geometry.suffix_shift;
     idx->dev.suffix_mask = slots - 1;
     // order-1 statistics of the two-character strings for the plan's sort key (small alphabets; not having them is no error)

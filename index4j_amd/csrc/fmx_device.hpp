@@ -83,6 +83,14 @@ struct DevIndex {
     int32_t suffix_key_bits;
     uint32_t suffix_shift;  // group of a key = (its hashed bits * kSuffixHashMul) >> suffix_shift (fm_suffix_home)
     uint32_t suffix_mask;   // slots - 1 (slots: a power of two, >= 1024)
+    // Child lists (nullptr: none — every level is hashed): the table's DEEPEST level, the strings of `suffix_chars` codes, where
+    // a hashed level of that depth would pass the size limit and this form does not.  A string X of suffix_chars codes is one of
+    // the hashed level below, P = X without its last character, with one code appended, and the X of one P lie side by side
+    // inside P's rows: entry = {code (1 byte), first row (4 bytes)}, the entries of one P sorted by code in consecutive places of
+    // both arrays, behind them a terminator {0, the last child's end}.  An entry's end is the next entry's row (fm_suffix_child_*
+    // below); P's slot carries (place of its first entry + 1) in bits 40 .. 63 of its key word.
+    const uint32_t *suffix_child_rows = nullptr;
+    const uint8_t *suffix_child_codes = nullptr;
     // Order-1 statistics of the table's two-character strings (nullptr: none — alphabets above kOrder1MaxSigma codes): entry
     // [x * wt_sigma + y] = {where the rows of "xy" start inside x's rows, and how much of them they take} as fractions
     // ((s(xy) - C[x]) / n_x, |xy| / n_x; {0, 0}: "xy" does not occur).  k_plan_codes stages it in LDS and estimates from it
@@ -149,12 +157,14 @@ FMX_HD int fmx_popcll(uint64_t v) { return __builtin_popcountll(v); }
 // the texture addresser, the scarce resource of these kernels)
 #if defined(__HIPCC__)
 #define FMX_NO_UNROLL _Pragma("clang loop unroll(disable)")
+#define FMX_UNROLL _Pragma("clang loop unroll(full)")
 #define FMX_OPAQUE32(v) asm volatile("" : "+v"(v))
 #define FMX_OPAQUE64(v) asm volatile("" : "+v"(v))
 // pins a 16-byte load: one dwordx4, complete at this point (used to request independent loads together)
 #define FMX_PIN_QUAD(q) asm volatile("" : "+v"((q).x), "+v"((q).y), "+v"((q).z), "+v"((q).w))
 #else
 #define FMX_NO_UNROLL
+#define FMX_UNROLL
 #define FMX_OPAQUE32(v) (void)0
 #define FMX_OPAQUE64(v) (void)0
 #define FMX_PIN_QUAD(q) (void)0
@@ -1803,24 +1813,102 @@ FMX_HD uint32_t fm_suffix_home(const DevIndex &ix, uint64_t key, int len) {
     const uint32_t turn = (uint32_t)(hash >> (ix.suffix_shift - kSuffixGroupLog2)) & (kSuffixGroup - 1);
     return (group * kSuffixGroup + ((uint32_t)low6 ^ turn)) & ix.suffix_mask;
 }
-// A pattern whose trailing `len` codes spell `key`: where the search stands after them, if the table says so.
-// Returns false when the loop has to run from the first character.
-FMX_HD bool fm_suffix_lookup(const DevIndex &ix, uint64_t key, int len, int32_t &start, int32_t &end, int32_t &back) {
+// fm_suffix_find: the slot of a hashed string — `len` codes, below suffix_chars where the deepest level is child lists — and
+// its 16 bytes; kSuffixNoSlot: not in the table.  With child lists present the key word's bits 40 .. 63 are not the string's.
+constexpr uint32_t kSuffixNoSlot = ~0u;
+constexpr int kSuffixChildShift = 40;  // child lists stand on a hashed level of at most 5 codes of 8 bits
+constexpr uint64_t kSuffixChildKeyMask = (1ull << kSuffixChildShift) - 1ull;
+constexpr uint32_t kSuffixChildMax = 0xfffff0u;     // entries of all lists together (place + 1 fits 24 bits and is not all ones)
+constexpr uint32_t kSuffixChildHole = 0x80000000u;  // a row word's bit 31: no string, only the end of the entry in front
+constexpr uint32_t kSuffixChildPad = 32;            // bytes behind the codes: a lookup reads 16 at a time
+FMX_HD uint32_t fm_suffix_find(const DevIndex &ix, uint64_t key, int len, Quad &q) {
+    const uint64_t keep = ix.suffix_child_rows ? kSuffixChildKeyMask : ~0ull;
     uint32_t h = fm_suffix_home(ix, key, len);
-    Quad q = ld_quad(ix.suffix_table + h);  // the home slot answers nearly every lookup (the table is at most 0.7 full)
+    q = ld_quad(ix.suffix_table + h);  // the home slot answers nearly every lookup (the table is at most 0.7 full)
     FMX_PIN_QUAD(q);
     uint64_t k = (uint64_t)q.x | ((uint64_t)q.y << 32);
     // (ends at a free slot: the table always has free slots in every column; the bound is for a damaged table)
-    for (uint32_t probe = 0; k != key && k != kSuffixEmpty && probe < ix.suffix_mask / kSuffixGroup; ++probe) {
+    for (uint32_t probe = 0; (k & keep) != key && k != kSuffixEmpty && probe < ix.suffix_mask / kSuffixGroup; ++probe) {
         h = (h + kSuffixGroup) & ix.suffix_mask;
         q = ld_quad(ix.suffix_table + h);
         k = (uint64_t)q.x | ((uint64_t)q.y << 32);
     }
-    if (k != key) return false;
+    return (k != kSuffixEmpty && (k & keep) == key) ? h : kSuffixNoSlot;
+}
+// A string of suffix_chars codes from the child lists: the slot of P (all codes but the last), the codes of P's entries —
+// sorted, so the first one that is not below the last code decides —, then the entry's row and the next entry's.
+FMX_HD bool fm_suffix_child_lookup(const DevIndex &ix, uint64_t key, int len, int32_t &start, int32_t &end, int32_t &back) {
+    const uint32_t c = (uint32_t)key & 0xffu;
+    Quad q;
+    if (c == 0 || fm_suffix_find(ix, key >> 8, len - 1, q) == kSuffixNoSlot) return false;
+    uint32_t at = q.y >> (kSuffixChildShift - 32);
+    if (at == 0) return false;  // no string of suffix_chars codes starts with P
+    --at;
+    // (a parent has at most 255 children and a hole behind each: 32 runs of 16 codes; the bound is for a damaged table)
+    for (int run = 0; run < 33; ++run, at += 16) {
+        const Quad w = ld_quad(ix.suffix_child_codes + at);
+        const uint32_t words[4] = {w.x, w.y, w.z, w.w};
+        int t = 16;
+        uint32_t code = 0;
+        FMX_UNROLL
+        for (int i = 15; i >= 0; --i) {
+            const uint32_t b = (words[i >> 2] >> ((i & 3) * 8)) & 0xffu;
+            if (b == 0 || b >= c) {
+                t = i;
+                code = b;
+            }
+        }
+        if (t == 16) continue;
+        if (code != c) return false;
+        const uint32_t row = ix.suffix_child_rows[at + t], next = ix.suffix_child_rows[at + t + 1];
+        if (row & kSuffixChildHole) return false;
+        start = (int32_t)row;
+        end = (int32_t)(next & ~kSuffixChildHole);
+        back = len - 1;
+        return true;
+    }
+    return false;
+}
+// A pattern whose trailing `len` codes spell `key`: where the search stands after them, if the table says so.
+// Returns false when the loop has to run from the first character.
+FMX_HD bool fm_suffix_lookup(const DevIndex &ix, uint64_t key, int len, int32_t &start, int32_t &end, int32_t &back) {
+    if (ix.suffix_child_rows && len == ix.suffix_chars) return fm_suffix_child_lookup(ix, key, len, start, end, back);
+    Quad q;
+    // (a slot with an empty interval is no string of the table: it carries the child lists of a string that was dropped)
+    if (fm_suffix_find(ix, key, len, q) == kSuffixNoSlot || q.z >= q.w) return false;
     start = (int32_t)q.z;
     end = (int32_t)q.w;
     back = len - 1;
     return true;
+}
+// Growing the child lists (k_suffix_child_* in fmx_kernels.hip; the host tests run the same three functions): the strings of
+// suffix_chars codes that share P, `run[0 .. n)` as fm_suffix_extend made them, are sorted by their last code; a list has an
+// entry per string, a HOLE behind a string whose end is not the next string's first row (a string between them was dropped
+// for a status: what looks for it must run the loop), and the terminator.
+FMX_HD void fm_suffix_child_sort(SuffixSlot *run, uint32_t n) {
+    for (uint32_t i = 1; i < n; ++i) {
+        const SuffixSlot x = run[i];
+        uint32_t j = i;
+        for (; j > 0 && (run[j - 1].key & 0xffu) > (x.key & 0xffu); --j) run[j] = run[j - 1];
+        run[j] = x;
+    }
+}
+FMX_HD uint32_t fm_suffix_child_entries(const SuffixSlot *run, uint32_t n) {
+    uint32_t entries = n + 1;
+    for (uint32_t i = 0; i + 1 < n; ++i) entries += run[i].end != run[i + 1].start;
+    return entries;
+}
+FMX_HD void fm_suffix_child_write(const SuffixSlot *run, uint32_t n, uint32_t at, uint32_t *rows, uint8_t *codes) {
+    for (uint32_t i = 0; i < n; ++i) {
+        codes[at] = (uint8_t)(run[i].key & 0xffu);
+        rows[at++] = run[i].start;
+        if (i + 1 < n && run[i].end != run[i + 1].start) {
+            codes[at] = (uint8_t)(run[i].key & 0xffu);
+            rows[at++] = run[i].end | kSuffixChildHole;
+        }
+    }
+    codes[at] = 0;
+    rows[at] = run[n - 1].end;
 }
 // the key of a pattern's last `len` characters from its codes (code_at(0) = the last character); false: a code of 0
 template <class CodeAt>

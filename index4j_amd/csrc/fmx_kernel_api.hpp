@@ -12,6 +12,17 @@ int launch_suffix_expand(const fmx::DevIndex &ix, int n_cu, const fmx::SuffixSlo
 int launch_suffix_insert(const fmx::DevIndex &geometry, const fmx::SuffixSlot *in, uint32_t n_in, int len, fmx::SuffixSlot *slots,
                          hipStream_t st);
 int launch_suffix_order1(const fmx::DevIndex &ix, float *out, hipStream_t st);
+// ... its deepest level as child lists: parents' slots and counts, exclusive scan (one workgroup), runs per parent, sorted runs and
+// their entries, the lists themselves
+int launch_suffix_child_parents(const fmx::DevIndex &hashed, const fmx::SuffixSlot *kids, uint32_t n_kids, int len,
+                                fmx::SuffixSlot *table, uint32_t *kid_slot, uint32_t *per_slot, hipStream_t st);
+int launch_suffix_child_scan(const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total, hipStream_t st);
+int launch_suffix_child_place(const fmx::SuffixSlot *kids, uint32_t n_kids, const uint32_t *kid_slot, uint32_t *cursor,
+                              fmx::SuffixSlot *placed, hipStream_t st);
+int launch_suffix_child_sort(uint32_t slots, const uint32_t *per_slot, const uint32_t *run_end, fmx::SuffixSlot *placed,
+                             uint32_t *entries, hipStream_t st);
+int launch_suffix_child_write(uint32_t slots, const uint32_t *per_slot, const uint32_t *run_end, const fmx::SuffixSlot *placed,
+                              const uint32_t *first, fmx::SuffixSlot *table, uint32_t *rows, uint8_t *codes, hipStream_t st);
 int launch_win_build(const fmx::DevIndex &ix, int n_cu, uint32_t n_win, fmx::Quad *out, uint32_t *others, hipStream_t st);
 int launch_win_other(const fmx::DevIndex &ix, int n_cu, uint32_t n_win, fmx::Quad *cells, const uint32_t *first, uint16_t *entries,
                      uint32_t *open_entries, int entry4, uint64_t *full, uint32_t full_cap, hipStream_t st);

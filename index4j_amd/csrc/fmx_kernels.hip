@@ -729,7 +729,7 @@ __device__ __forceinline__ void count_one_lean(const CountLeanHot &H, CountLeanT
                 q = ld_quad(table + h);
                 k = (uint64_t)q.x | ((uint64_t)q.y << 32);
             }
-            if (k == key) {
+            if (k == key && q.z < q.w) {  // (an empty interval: a slot that only carries child lists — fm_suffix_lookup)
                 start = (int32_t)q.z;
                 end = (int32_t)q.w;
                 back = len - 1;
@@ -930,6 +930,135 @@ int launch_suffix_expand(const DevIndex &ix, int n_cu, const SuffixSlot *in, uin
 int launch_suffix_insert(const DevIndex &geometry, const SuffixSlot *in, uint32_t n_in, int len, SuffixSlot *slots, hipStream_t st) {
     if (n_in == 0) return 0;
     hipLaunchKernelGGL(k_suffix_insert, dim3((n_in + 255) / 256), dim3(256), 0, st, geometry, in, n_in, len, slots);
+    return (int)hipGetLastError();
+}
+
+// ---- the deepest level as child lists (fmx_device.hpp: DevIndex.suffix_child_rows).  `kids`: the strings of len codes as
+// k_suffix_expand made them; ix carries the finished hashed table of the levels below (no child pointers yet: keys as inserted).
+// per_slot / first / entries: one word per slot of the hashed table. ----
+// the slot of every string's parent (the string without its last code), and how many strings each slot has
+// A parent that was dropped for a status (its own search raises it; its children's need not) has no slot: it gets one here that
+// holds NO interval (start = end = 0: fm_suffix_lookup does not answer from such a slot), only to carry its list.
+__global__ __launch_bounds__(256) void k_suffix_child_parents(DevIndex ix, const SuffixSlot *__restrict__ kids, uint32_t n_kids, int len,
+                                                              SuffixSlot *table, uint32_t *__restrict__ kid_slot,
+                                                              uint32_t *__restrict__ per_slot) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_kids) return;
+    Quad q;
+    const uint64_t parent = kids[i].key >> 8;
+    uint32_t h = fm_suffix_find(ix, parent, len - 1, q);
+    if (h == kSuffixNoSlot) {
+        // (the first lane to claim a free slot of the probe sequence makes it the parent's; its siblings meet the key there)
+        uint32_t at = fm_suffix_home(ix, parent, len - 1);
+        for (uint32_t probe = 0; probe <= ix.suffix_mask / kSuffixGroup; ++probe, at = (at + kSuffixGroup) & ix.suffix_mask) {
+            const unsigned long long was = atomicCAS(reinterpret_cast<unsigned long long *>(&table[at].key),
+                                                     (unsigned long long)kSuffixEmpty, (unsigned long long)parent);
+            if (was == (unsigned long long)kSuffixEmpty) {
+                table[at].start = 0;
+                table[at].end = 0;
+            }
+            if (was == (unsigned long long)kSuffixEmpty || was == (unsigned long long)parent) {
+                h = at;
+                break;
+            }
+        }
+    }
+    kid_slot[i] = h;
+    if (h != kSuffixNoSlot) atomicAdd(&per_slot[h], 1u);
+}
+// out[i] = in[0] + .. + in[i - 1], *total = the sum of all n; ONE workgroup of 1,024 lanes (a one-off step of the build; in == out is fine)
+__global__ __launch_bounds__(1024) void k_suffix_child_scan(const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *__restrict__ total) {
+    __shared__ uint32_t part[1024];
+    const uint32_t each = (n + 1023u) / 1024u;
+    const uint32_t lo = min(n, threadIdx.x * each), hi = min(n, lo + each);
+    uint32_t sum = 0;
+    for (uint32_t j = lo; j < hi; ++j) sum += in[j];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (int t = 0; t < 1024; ++t) {
+            const uint32_t v = part[t];
+            part[t] = run;
+            run += v;
+        }
+        *total = run;
+    }
+    __syncthreads();
+    uint32_t run = part[threadIdx.x];
+    for (uint32_t j = lo; j < hi; ++j) {
+        const uint32_t v = in[j];
+        out[j] = run;
+        run += v;
+    }
+}
+// every string into its parent's run of `placed` (cursor: first[] on entry, each slot's END afterwards)
+__global__ __launch_bounds__(256) void k_suffix_child_place(const SuffixSlot *__restrict__ kids, uint32_t n_kids,
+                                                            const uint32_t *__restrict__ kid_slot, uint32_t *__restrict__ cursor,
+                                                            SuffixSlot *__restrict__ placed) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_kids) return;
+    const uint32_t h = kid_slot[i];
+    if (h == kSuffixNoSlot) return;
+    placed[atomicAdd(&cursor[h], 1u)] = kids[i];
+}
+// a lane per slot: its run sorted by code, and the entries its list takes (0: no children)
+__global__ __launch_bounds__(256) void k_suffix_child_sort(uint32_t slots, const uint32_t *__restrict__ per_slot,
+                                                           const uint32_t *__restrict__ run_end, SuffixSlot *__restrict__ placed,
+                                                           uint32_t *__restrict__ entries) {
+    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= slots) return;
+    const uint32_t n = per_slot[h];
+    uint32_t e = 0;
+    if (n != 0) {
+        SuffixSlot *run = placed + (run_end[h] - n);
+        fm_suffix_child_sort(run, n);
+        e = fm_suffix_child_entries(run, n);
+    }
+    entries[h] = e;
+}
+// a lane per slot: its list at place first[h], and that place + 1 into the slot's key word
+__global__ __launch_bounds__(256) void k_suffix_child_write(uint32_t slots, const uint32_t *__restrict__ per_slot,
+                                                            const uint32_t *__restrict__ run_end, const SuffixSlot *__restrict__ placed,
+                                                            const uint32_t *__restrict__ first, SuffixSlot *__restrict__ table,
+                                                            uint32_t *__restrict__ rows, uint8_t *__restrict__ codes) {
+    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= slots) return;
+    const uint32_t n = per_slot[h];
+    if (n == 0) return;
+    fm_suffix_child_write(placed + (run_end[h] - n), n, first[h], rows, codes);
+    table[h].key |= (uint64_t)(first[h] + 1u) << kSuffixChildShift;
+}
+int launch_suffix_child_parents(const DevIndex &hashed, const SuffixSlot *kids, uint32_t n_kids, int len, SuffixSlot *table,
+                                uint32_t *kid_slot, uint32_t *per_slot, hipStream_t st) {
+    if (n_kids == 0) return 0;
+    DevIndex plain = hashed;
+    plain.sb_cache = nullptr;
+    plain.suffix_child_rows = nullptr;
+    plain.suffix_child_codes = nullptr;
+    hipLaunchKernelGGL(k_suffix_child_parents, dim3((n_kids + 255) / 256), dim3(256), 0, st, plain, kids, n_kids, len, table, kid_slot,
+                       per_slot);
+    return (int)hipGetLastError();
+}
+int launch_suffix_child_scan(const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total, hipStream_t st) {
+    hipLaunchKernelGGL(k_suffix_child_scan, dim3(1), dim3(1024), 0, st, in, out, n, total);
+    return (int)hipGetLastError();
+}
+int launch_suffix_child_place(const SuffixSlot *kids, uint32_t n_kids, const uint32_t *kid_slot, uint32_t *cursor, SuffixSlot *placed,
+                              hipStream_t st) {
+    if (n_kids == 0) return 0;
+    hipLaunchKernelGGL(k_suffix_child_place, dim3((n_kids + 255) / 256), dim3(256), 0, st, kids, n_kids, kid_slot, cursor, placed);
+    return (int)hipGetLastError();
+}
+int launch_suffix_child_sort(uint32_t slots, const uint32_t *per_slot, const uint32_t *run_end, SuffixSlot *placed, uint32_t *entries,
+                             hipStream_t st) {
+    hipLaunchKernelGGL(k_suffix_child_sort, dim3((slots + 255) / 256), dim3(256), 0, st, slots, per_slot, run_end, placed, entries);
+    return (int)hipGetLastError();
+}
+int launch_suffix_child_write(uint32_t slots, const uint32_t *per_slot, const uint32_t *run_end, const SuffixSlot *placed,
+                              const uint32_t *first, SuffixSlot *table, uint32_t *rows, uint8_t *codes, hipStream_t st) {
+    hipLaunchKernelGGL(k_suffix_child_write, dim3((slots + 255) / 256), dim3(256), 0, st, slots, per_slot, run_end, placed, first, table,
+                       rows, codes);
     return (int)hipGetLastError();
 }
 
@@ -2407,7 +2536,7 @@ int launch_count(const DevIndex &ix, int n_cu, const uint16_t *pat, const int32_
 #if !FMX_COMPACT
     // a planned batch over an expanded image whose superblock headers fit LDS: the lean kernel (option "count_lean" = 0: A/B)
     if (mode == 1 && options().count_lean && pl.redo_list && pl.redo_count && ix.n_sb <= kSbCacheMax && ix.n_sb <= ix.sb_cache_limit &&
-        (!ix_launch.suffix_table || pl.code_bits == ix.suffix_key_bits)) {
+        (!ix_launch.suffix_table || (pl.code_bits == ix.suffix_key_bits && !ix.suffix_child_rows))) {  // (its lookup knows hashed levels only)
         CountLeanArgs a;
         a.hot.base = ix.base;
         a.hot.sbc = ix.sbc;

@@ -335,6 +335,46 @@ int fmx_field_values_class_batch(const fmx_index *idx, const uint16_t *alt, cons
                                  int32_t max_len, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
                                  int32_t *occurrences, int32_t *status);
 
+/* THE VALUES THAT FOLLOW A PATTERN, WHERE THE LINE MATCHES A QUERY (grep terminating | grep -o 'blk_[^ ]*' | sort | uniq -c; the
+ * "count by" of a log search, which always carries a filter and a time window) — fmx_field_values_batch over the hits that lie in
+ * given lines: the two packed stages over ONE batch of the filter terms and the value patterns + fmx_query_lines_of_hits_dev over
+ * the terms' hits (no limit) + fmx_hits_in_lines_dev over the value patterns' hits (below: the keep rule) + the values stages over
+ * the kept hits.  Nothing in between comes down: neither the lines nor the hits.
+ * The n VALUE PATTERNS are (pat, pat_off, n); the n_terms TERMS (term_pat, term_off, n_terms) are cut into q queries by query_off /
+ * term_kind exactly as in fmx_match_query_batch, whose definitions hold unchanged: a query of NONE terms only has no lines, so a
+ * value pattern that asks for it has no values; a term with FMX_ST_TOO_MANY_RANGES has no hits, as in fmx_match_query_class_batch.
+ * where_of = n ints, each -1 .. q - 1: a hit of pattern i counts iff its line — the line of its FIRST character — lies in
+ * [line_lo, line_hi) and, for where_of[i] >= 0, belongs to query where_of[i]; several patterns may share a query.  A window of 0,
+ * INT32_MAX does not filter.  A line table (fmx_line_table_build) is needed only if some where_of[i] >= 0 or a window is given;
+ * with every where_of[i] < 0 and no window the answer is bit for bit fmx_field_values_batch's.
+ * stop, n_stop, max_len, val_off, *counts, *text_off, *chars and status: fmx_field_values_batch's, the ONE allocation included (free
+ * *counts only; all three NULL when there are no values and on every failure).  occurrences[i] (nullable) stays the pattern's
+ * count in the WHOLE text; kept[i] (nullable, n ints) is the hits that passed: the counts of pattern i's values add up to kept[i]
+ * (it is filled on an index built without extraction too, where every status is FMX_ST_NOT_ENABLED and there are no values).
+ * term_status (nullable, n_terms ints) carries the terms' statuses, as fmx_match_query_batch's status does.
+ * Device scratch: 4 bytes per hit of the merged batch, the query stage's over the TERMS' hits, the filter's 8 bytes per hit, and the
+ * values stage's about 170 + 2 * max_len bytes per KEPT hit only.  One more 8-byte-per-pattern read and wait than
+ * fmx_field_values_batch: the kept hits' offsets come down before the values stage is sized.
+ * FMX_E_ARG for null or negative arguments, line_lo > line_hi, a where_of outside -1 .. q - 1, query_off / term_kind that
+ * fmx_match_query_batch refuses, offsets that decrease, max_len or n_stop outside their intervals, an index without a line table
+ * when the call filters (the error names fmx_line_table_build), more than 2^31 - 1 hits in the merged batch, a SuffixArray,
+ * RrrVector or stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident; FMX_E_NOMEM as
+ * fmx_field_values_batch.  n == 0: FMX_OK, val_off[0] = 0, nothing is searched and term_status is zeroed. */
+int fmx_field_values_where_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *term_pat,
+                                 const int32_t *term_off, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                 const int32_t *where_of, int32_t line_lo, int32_t line_hi, const uint16_t *stop, int32_t n_stop,
+                                 int32_t max_len, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
+                                 int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *term_status);
+/* ... with class patterns as value patterns (alt, pos_off, n_pos, pat_off, n) and as terms (term_alt, term_pos_off, term_n_pos,
+ * term_off, n_terms): the three packed arrays of fmx_count_class_batch, twice; one max_ranges for both. */
+int fmx_field_values_where_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                       int32_t n, const uint16_t *term_alt, const int32_t *term_pos_off, int32_t term_n_pos,
+                                       const int32_t *term_off, int32_t n_terms, int32_t max_ranges, const int32_t *query_off,
+                                       const uint8_t *term_kind, int32_t q, const int32_t *where_of, int32_t line_lo, int32_t line_hi,
+                                       const uint16_t *stop, int32_t n_stop, int32_t max_len, int64_t *val_off, int32_t **counts,
+                                       int64_t **text_off, uint16_t **chars, int32_t *occurrences, int32_t *kept, int32_t *status,
+                                       int32_t *term_status);
+
 /* THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY (extract, FM:564-608, batched) — the host form of
  * fmx_extract_packed_offsets_dev + fmx_extract_packed_fill_dev (below: the layout, the statuses, how the work is cut).
  * host buffers, synchronous: text_off = n + 1 int64 (out), text_off[0] = 0; *chars = text_off[n] UTF-16 code units owned by the
@@ -350,7 +390,7 @@ int fmx_extract_packed_batch(const fmx_index *idx, const int32_t *start, const i
  * and nothing in between comes down.  An id that is no line gets FMX_ST_POS_NEGATIVE and length 0.  FMX_E_ARG without a table. */
 int fmx_line_text_batch(const fmx_index *idx, const int32_t *lines, int32_t n, int64_t *text_off, uint16_t **chars, int32_t *status);
 /* how many ranges the calling thread's last fmx_extract_packed_batch / fmx_line_text_batch — or windows its last
- * fmx_field_values_batch / fmx_field_values_class_batch — ran literally (the redo list below); -1 before the first such call.  0 on
+ * fmx_field_values_batch / fmx_field_values_class_batch or their _where forms — ran literally (the redo list below); -1 before the first such call.  0 on
  * an index without quirk rows. */
 int64_t fmx_extract_packed_last_redo(void);
 
@@ -600,6 +640,32 @@ int fmx_values_of_hits_dev(const fmx_index *idx, int32_t n, const int32_t *term_
                            int64_t *d_text_off, int32_t *d_status, void *d_ws, size_t ws_bytes, void *stream);
 int fmx_values_fill_dev(const fmx_index *idx, int64_t n_groups, const int64_t *d_text_off, uint16_t *d_chars, const void *d_ws,
                         size_t ws_bytes, void *stream);
+/* THE HITS THAT LIE IN GIVEN LINES over device pointers: packed hits (d_hit_off, d_locs) of n patterns -> the same packed format
+ * (d_kept_off, d_kept_locs) with the hits that pass, so that the line, sequence and values stages run unchanged on the filtered
+ * hits.  (d_line_off, d_lines) are the packed lines of q queries, ascending and distinct per query: what fmx_lines_of_hits_dev,
+ * fmx_query_lines_of_hits_dev and fmx_sequence_lines_of_hits_dev leave without a limit.  where_of (n ints, -1 .. q - 1) is a HOST
+ * array: validated, and copied into d_ws before the call returns.
+ * THE KEEP RULE: a hit h of pattern i is kept iff L = the line of h (a hit belongs to the line of its first character:
+ * fmx_lines_of_hits_dev's rule) satisfies line_lo <= L < line_hi, and where_of[i] < 0 or L occurs in
+ * d_lines[d_line_off[w] .. d_line_off[w + 1]), w = where_of[i].  A window of 0, INT32_MAX does not filter.
+ * d_kept_off (n + 1 int64): d_kept_off[0] = 0, d_kept_off[i + 1] - d_kept_off[i] = the kept hits of pattern i.  d_kept_locs (room
+ * for n_hits ints, not overlapping d_locs): the kept hits IN THE ORDER THEY HAD — the compaction is stable, the hits of a pattern
+ * stay in SA-row order; entries from d_kept_off[n] on keep the caller's values.  d_hit_off[0] may be non-zero: the hits of the
+ * call are the slots [d_hit_off[0], min(d_hit_off[n], n_hits)) of d_locs, those in front and behind are ignored — one packed block
+ * may hold filter terms and value patterns side by side (hand over d_hit_off + the number of terms).
+ * The stages hand lanes to hits: a flag per slot (the hit's pattern from the hit tiles, its line over the fences staged in LDS,
+ * ONE binary search in the query's line list), rocPRIM's exclusive scan of the flags, a scatter; a lane per pattern reads
+ * d_kept_off off the scan.  Integers only, no atomics: the result does not depend on scheduling.  Asynchronous on `stream`,
+ * nothing is synchronised or allocated.  d_ws: at least fmx_hits_in_lines_scratch_bytes(n, n_hits) bytes (8 per slot, 4 per
+ * pattern, rocPRIM's temporary storage; 0 for an empty call or n_hits beyond 2^31 - 1).  The grids are fmx_hit_lines_geometry's.
+ * n == 0 or n_hits == 0: the n + 1 offsets are zeroed and nothing else is written.  FMX_E_ARG for null or negative arguments,
+ * line_lo > line_hi, a where_of outside -1 .. q - 1, n_hits > 2^31 - 1, an index without a line table (the error names
+ * fmx_line_table_build), a workspace that is too small (nothing is launched, nothing is written), a SuffixArray / RrrVector /
+ * stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident. */
+size_t fmx_hits_in_lines_scratch_bytes(int32_t n, int64_t n_hits);
+int fmx_hits_in_lines_dev(const fmx_index *idx, int32_t n, const int32_t *where_of, int32_t q, const int64_t *d_line_off, const int32_t *d_lines,
+                          int32_t line_lo, int32_t line_hi, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits,
+                          int64_t *d_kept_off, int32_t *d_kept_locs, void *d_ws, size_t ws_bytes, void *stream);
 /* CLASS PATTERNS over device pointers (d_alt, d_pos_off, d_pat_off: the three packed arrays of fmx_count_class_batch, in device
  * memory and trusted as the literal device forms trust theirs); asynchronous on `stream`, nothing is allocated or synchronised.
  * THE SEARCH keeps, per pattern, a frontier of SA ranges: the last position gives {C[c], C[c + 1]} of each of its codes, every

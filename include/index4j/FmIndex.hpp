@@ -441,6 +441,70 @@ public:
         }
         return out;
     }
+    // ... only within the lines of a query (fmx.h "THE VALUES THAT FOLLOW A PATTERN, WHERE THE LINE MATCHES A QUERY": grep terminating |
+    // grep -o 'blk_[^ ]*' | sort | uniq -c; needs buildLineTable unless nothing filters).  A hit of pattern i counts iff its line —
+    // the line of its first character — lies in [lineLo, lineHi) and, for whereOf[i] >= 0, matches queries[whereOf[i]] (matchQuery's
+    // rule; whereOf[i] = -1: the window alone).  occurrences[i] stays the pattern's count in the whole text, kept[i] is the hits
+    // that passed: the counts of the pattern's values add up to it.  termStatus: per term, in the order all, any, none of query 0,
+    // then query 1 ... (not thrown).  fieldValuesWhere: one pattern and one query as (value, count) pairs, statuses thrown.
+    struct FieldValuesWhere : FieldValues {
+        std::vector<int32_t> kept, termStatus;
+    };
+    FieldValuesWhere fieldValuesWhereBatch(const std::vector<std::u16string> &patterns, const std::vector<Query> &queries,
+                                           const std::vector<int32_t> &whereOf, const std::u16string &stop, int maxLen, int32_t lineLo = 0,
+                                           int32_t lineHi = INT32_MAX) const {
+        if (whereOf.size() != patterns.size()) throw std::invalid_argument("whereOf has one entry per pattern");
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        for (const Query &qu : queries) {
+            const std::vector<std::u16string> *groups[3] = {&qu.all, &qu.any, &qu.none};
+            for (int k = 0; k < 3; ++k)
+                for (const std::u16string &t : *groups[k]) {
+                    terms.push_back(t);
+                    kind.push_back((uint8_t)k);
+                }
+            queryOff.push_back((int32_t)terms.size());
+        }
+        std::vector<uint16_t> chars, termChars;
+        std::vector<int32_t> off, termOff;
+        pack(patterns, chars, off);
+        pack(terms, termChars, termOff);
+        FieldValuesWhere out;
+        static_cast<FieldValues &>(out) = emptyFieldValues(patterns.size());
+        out.kept.assign(patterns.size(), 0);
+        out.termStatus.assign(terms.size(), 0);
+        kind.push_back(0);  // (never an empty array)
+        int32_t *counts = nullptr;
+        int64_t *textOff = nullptr;
+        uint16_t *units = nullptr;
+        detail::check(fmx_field_values_where_batch(h_, chars.data(), off.data(), (int32_t)patterns.size(), termChars.data(), termOff.data(),
+                                                   (int32_t)terms.size(), queryOff.data(), kind.data(), (int32_t)queries.size(), whereOf.data(), lineLo,
+                                                   lineHi, reinterpret_cast<const uint16_t *>(stop.data()), (int32_t)stop.size(), maxLen,
+                                                   out.offsets.data(), &counts, &textOff, &units, out.occurrences.data(), out.kept.data(),
+                                                   out.status.data(), out.termStatus.data()),
+                      "fmx_field_values_where_batch");
+        takeFieldValues(out, counts, textOff, units);
+        return out;
+    }
+    std::vector<std::pair<std::u16string, int32_t>> fieldValuesWhere(const std::u16string &pattern, const Query &where,
+                                                                      const std::u16string &stop = u" \t\r\n", int maxLen = 32, int top = 0,
+                                                                      int32_t lineLo = 0, int32_t lineHi = INT32_MAX) const {
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        for (const std::vector<std::u16string> *g : {&where.all, &where.any, &where.none})
+            for (const std::u16string &t : *g)
+                if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const FieldValuesWhere v = fieldValuesWhereBatch({pattern}, {where}, {0}, stop, maxLen, lineLo, lineHi);
+        detail::raise_for_status(v.status[0]);
+        for (int s : v.termStatus) detail::raise_for_status(s);
+        std::vector<std::pair<std::u16string, int32_t>> out;
+        for (size_t g = 0; g < v.counts.size(); ++g) out.emplace_back(v[g], v.counts[g]);
+        if (top > 0) {  // (a stable sort: equal counts keep the order of the values)
+            std::stable_sort(out.begin(), out.end(), [](const auto &a, const auto &b) { return a.second > b.second; });
+            if (out.size() > (size_t)top) out.resize((size_t)top);
+        }
+        return out;
+    }
 
     // the text of ranges and of lines in ONE packed array (fmx.h "THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY"): range / line
     // i is chars[offsets[i] .. offsets[i + 1]) — what extract(start, stop, destination, 0) leaves in destination; memory follows

@@ -1895,6 +1895,8 @@ struct RangeStage {
     int64_t *range_hit_off = nullptr;  // n_ranges + 1: where the hits of each range begin (literal patterns: hit_off itself)
     int64_t *hit_off = nullptr;        // n + 1: where the hits of each pattern begin
     int64_t total = 0;                 // hit_off[n], read once
+    int32_t mark = -1;                 // >= 0: hit_off[mark] comes down with the total, into mark_total (a batch of two parts)
+    int64_t mark_total = 0;
     int32_t *counts = nullptr, *lf_steps = nullptr, *status = nullptr;  // per pattern, where the stage was asked for them
     int64_t *range_off = nullptr;      // class patterns: n + 1, the ranges of each pattern ...
     int32_t *range_status = nullptr;   // ... and, where the caller wants statuses, the walk status of each range (fill_hits folds them)
@@ -1905,6 +1907,7 @@ constexpr int64_t kLocateAllWindow = (int64_t)1 << 24;  // 64 MiB of positions
 
 static int read_hit_total(PackedCall &call, RangeStage &r) {
     HIP_TRY(hipMemcpyAsync(&r.total, r.hit_off + r.n, 8, hipMemcpyDeviceToHost, call.stream.s));
+    if (r.mark >= 0) HIP_TRY(hipMemcpyAsync(&r.mark_total, r.hit_off + r.mark, 8, hipMemcpyDeviceToHost, call.stream.s));
     HIP_TRY(hipStreamSynchronize(call.stream.s));
     return FMX_OK;
 }
@@ -3854,35 +3857,38 @@ struct ValuesShape {
     size_t text_off_at = 0, chars_at = 0;  // inside the result
 };
 }  // namespace
-static int values_down(PackedCall &call, RangeStage &r, const int32_t *term_len, const uint16_t *stop, int32_t n_stop, int32_t max_len,
-                       int64_t *val_off, ValuesShape &shape) {
+// the hits: `total` of n patterns at d_hit_off, their statuses at d_status — the range stage's own, filled here (fill != NULL), or
+// hits that are on the device already (d_ready: what a stage between the fill and this one left)
+static int values_down_hits(PackedCall &call, RangeStage *fill, int32_t n, const int64_t *d_hit_off, const int32_t *d_ready, int64_t total,
+                            int32_t *d_status, const int32_t *term_len, const uint16_t *stop, int32_t n_stop, int32_t max_len, int64_t *val_off,
+                            ValuesShape &shape) {
     const fmx_index *idx = call.blocks.idx;
     Scratch &b = call.blocks;
     const hipStream_t st = call.stream.s;
-    const int32_t n = r.n;
-    int rc = check_values_hits(r.total, max_len);
+    int rc = check_values_hits(total, max_len);
     if (rc) return rc;
     int64_t *d_voff = nullptr, *d_toff = nullptr;
     int32_t *d_locs = nullptr, *d_count = nullptr;
     uint16_t *d_chars = nullptr;
     if ((rc = b.block((size_t)(n + 1) * 8, &d_voff))) return rc;
-    if (!idx->dev.enable_extract || r.total == 0) {
+    if (!idx->dev.enable_extract || total == 0) {
         HIP_TRY(hipMemsetAsync(d_voff, 0, (size_t)(n + 1) * 8, st));
         if (!idx->dev.enable_extract) {
-            const int e = fmx::launch_values_status_all(idx->n_cu, r.status, n, FMX_ST_NOT_ENABLED, st);
+            const int e = fmx::launch_values_status_all(idx->n_cu, d_status, n, FMX_ST_NOT_ENABLED, st);
             if (e) return fail(FMX_E_HIP, std::string("values of hits: ") + hipGetErrorString((hipError_t)e));
         }
     } else {
-        const size_t ws_bytes = fmx::values_of_hits_scratch_bytes(n, r.total, max_len);
+        const size_t ws_bytes = fmx::values_of_hits_scratch_bytes(n, total, max_len);
         void *ws = nullptr;
-        if ((rc = b.block((size_t)r.total * 4, &d_locs)) || (rc = b.block((size_t)r.total * 4, &d_count)) ||
-            (rc = b.block(((size_t)r.total + 1) * 8, &d_toff)) || (rc = b.block(ws_bytes, &ws)) || (rc = fill_hits(call, r, 0, r.total, d_locs)) ||
-            (rc = values_of_hits_impl(idx, n, term_len, stop, n_stop, max_len, r.hit_off, d_locs, r.total, d_voff, d_count, d_toff, r.status, ws,
-                                      ws_bytes, st)))
+        if ((!d_ready && (rc = b.block((size_t)total * 4, &d_locs))) || (rc = b.block((size_t)total * 4, &d_count)) ||
+            (rc = b.block(((size_t)total + 1) * 8, &d_toff)) || (rc = b.block(ws_bytes, &ws)) ||
+            (fill && (rc = fill_hits(call, *fill, 0, total, d_locs))) ||
+            (rc = values_of_hits_impl(idx, n, term_len, stop, n_stop, max_len, d_hit_off, d_ready ? d_ready : d_locs, total, d_voff, d_count,
+                                      d_toff, d_status, ws, ws_bytes, st)))
             return rc;
         fmx::ValuesWindows w;
         int32_t redo = 0;
-        (void)fmx::values_windows(ws, ws_bytes, n, r.total, max_len, &w);
+        (void)fmx::values_windows(ws, ws_bytes, n, total, max_len, &w);
         HIP_TRY(hipMemcpyAsync(&shape.groups, d_voff + n, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&redo, fmx::extract_packed_redo(w.scratch), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -3908,6 +3914,10 @@ static int values_down(PackedCall &call, RangeStage &r, const int32_t *term_len,
     }
     HIP_TRY(hipMemcpyAsync(val_off, d_voff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
     return FMX_OK;
+}
+static int values_down(PackedCall &call, RangeStage &r, const int32_t *term_len, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                       int64_t *val_off, ValuesShape &shape) {
+    return values_down_hits(call, &r, r.n, r.hit_off, nullptr, r.total, r.status, term_len, stop, n_stop, max_len, val_off, shape);
 }
 static void values_hand_over(const ValuesShape &shape, int32_t **counts, int64_t **text_off, uint16_t **chars) {
     g_extract_packed_redo = shape.redo;
@@ -3970,6 +3980,64 @@ int fmx_field_values_class_batch(const fmx_index *idx, const uint16_t *alt, cons
     values_hand_over(shape, counts, text_off, chars);
     return FMX_OK;
     });
+}
+
+// fmx_where_api.cpp's way into the sequence above (fmx_plan.hpp: values_between_call): ONE range stage over the merged batch — the
+// terms' hits in front, hit_off[n_terms] comes down with the total —, every hit into one block, the caller's stage, ONE wait for
+// kept_off, the values stages over the kept hits.  occurrences / status are the value patterns', term_status the terms'.
+extern "C++" {
+namespace fmx {
+int line_view(const fmx_index *idx, LineView *view) {
+    if (const int rc = require_fm_device(idx)) return rc;
+    *view = {static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_cu};
+    return FMX_OK;
+}
+int check_query_arrays(int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind) {
+    return check_queries(n, q, query_off, term_kind);
+}
+static int between_block(void *call, size_t bytes, void **out) { return static_cast<PackedCall *>(call)->blocks.block(bytes, out); }
+int values_between_call(const fmx_index *idx, const ValuesBatch &batch, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                        ValuesBetweenFn between, void *arg, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
+                        int32_t *occurrences, int32_t *status, int32_t *kept, int32_t *term_status) {
+    const int32_t n_terms = batch.n_terms, n = batch.n, n_all = n_terms + n;
+    PackedCall call(idx);
+    RangeStage r;
+    ValuesShape shape;
+    LineView view;
+    r.mark = n_terms;
+    const bool want_status = status || term_status;
+    int rc = line_view(idx, &view);
+    if (rc) return rc;
+    rc = batch.pos_off ? class_ranges(call, batch.chars, batch.pos_off, batch.n_pos, batch.pat_off, n_all, batch.max_ranges, true, want_status, r)
+                       : literal_ranges(call, batch.chars, batch.pat_off, n_all, -1, true, false, want_status, r);
+    if (rc) return rc;
+    if (r.total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
+    Scratch &b = call.blocks;
+    const hipStream_t st = call.stream.s;
+    const int64_t value_hits = r.total - r.mark_total;
+    int32_t *d_locs = nullptr, *d_kept = nullptr;
+    int64_t *d_koff = nullptr;
+    if ((rc = b.block((size_t)(n + 1) * 8, &d_koff)) || (rc = b.block((size_t)r.total * 4 + 8, &d_locs)) ||
+        (rc = b.block((size_t)value_hits * 4 + 8, &d_kept)) || (rc = fill_hits(call, r, 0, r.total, d_locs)))
+        return rc;
+    const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, d_koff, d_kept, &call, between_block};
+    if ((rc = between(hits, arg))) return rc;
+    std::vector<int64_t> kept_off((size_t)n + 1);
+    HIP_TRY(hipMemcpyAsync(kept_off.data(), d_koff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const std::vector<int32_t> len = lengths_of(batch.pat_off + n_terms, n);  // (pat_off has been judged)
+    if ((rc = values_down_hits(call, nullptr, n, d_koff, d_kept, kept_off[(size_t)n], r.status ? r.status + n_terms : nullptr, len.data(), stop,
+                               n_stop, max_len, val_off, shape)))
+        return rc;
+    if (occurrences) HIP_TRY(hipMemcpyAsync(occurrences, r.counts + n_terms, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, r.status + n_terms, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (term_status && n_terms > 0) HIP_TRY(hipMemcpyAsync(term_status, r.status, (size_t)n_terms * 4, hipMemcpyDeviceToHost, st));
+    if ((rc = packed_finish(call, r, nullptr, nullptr, nullptr, counts))) return rc;
+    for (int32_t i = 0; i < n && kept; ++i) kept[i] = (int32_t)(kept_off[(size_t)i + 1] - kept_off[(size_t)i]);
+    values_hand_over(shape, counts, text_off, chars);
+    return FMX_OK;
+}
+}  // namespace fmx
 }
 
 // shared host-buffer driver of the two pipelines (mode < 0: fixed-length extract)

@@ -145,4 +145,55 @@ int launch_values_groups(int n_cu, int32_t n, int32_t n_stop, int32_t max_len, i
 int launch_values_fill(int n_cu, int64_t groups, const int64_t *text_off, uint16_t *chars, const void *ws, void *stream);
 int launch_values_status_all(int n_cu, int32_t *status, int32_t n, int32_t value, void *stream);  // status[0, n) = value
 
+// fmx_hit_filter.hip — packed hits -> the packed hits that lie in given lines, in the order they had (fmx_hits_in_lines_dev;
+// fmx_hit_filter.hpp has the keep rule).  Compiled once.  where_of (n, each -1 .. q - 1) is a HOST array the caller has validated;
+// it is copied into the workspace before the launcher returns.  T == nullptr (no line table): the caller holds every where_of
+// negative and the window 0 .. INT32_MAX — every hit is kept, the block is moved to the front.  kept_locs must not overlap locs.
+// The grids are hit_lines_geometry's.  hipErrorInvalidValue before anything is launched or written: too small a workspace,
+// n_hits beyond 2^31 - 1.  n <= 0 or n_hits <= 0: nothing is done.
+size_t hits_in_lines_scratch_bytes(int32_t n, int64_t n_hits);
+int launch_hits_in_lines(const int32_t *T, int32_t count, int n_cu, int32_t n, const int32_t *where_of, const int64_t *line_off,
+                         const int32_t *lines, int32_t line_lo, int32_t line_hi, const int64_t *hit_off, const int32_t *locs, int64_t n_hits,
+                         int64_t *kept_off, int32_t *kept_locs, void *ws, size_t ws_bytes, void *stream);
+
+// fmx_api.cpp, for fmx_where_api.cpp.  line_view: the line table of a resident FM handle after the checks of every FM device entry
+// point (their return value; 0 = *view is filled; table == nullptr: fmx_line_table_build has not run).
+struct LineView {
+    const int32_t *table;
+    int32_t count;  // boundaries in the table
+    int n_cu;
+};
+int line_view(const ::fmx_index *idx, LineView *view);
+// the HOST arrays that cut n terms into q queries, as fmx_match_query_batch judges them (its return value)
+int check_query_arrays(int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind);
+// values_between_call: the packed host sequence of the values forms (a range stage, the fill, the values stages, ONE result
+// allocation, the per-pattern arrays, the last wait) over a MERGED batch — n_terms filter terms in front, then n value patterns,
+// literal (pos_off == nullptr: chars / pat_off are fmx_count_batch's) or class (alt / pos_off / pat_off are fmx_count_class_batch's)
+// — with a stage of the caller's between the fill and the values stages.  `between` sees every hit of the merged batch on the
+// device and leaves the value patterns' kept hits as (kept_off, kept_locs), asynchronously on `stream`; its device blocks come
+// from block() and live until the call has synchronised.  It returns an FMX_* code (fmx::api_fail sets the message).
+struct HitsBetween {
+    const LineView *view;
+    void *stream;
+    int32_t n_terms, n;
+    const int64_t *hit_off;      // n_terms + n + 1 (device)
+    const int32_t *locs;         // `total` hits (device)
+    int64_t term_hits, total;    // hit_off[n_terms], hit_off[n_terms + n]
+    int64_t *kept_off;           // n + 1 (device, out)
+    int32_t *kept_locs;          // room for total - term_hits (device, out)
+    void *call;
+    int (*block)(void *call, size_t bytes, void **out);
+};
+struct ValuesBatch {
+    const uint16_t *chars;
+    const int32_t *pos_off;  // nullptr: literal patterns
+    int32_t n_pos;
+    const int32_t *pat_off;
+    int32_t n_terms, n, max_ranges;
+};
+typedef int (*ValuesBetweenFn)(const HitsBetween &hits, void *arg);
+int values_between_call(const ::fmx_index *idx, const ValuesBatch &batch, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                        ValuesBetweenFn between, void *arg, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
+                        int32_t *occurrences, int32_t *status, int32_t *kept, int32_t *term_status);
+
 }  // namespace fmx

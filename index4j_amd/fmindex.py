@@ -55,6 +55,7 @@ def pack_patterns(patterns):
 
 CLASS_RANGES_MAX = 1024  # FMX_CLASS_RANGES_MAX
 CLASS_ALTS_MAX = 64  # FMX_CLASS_ALTS_MAX
+LINES_ALL = 2 ** 31 - 1  # the end of a window of lines that does not filter: lines=(0, LINES_ALL)
 CLASS_RANGES_DEFAULT = 256  # max_ranges where the caller names none: two frontiers of 4 KiB per pattern
 
 
@@ -519,14 +520,21 @@ class FmIndex:
                                    want_counts, want_spans)
 
     # ---- the values that follow a pattern, with counts (fmx.h "THE VALUES THAT FOLLOW A PATTERN, WITH COUNTS") ----
-    def _values_call(self, call, where, args, n, stop, max_len):
+    def _values_call(self, call, where, args, n, stop, max_len, n_terms=None):
+        """n_terms: the `where` forms, which also fill kept (per pattern, in front of status) and term_status (behind it)"""
         stop = as_chars(stop)
         val_off = np.zeros(n + 1, dtype=np.int64)
         occurrences = np.zeros(n, dtype=np.int32)
         status = np.zeros(n, dtype=np.int32)
         buf, toff_at, chars_at = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        if n_terms is None:
+            tail = (status.ctypes.data,)
+        else:
+            kept = np.zeros(n, dtype=np.int32)
+            term_status = np.zeros(n_terms, dtype=np.int32)
+            tail = (kept.ctypes.data, status.ctypes.data, term_status.ctypes.data)
         check(call(self._h, *args, stop.ctypes.data, len(stop), int(max_len), val_off.ctypes.data, C.byref(buf), C.byref(toff_at),
-                   C.byref(chars_at), occurrences.ctypes.data, status.ctypes.data), where)
+                   C.byref(chars_at), occurrences.ctypes.data, *tail), where)
         groups = int(val_off[n])
         try:  # the library's buffer (counts, offsets and code units in one block) is copied into arrays of NumPy's own
             if groups:
@@ -538,6 +546,8 @@ class FmIndex:
                 counts, text_off, chars = np.zeros(0, np.int32), np.zeros(1, np.int64), np.zeros(0, np.uint16)
         finally:
             lib.fmx_free_buffer(buf)
+        if n_terms is not None:
+            return chars, text_off, counts, val_off, status, occurrences, kept, term_status
         return chars, text_off, counts, val_off, status, occurrences
 
     def field_values_batch(self, chars, offsets, stop, max_len):
@@ -557,6 +567,49 @@ class FmIndex:
         alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
         return self._values_call(lib.fmx_field_values_class_batch, "fmx_field_values_class_batch",
                                  (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, int(max_ranges)), n, stop, max_len)
+
+    # ---- ... only within the lines of a query (fmx.h "THE VALUES THAT FOLLOW A PATTERN, WHERE THE LINE MATCHES A QUERY") ----
+    @staticmethod
+    def _where_arrays(n, n_terms, query_off, term_kind, where_of, lines):
+        query_off = np.ascontiguousarray(query_off, dtype=np.int32)
+        term_kind = np.ascontiguousarray(term_kind, dtype=np.uint8)
+        where_of = np.ascontiguousarray(where_of, dtype=np.int32)
+        if len(term_kind) != n_terms:
+            raise ValueError("term_kind has %d entries for %d terms" % (len(term_kind), n_terms))
+        if len(where_of) != n:
+            raise ValueError("where_of has %d entries for %d patterns" % (len(where_of), n))
+        lo, hi = (0, LINES_ALL) if lines is None else (int(lines[0]), int(lines[1]))
+        return query_off, term_kind, where_of, len(query_off) - 1, lo, hi
+
+    def field_values_where_batch(self, chars, offsets, term_chars, term_offsets, query_off, term_kind, where_of, stop, max_len, lines=None):
+        """field_values_batch over the hits that lie in the lines of a query and in a window of lines
+        (fmx_field_values_where_batch; grep terminating | grep -o 'blk_[^ ]*' | sort | uniq -c).  The terms (term_chars,
+        term_offsets) are cut into queries by query_off / term_kind exactly as in match_query_batch; a hit of pattern i counts iff
+        its line — the line of its first character — is in lines = (lo, hi), lo <= line < hi (None: every line), and
+        where_of[i] < 0 or the line matches query where_of[i].  Needs build_line_table() unless nothing filters.  Returns
+        (chars, text_off, counts, val_off, status, occurrences, kept, term_status): as field_values_batch, occurrences still the
+        pattern's count in the whole text, kept[i] the hits that passed (the counts of a pattern's values add up to it)."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        term_chars = np.ascontiguousarray(term_chars, dtype=np.uint16)
+        term_offsets = np.ascontiguousarray(term_offsets, dtype=np.int32)
+        n, n_terms = len(offsets) - 1, len(term_offsets) - 1
+        query_off, term_kind, where_of, q, lo, hi = self._where_arrays(n, n_terms, query_off, term_kind, where_of, lines)
+        return self._values_call(lib.fmx_field_values_where_batch, "fmx_field_values_where_batch",
+                                 (chars.ctypes.data, offsets.ctypes.data, n, term_chars.ctypes.data, term_offsets.ctypes.data, n_terms,
+                                  query_off.ctypes.data, term_kind.ctypes.data, q, where_of.ctypes.data, lo, hi), n, stop, max_len, n_terms)
+
+    def field_values_where_class_batch(self, alt, pos_off, pat_off, term_alt, term_pos_off, term_pat_off, query_off, term_kind, where_of, stop,
+                                       max_len, lines=None, max_ranges=CLASS_RANGES_DEFAULT):
+        """field_values_where_batch with class patterns as value patterns and as terms (fmx_field_values_where_class_batch); same
+        returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        term_alt, term_pos_off, term_pat_off, term_n_pos, n_terms = self._class_arrays(term_alt, term_pos_off, term_pat_off)
+        query_off, term_kind, where_of, q, lo, hi = self._where_arrays(n, n_terms, query_off, term_kind, where_of, lines)
+        return self._values_call(lib.fmx_field_values_where_class_batch, "fmx_field_values_where_class_batch",
+                                 (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, term_alt.ctypes.data,
+                                  term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms, int(max_ranges), query_off.ctypes.data,
+                                  term_kind.ctypes.data, q, where_of.ctypes.data, lo, hi), n, stop, max_len, n_terms)
 
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
@@ -752,14 +805,49 @@ class FmIndex:
             raise_for_status(st)
         return (out[0], out[3]) if want_spans else out[0]
 
-    def field_values(self, pattern, stop=" \t\r\n", max_len=32, top=None, ignore_case=False):
+    def _values_where(self, pattern, where, lines, stop, max_len, ignore_case, count_only=False):
+        """one pattern through field_values_where_batch / field_values_where_class_batch: where = dict(all=, any=, none=) is ONE
+        query (match_query's words; None: no query), lines = (lo, hi) a window of line ids (None: every line)"""
+        p = as_chars(pattern)
+        terms, kinds = [], []
+        for kind, word in enumerate(("all", "any", "none")):
+            group = (where or {}).get(word, ())
+            for t in ([group] if isinstance(group, str) else group):  # (a lone str is one term)
+                terms.append(as_chars(t))
+                kinds.append(kind)
+        if where is not None and set(where) - {"all", "any", "none"}:
+            raise ValueError("where takes all=, any= and none=")
+        if min((len(t) for t in terms + [p]), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        query_off, where_of = ([0, len(terms)], [0]) if where is not None else ([0], [-1])
+        if ignore_case:
+            out = self.field_values_where_class_batch(*pack_class_patterns([_ignore_case(p)]), *pack_class_patterns([_ignore_case(t) for t in terms]),
+                                                      query_off, np.array(kinds, np.uint8), where_of, stop, max_len, lines)
+        else:
+            out = self.field_values_where_batch(*pack_patterns([p]), *pack_patterns(terms), query_off, np.array(kinds, np.uint8), where_of, stop,
+                                                max_len, lines)
+        for st in [out[4][0]] + out[7].tolist():
+            if not (count_only and st == 1):  # (kept is filled on an index built without extraction too)
+                raise_for_status(st)
+        return out
+
+    def count_where(self, pattern, where=None, lines=None, ignore_case=False):
+        """the occurrences of `pattern` inside the lines that match where = dict(all=, any=, none=) (match_query's words) and lie in
+        lines = (lo, hi): grep ... | grep -o pattern | wc -l.  A hit belongs to the line of its first character."""
+        return int(self._values_where(pattern, where, lines, "", 1, ignore_case, count_only=True)[6][0])
+
+    def field_values(self, pattern, stop=" \t\r\n", max_len=32, top=None, ignore_case=False, where=None, lines=None):
         """[(value, count)] of the distinct values that follow `pattern` (grep -o 'pattern[^stop]*' | sort | uniq -c): ascending by
         UTF-16 code unit, a value in front of its extensions; with top=k the k entries with the largest counts, ties by value
-        (sorted on the host over the groups).  ignore_case: the pattern in any case, one answer for all spellings."""
+        (sorted on the host over the groups).  ignore_case: the pattern in any case, one answer for all spellings.
+        where=dict(all=, any=, none=) and lines=(lo, hi): only the hits in the lines that match that query (match_query's words)
+        and lie in that window of line ids — count by value WHERE the line holds ...; needs build_line_table()."""
         p = as_chars(pattern)
         if len(p) == 0:
             raise IndexError("ArrayIndexOutOfBoundsException")
-        if ignore_case:
+        if where is not None or lines is not None:
+            out = self._values_where(p, where, lines, stop, max_len, ignore_case)[:6]
+        elif ignore_case:
             out = self.field_values_class_batch(*pack_class_patterns([_ignore_case(p)]), stop, max_len)
         else:
             out = self.field_values_batch(*pack_patterns([p]), stop, max_len)

@@ -375,6 +375,49 @@ int fmx_field_values_where_class_batch(const fmx_index *idx, const uint16_t *alt
                                        int64_t **text_off, uint16_t **chars, int32_t *occurrences, int32_t *kept, int32_t *status,
                                        int32_t *term_status);
 
+/* LINES AND HITS PER BUCKET OF LINES (the timeline of a log search: the matching events per time bucket, beside the hit list and
+ * the "count by") — the host forms of fmx_lines_histogram_dev and fmx_hits_histogram_dev (below: the stages).
+ * EDGES: edges = n_edges >= 2 ints, B = n_edges - 1 buckets.  They are line ids, in the ids of fmx_line_bounds_batch; edges[0] >= 0;
+ * they never decrease, equal neighbours make an empty bucket; they may exceed the number of lines.  Bucket b is the lines L with
+ * edges[b] <= L < edges[b + 1]; a line below edges[0] or at or above edges[B] is counted in no bucket.  One edge array serves the
+ * whole batch.  (Edges come from timestamps with what exists: the first line that holds "081109 2035" is
+ * fmx_match_lines_batch's first line for it, max_lines = 1.)  Counts are int32; (int64) rows * B above 2^27 is FMX_E_ARG.
+ * LINES PER BUCKET: hist = the caller's q * B ints, hist[Q * B + b] = the number of lines of query Q in bucket b — the lines are
+ * fmx_match_query_batch's, whose definitions (pat, pat_off, n, query_off, term_kind, q; line_count, occurrences, status, each
+ * nullable) hold unchanged: a query of NONE terms only has no lines, so a row of zeros; row Q adds up to line_count[Q] when the
+ * edges span every line.  The two packed stages, fmx_query_lines_of_hits_dev (no limit) and fmx_lines_histogram_dev run; only hist
+ * and the small per-query and per-term arrays come down — the lines do not.
+ * FMX_E_ARG as fmx_match_query_batch, and for n_edges < 2, a negative first edge, decreasing edges, more than 2^27 counters;
+ * FMX_E_NO_DEVICE for a handle that is not resident; FMX_E_NOMEM leaves nothing behind.  n == 0: FMX_OK, hist and line_count are
+ * zeroed, nothing is searched. */
+int fmx_line_histogram_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const int32_t *query_off,
+                             const uint8_t *term_kind, int32_t q, const int32_t *edges, int32_t n_edges, int32_t *hist, int32_t *line_count,
+                             int32_t *occurrences, int32_t *status);
+/* ... with class patterns as terms: the three packed arrays of fmx_count_class_batch and max_ranges, as fmx_match_query_class_batch */
+int fmx_line_histogram_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                   int32_t n, int32_t max_ranges, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                   const int32_t *edges, int32_t n_edges, int32_t *hist, int32_t *line_count, int32_t *occurrences,
+                                   int32_t *status);
+/* HITS PER BUCKET: fmx_field_values_where_batch's call without the values stage (its value patterns, terms, query_off, term_kind,
+ * where_of, occurrences, kept, status and term_status, no window).  hist = the caller's n * B ints, hist[i * B + b] = the number of
+ * hits of value pattern i that fmx_hits_in_lines_dev keeps for where_of[i] and whose line — the line of the hit's FIRST character
+ * — lies in bucket b.  A hit is counted as often as it occurs: two "blk_" on one line are two.  Row i adds up to at most kept[i],
+ * and to exactly kept[i] when the edges span every line.  With every where_of[i] < 0 the filter stage is skipped and the raw hits
+ * are binned (kept[i] = occurrences[i]).  A line table is needed in every case: the buckets are lines.
+ * FMX_E_ARG as fmx_field_values_where_batch (its window, stop set and max_len aside) and for the edges as above, an index without a
+ * line table (the error names fmx_line_table_build); FMX_E_NO_DEVICE for a handle that is not resident; FMX_E_NOMEM leaves nothing
+ * behind.  n == 0: FMX_OK, nothing is searched and term_status is zeroed. */
+int fmx_hit_histogram_where_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *term_pat,
+                                  const int32_t *term_off, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                  const int32_t *where_of, const int32_t *edges, int32_t n_edges, int32_t *hist, int32_t *occurrences,
+                                  int32_t *kept, int32_t *status, int32_t *term_status);
+/* ... with class patterns as value patterns and as terms, as fmx_field_values_where_class_batch */
+int fmx_hit_histogram_where_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                        int32_t n, const uint16_t *term_alt, const int32_t *term_pos_off, int32_t term_n_pos,
+                                        const int32_t *term_off, int32_t n_terms, int32_t max_ranges, const int32_t *query_off,
+                                        const uint8_t *term_kind, int32_t q, const int32_t *where_of, const int32_t *edges, int32_t n_edges,
+                                        int32_t *hist, int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *term_status);
+
 /* THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY (extract, FM:564-608, batched) — the host form of
  * fmx_extract_packed_offsets_dev + fmx_extract_packed_fill_dev (below: the layout, the statuses, how the work is cut).
  * host buffers, synchronous: text_off = n + 1 int64 (out), text_off[0] = 0; *chars = text_off[n] UTF-16 code units owned by the
@@ -666,6 +709,36 @@ size_t fmx_hits_in_lines_scratch_bytes(int32_t n, int64_t n_hits);
 int fmx_hits_in_lines_dev(const fmx_index *idx, int32_t n, const int32_t *where_of, int32_t q, const int64_t *d_line_off, const int32_t *d_lines,
                           int32_t line_lo, int32_t line_hi, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits,
                           int64_t *d_kept_off, int32_t *d_kept_locs, void *d_ws, size_t ws_bytes, void *stream);
+/* LINES AND HITS PER BUCKET OF LINES over device pointers (the edges and buckets: fmx_line_histogram_batch above).  edges is a HOST
+ * array in both forms, as where_of and query_off are: validated, and copied into d_ws before the call returns.  d_hist gets
+ * rows * B int32; entries behind them keep the caller's values.
+ * fmx_lines_histogram_dev: packed ascending lists (d_line_off, d_lines) of q lists — what the line, query and sequence stages
+ * leave without a limit; an entry that occurs twice in a list counts twice — -> d_hist[Q * B + b] = the entries of list Q in bucket
+ * b.  A lane per (list, edge) does ONE lower bound of the edge in its list, a lane per (list, bucket) then takes the difference
+ * of two neighbouring ranks: q * n_edges short searches — a list of 10^7 lines costs what a list of 10 costs, no lane walks a
+ * list.  Needs no line table.  d_ws: at least fmx_lines_histogram_scratch_bytes(q, n_edges) bytes (8 per (list, edge), 4 per edge).
+ * fmx_hits_histogram_dev: packed hits (d_hit_off, d_locs, n_hits) of n patterns exactly as fmx_hits_in_lines_dev takes them —
+ * d_hit_off[0] may be non-zero, slots behind d_hit_off[n] are ignored; the hits are in SA-row order, not in text order — ->
+ * d_hist[i * B + b] = the hits of pattern i whose line (the line of the hit's first character) lies in bucket b.  A lane per slot
+ * makes the key pattern | bucket (the pattern from the hit tiles, the line over the fences staged in LDS, the bucket by an upper
+ * bound over the edges: up to 4,096 edges are staged in LDS, more are searched in HBM — correct, not tuned; the bucket B stands
+ * for "no bucket", the pattern n for a slot that is no hit); ONE device-wide rocPRIM radix sort over the bits in use; a lane per
+ * (pattern, bucket) takes two lower bounds in the sorted keys.  d_ws: at least fmx_hits_histogram_scratch_bytes(n, n_hits,
+ * n_edges) bytes (16 per slot, 4 per edge, rocPRIM's temporary storage).
+ * Both: integers only, no atomics — the result does not depend on scheduling; lanes go to slots or to counters, never to patterns;
+ * the grids are fmx_hit_lines_geometry's; asynchronous on `stream`, nothing is allocated, nothing is synchronised beyond the staged
+ * host copy of edges.  The scratch sizes are 0 for an empty call or a shape the call refuses.  q == 0, n == 0: nothing is written;
+ * n_hits == 0: the n * B counters are zeroed and nothing else is written.
+ * FMX_E_ARG for null or negative arguments, n_edges < 2, a negative first edge, decreasing edges, (int64) rows * B above 2^27,
+ * n_hits > 2^31 - 1, an index without a line table (hits form only; the error names fmx_line_table_build), a workspace that is too
+ * small (nothing is launched, nothing is written), a SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE for a
+ * handle that is not resident. */
+size_t fmx_lines_histogram_scratch_bytes(int32_t q, int32_t n_edges);
+size_t fmx_hits_histogram_scratch_bytes(int32_t n, int64_t n_hits, int32_t n_edges);
+int fmx_lines_histogram_dev(const fmx_index *idx, int32_t q, const int64_t *d_line_off, const int32_t *d_lines, const int32_t *edges,
+                            int32_t n_edges, int32_t *d_hist, void *d_ws, size_t ws_bytes, void *stream);
+int fmx_hits_histogram_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, const int32_t *edges,
+                           int32_t n_edges, int32_t *d_hist, void *d_ws, size_t ws_bytes, void *stream);
 /* CLASS PATTERNS over device pointers (d_alt, d_pos_off, d_pat_off: the three packed arrays of fmx_count_class_batch, in device
  * memory and trusted as the literal device forms trust theirs); asynchronous on `stream`, nothing is allocated or synchronised.
  * THE SEARCH keeps, per pattern, a frontier of SA ranges: the last position gives {C[c], C[c + 1]} of each of its codes, every

@@ -506,6 +506,89 @@ public:
         return out;
     }
 
+    // matching lines and hits per bucket of lines, the timeline (fmx.h "LINES AND HITS PER BUCKET OF LINES"; needs buildLineTable).
+    // edges: B + 1 line ids that never decrease, bucket b = the lines edges[b] <= L < edges[b + 1]; a line outside edges[0] ..
+    // edges[B] is counted nowhere.  lineHistogramBatch: counts[Q * B + b] = the lines of matchQuery(queries[Q]) in bucket b — only
+    // the counters come down; lineCount per query, occurrences per term.  hitHistogramWhereBatch: counts[i * B + b] = the hits of
+    // patterns[i] that fieldValuesWhereBatch keeps for whereOf[i] (no window) whose line — the line of the hit's first character —
+    // lies in bucket b; a hit counts as often as it occurs.  Statuses are not thrown by the batch forms; lineHistogram and
+    // hitHistogramWhere answer one row and throw them.
+    struct LineHistogram {
+        int32_t buckets = 0;
+        std::vector<int32_t> counts, lineCount, occurrences, status;
+        std::vector<int32_t> row(size_t i) const { return {counts.begin() + i * (size_t)buckets, counts.begin() + (i + 1) * (size_t)buckets}; }
+    };
+    LineHistogram lineHistogramBatch(const std::vector<Query> &queries, const std::vector<int32_t> &edges) const {
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        flattenQueries(queries, terms, kind, queryOff);
+        std::vector<uint16_t> chars;
+        std::vector<int32_t> off;
+        pack(terms, chars, off);
+        LineHistogram out;
+        out.buckets = edges.size() > 1 ? (int32_t)edges.size() - 1 : 0;
+        out.counts.assign(queries.size() * (size_t)out.buckets + 1, 0);
+        out.lineCount.assign(queries.size(), 0);
+        out.occurrences.assign(terms.size(), 0);
+        out.status.assign(terms.size(), 0);
+        detail::check(fmx_line_histogram_batch(h_, chars.data(), off.data(), (int32_t)terms.size(), queryOff.data(), kind.data(),
+                                               (int32_t)queries.size(), edges.data(), (int32_t)edges.size(), out.counts.data(),
+                                               out.lineCount.data(), out.occurrences.data(), out.status.data()),
+                      "fmx_line_histogram_batch");
+        out.counts.pop_back();
+        return out;
+    }
+    std::vector<int32_t> lineHistogram(const Query &query, const std::vector<int32_t> &edges) const {
+        for (const std::vector<std::u16string> *g : {&query.all, &query.any, &query.none})
+            for (const std::u16string &t : *g)
+                if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const LineHistogram h = lineHistogramBatch({query}, edges);
+        for (int s : h.status) detail::raise_for_status(s);
+        return h.counts;
+    }
+    struct HitHistogram {
+        int32_t buckets = 0;
+        std::vector<int32_t> counts, occurrences, kept, status, termStatus;
+        std::vector<int32_t> row(size_t i) const { return {counts.begin() + i * (size_t)buckets, counts.begin() + (i + 1) * (size_t)buckets}; }
+    };
+    HitHistogram hitHistogramWhereBatch(const std::vector<std::u16string> &patterns, const std::vector<Query> &queries,
+                                        const std::vector<int32_t> &whereOf, const std::vector<int32_t> &edges) const {
+        if (whereOf.size() != patterns.size()) throw std::invalid_argument("whereOf has one entry per pattern");
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        flattenQueries(queries, terms, kind, queryOff);
+        std::vector<uint16_t> chars, termChars;
+        std::vector<int32_t> off, termOff;
+        pack(patterns, chars, off);
+        pack(terms, termChars, termOff);
+        HitHistogram out;
+        out.buckets = edges.size() > 1 ? (int32_t)edges.size() - 1 : 0;
+        out.counts.assign(patterns.size() * (size_t)out.buckets + 1, 0);
+        out.occurrences.assign(patterns.size(), 0);
+        out.kept.assign(patterns.size(), 0);
+        out.status.assign(patterns.size(), 0);
+        out.termStatus.assign(terms.size(), 0);
+        detail::check(fmx_hit_histogram_where_batch(h_, chars.data(), off.data(), (int32_t)patterns.size(), termChars.data(), termOff.data(),
+                                                    (int32_t)terms.size(), queryOff.data(), kind.data(), (int32_t)queries.size(), whereOf.data(),
+                                                    edges.data(), (int32_t)edges.size(), out.counts.data(), out.occurrences.data(),
+                                                    out.kept.data(), out.status.data(), out.termStatus.data()),
+                      "fmx_hit_histogram_where_batch");
+        out.counts.pop_back();
+        return out;
+    }
+    std::vector<int32_t> hitHistogramWhere(const std::u16string &pattern, const Query &where, const std::vector<int32_t> &edges) const {
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        for (const std::vector<std::u16string> *g : {&where.all, &where.any, &where.none})
+            for (const std::u16string &t : *g)
+                if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const HitHistogram h = hitHistogramWhereBatch({pattern}, {where}, {0}, edges);
+        detail::raise_for_status(h.status[0]);
+        for (int s : h.termStatus) detail::raise_for_status(s);
+        return h.counts;
+    }
+
     // the text of ranges and of lines in ONE packed array (fmx.h "THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY"): range / line
     // i is chars[offsets[i] .. offsets[i + 1]) — what extract(start, stop, destination, 0) leaves in destination; memory follows
     // the sum of the lengths.  status[i] is the range's own (not thrown: one range out of the text does not hide the others);
@@ -645,6 +728,21 @@ private:
             off.push_back((int32_t)chars.size());
         }
         if (chars.empty()) chars.push_back(0);
+    }
+    // the terms of a batch of queries in the order all, any, none of query 0, then query 1 ..., their kinds (one entry more: never
+    // an empty array) and the offsets that cut them into queries (queryOff starts as {0})
+    static void flattenQueries(const std::vector<Query> &queries, std::vector<std::u16string> &terms, std::vector<uint8_t> &kind,
+                               std::vector<int32_t> &queryOff) {
+        for (const Query &qu : queries) {
+            const std::vector<std::u16string> *groups[3] = {&qu.all, &qu.any, &qu.none};
+            for (int k = 0; k < 3; ++k)
+                for (const std::u16string &t : *groups[k]) {
+                    terms.push_back(t);
+                    kind.push_back((uint8_t)k);
+                }
+            queryOff.push_back((int32_t)terms.size());
+        }
+        kind.push_back(0);
     }
     // the three packed arrays of a batch of class patterns (fmx_count_class_batch)
     static FieldValues emptyFieldValues(size_t n) {

@@ -4037,6 +4037,31 @@ int values_between_call(const fmx_index *idx, const ValuesBatch &batch, const ui
     values_hand_over(shape, counts, text_off, chars);
     return FMX_OK;
 }
+int hits_stage_call(const fmx_index *idx, const ValuesBatch &batch, ValuesBetweenFn stage, void *arg, int32_t *occurrences, int32_t *status,
+                    int32_t *term_occurrences, int32_t *term_status) {
+    const int32_t n_terms = batch.n_terms, n = batch.n, n_all = n_terms + n;
+    PackedCall call(idx);
+    RangeStage r;
+    LineView view;
+    r.mark = n_terms;
+    const bool want_status = status || term_status;
+    int rc = line_view(idx, &view);
+    if (rc) return rc;
+    rc = batch.pos_off ? class_ranges(call, batch.chars, batch.pos_off, batch.n_pos, batch.pat_off, n_all, batch.max_ranges, true, want_status, r)
+                       : literal_ranges(call, batch.chars, batch.pat_off, n_all, -1, true, false, want_status, r);
+    if (rc) return rc;
+    if (r.total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
+    const hipStream_t st = call.stream.s;
+    int32_t *d_locs = nullptr;
+    if ((rc = call.blocks.block((size_t)r.total * 4 + 8, &d_locs)) || (rc = fill_hits(call, r, 0, r.total, d_locs))) return rc;
+    const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, nullptr, nullptr, &call, between_block};
+    if ((rc = stage(hits, arg))) return rc;
+    if (occurrences && n > 0) HIP_TRY(hipMemcpyAsync(occurrences, r.counts + n_terms, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (status && n > 0) HIP_TRY(hipMemcpyAsync(status, r.status + n_terms, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (term_occurrences && n_terms > 0) HIP_TRY(hipMemcpyAsync(term_occurrences, r.counts, (size_t)n_terms * 4, hipMemcpyDeviceToHost, st));
+    if (term_status && n_terms > 0) HIP_TRY(hipMemcpyAsync(term_status, r.status, (size_t)n_terms * 4, hipMemcpyDeviceToHost, st));
+    return packed_finish(call, r, nullptr, nullptr, nullptr, nullptr);
+}
 }  // namespace fmx
 }
 

@@ -156,6 +156,18 @@ int launch_hits_in_lines(const int32_t *T, int32_t count, int n_cu, int32_t n, c
                          const int32_t *lines, int32_t line_lo, int32_t line_hi, const int64_t *hit_off, const int32_t *locs, int64_t n_hits,
                          int64_t *kept_off, int32_t *kept_locs, void *ws, size_t ws_bytes, void *stream);
 
+// fmx_line_hist.hip — matching lines and hits per bucket of lines (fmx_lines_histogram_dev, fmx_hits_histogram_dev;
+// fmx_line_hist.hpp has the definitions).  Compiled once.  edges (n_edges >= 2, edges[0] >= 0, never decreasing) is a HOST array; it
+// is judged again and copied into the workspace before the launcher returns.  hist gets rows * (n_edges - 1) int32, nothing behind
+// them.  The grids are hit_lines_geometry's.  hipErrorInvalidValue before anything is launched or written: too small a workspace,
+// bad edges, rows * B beyond 2^27, n_hits beyond 2^31 - 1, no line table (hits form).  q <= 0, n <= 0 or n_hits <= 0: nothing is done.
+size_t lines_histogram_scratch_bytes(int32_t q, int32_t n_edges);
+size_t hits_histogram_scratch_bytes(int32_t n, int64_t n_hits, int32_t n_edges);
+int launch_lines_histogram(int n_cu, int32_t q, const int64_t *line_off, const int32_t *lines, const int32_t *edges, int32_t n_edges,
+                           int32_t *hist, void *ws, size_t ws_bytes, void *stream);
+int launch_hits_histogram(const int32_t *T, int32_t count, int n_cu, int32_t n, const int64_t *hit_off, const int32_t *locs, int64_t n_hits,
+                          const int32_t *edges, int32_t n_edges, int32_t *hist, void *ws, size_t ws_bytes, void *stream);
+
 // fmx_api.cpp, for fmx_where_api.cpp.  line_view: the line table of a resident FM handle after the checks of every FM device entry
 // point (their return value; 0 = *view is filled; table == nullptr: fmx_line_table_build has not run).
 struct LineView {
@@ -195,5 +207,11 @@ typedef int (*ValuesBetweenFn)(const HitsBetween &hits, void *arg);
 int values_between_call(const ::fmx_index *idx, const ValuesBatch &batch, const uint16_t *stop, int32_t n_stop, int32_t max_len,
                         ValuesBetweenFn between, void *arg, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
                         int32_t *occurrences, int32_t *status, int32_t *kept, int32_t *term_status);
+// hits_stage_call, for fmx_hist_api.cpp: the same sequence up to the caller's stage and no further — ONE range stage over the merged
+// batch, every hit into one block, `stage`, the per-pattern arrays, the last wait.  kept_off / kept_locs of HitsBetween are NULL:
+// the stage takes what it needs from block().  What it copies to the host asynchronously on `stream` has arrived when the call
+// returns FMX_OK.  occurrences / status are the value patterns', term_occurrences / term_status the terms' (each nullable).
+int hits_stage_call(const ::fmx_index *idx, const ValuesBatch &batch, ValuesBetweenFn stage, void *arg, int32_t *occurrences, int32_t *status,
+                    int32_t *term_occurrences, int32_t *term_status);
 
 }  // namespace fmx

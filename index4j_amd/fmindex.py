@@ -611,6 +611,84 @@ class FmIndex:
                                   term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms, int(max_ranges), query_off.ctypes.data,
                                   term_kind.ctypes.data, q, where_of.ctypes.data, lo, hi), n, stop, max_len, n_terms)
 
+    # ---- matching lines and hits per bucket of lines, the timeline (fmx.h "LINES AND HITS PER BUCKET OF LINES") ----
+    @staticmethod
+    def _edges(edges):
+        edges = np.ascontiguousarray(edges, dtype=np.int32)
+        if edges.ndim != 1:
+            raise ValueError("edges is one array of line ids")
+        return edges, max(len(edges) - 1, 0)
+
+    def _line_histogram_call(self, call, where, args, n, query_off, term_kind, edges, want_counts):
+        query_off = np.ascontiguousarray(query_off, dtype=np.int32)
+        term_kind = np.ascontiguousarray(term_kind, dtype=np.uint8)
+        edges, B = self._edges(edges)
+        q = len(query_off) - 1
+        if len(term_kind) != n:
+            raise ValueError("term_kind has %d entries for %d terms" % (len(term_kind), n))
+        hist = np.zeros((q, B), dtype=np.int32)
+        line_count = np.zeros(q, dtype=np.int32)
+        occurrences = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        check(call(self._h, *args, query_off.ctypes.data, term_kind.ctypes.data, q, edges.ctypes.data, len(edges), hist.ctypes.data,
+                   line_count.ctypes.data, occurrences.ctypes.data, status.ctypes.data), where)
+        return (hist, status, line_count, occurrences) if want_counts else hist
+
+    def line_histogram_batch(self, chars, offsets, query_off, term_kind, edges, want_counts=False):
+        """the matching lines of every QUERY per bucket of lines (fmx_line_histogram_batch; the timeline of a log search): the
+        terms, query_off and term_kind are match_query_batch's; edges = B + 1 line ids that never decrease, bucket b is the
+        lines edges[b] <= L < edges[b + 1], a line outside edges[0] .. edges[B] is counted nowhere.  Returns the (q, B) int32
+        array — the lines themselves stay on the device —, with want_counts (hist, status, line_count, occurrences): status and
+        occurrences per TERM, line_count per query."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        n = len(offsets) - 1
+        return self._line_histogram_call(lib.fmx_line_histogram_batch, "fmx_line_histogram_batch", (chars.ctypes.data, offsets.ctypes.data, n), n,
+                                         query_off, term_kind, edges, want_counts)
+
+    def line_histogram_class_batch(self, alt, pos_off, pat_off, query_off, term_kind, edges, want_counts=False, max_ranges=CLASS_RANGES_DEFAULT):
+        """line_histogram_batch with class patterns as terms (fmx_line_histogram_class_batch); same returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        return self._line_histogram_call(lib.fmx_line_histogram_class_batch, "fmx_line_histogram_class_batch",
+                                         (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, int(max_ranges)), n, query_off,
+                                         term_kind, edges, want_counts)
+
+    def _hit_histogram_call(self, call, where, args, n, n_terms, query_off, term_kind, where_of, edges, want_counts):
+        query_off, term_kind, where_of, q, _, _ = self._where_arrays(n, n_terms, query_off, term_kind, where_of, None)
+        edges, B = self._edges(edges)
+        hist = np.zeros((n, B), dtype=np.int32)
+        occurrences, kept, status = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        term_status = np.zeros(n_terms, dtype=np.int32)
+        check(call(self._h, *args, query_off.ctypes.data, term_kind.ctypes.data, q, where_of.ctypes.data, edges.ctypes.data, len(edges),
+                   hist.ctypes.data, occurrences.ctypes.data, kept.ctypes.data, status.ctypes.data, term_status.ctypes.data), where)
+        return (hist, status, occurrences, kept, term_status) if want_counts else hist
+
+    def hit_histogram_where_batch(self, chars, offsets, term_chars, term_offsets, query_off, term_kind, where_of, edges, want_counts=False):
+        """the hits of every pattern per bucket of lines, only within the lines of a query (fmx_hit_histogram_where_batch):
+        field_values_where_batch's patterns, terms, query_off, term_kind and where_of, no window and no values; edges as in
+        line_histogram_batch.  A hit belongs to the line of its first character and counts as often as it occurs.  Returns the
+        (n, B) int32 array, with want_counts (hist, status, occurrences, kept, term_status); row i adds up to kept[i] when the
+        edges span every line.  Needs build_line_table()."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        term_chars = np.ascontiguousarray(term_chars, dtype=np.uint16)
+        term_offsets = np.ascontiguousarray(term_offsets, dtype=np.int32)
+        n, n_terms = len(offsets) - 1, len(term_offsets) - 1
+        return self._hit_histogram_call(lib.fmx_hit_histogram_where_batch, "fmx_hit_histogram_where_batch",
+                                        (chars.ctypes.data, offsets.ctypes.data, n, term_chars.ctypes.data, term_offsets.ctypes.data, n_terms), n,
+                                        n_terms, query_off, term_kind, where_of, edges, want_counts)
+
+    def hit_histogram_where_class_batch(self, alt, pos_off, pat_off, term_alt, term_pos_off, term_pat_off, query_off, term_kind, where_of, edges,
+                                        want_counts=False, max_ranges=CLASS_RANGES_DEFAULT):
+        """hit_histogram_where_batch with class patterns as value patterns and as terms (fmx_hit_histogram_where_class_batch); same
+        returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        term_alt, term_pos_off, term_pat_off, term_n_pos, n_terms = self._class_arrays(term_alt, term_pos_off, term_pat_off)
+        return self._hit_histogram_call(lib.fmx_hit_histogram_where_class_batch, "fmx_hit_histogram_where_class_batch",
+                                        (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, term_alt.ctypes.data,
+                                         term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms, int(max_ranges)), n, n_terms,
+                                        query_off, term_kind, where_of, edges, want_counts)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -858,6 +936,52 @@ class FmIndex:
         if top is not None:  # (a stable sort: equal counts keep the order of the values)
             pairs = sorted(pairs, key=lambda vc: -vc[1])[:max(int(top), 0)]
         return pairs
+
+    def line_histogram(self, edges, all=(), any=(), none=(), ignore_case=False):  # noqa: A002 (the words of the query)
+        """the lines of match_query(all, any, none) per bucket of lines: B = len(edges) - 1 ints, bucket b the lines edges[b] <= L <
+        edges[b + 1] (the timeline; an edge from a timestamp: match_lines("081109 2035", max_lines=1) is the first line of that
+        minute).  Only the B counters come down."""
+        terms, kinds = [], []
+        for kind, group in enumerate((all, any, none)):  # (a lone str is one term)
+            for p in ([group] if isinstance(group, str) else group):
+                terms.append(as_chars(p))
+                kinds.append(kind)
+        if min((len(t) for t in terms), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        if ignore_case:
+            out = self.line_histogram_class_batch(*pack_class_patterns([_ignore_case(t) for t in terms]), [0, len(terms)], np.array(kinds, np.uint8),
+                                                  edges, want_counts=True)
+        else:
+            out = self.line_histogram_batch(*pack_patterns(terms), [0, len(terms)], np.array(kinds, np.uint8), edges, want_counts=True)
+        for st in out[1]:
+            raise_for_status(st)
+        return out[0][0]
+
+    def hit_histogram(self, pattern, edges, where=None, ignore_case=False):
+        """the occurrences of `pattern` per bucket of lines (edges as in line_histogram), with where=dict(all=, any=, none=) only
+        those in the lines that match that query: B = len(edges) - 1 ints.  A hit belongs to the line of its first character; two
+        on one line are two."""
+        p = as_chars(pattern)
+        terms, kinds = [], []
+        for kind, word in enumerate(("all", "any", "none")):
+            group = (where or {}).get(word, ())
+            for t in ([group] if isinstance(group, str) else group):  # (a lone str is one term)
+                terms.append(as_chars(t))
+                kinds.append(kind)
+        if where is not None and set(where) - {"all", "any", "none"}:
+            raise ValueError("where takes all=, any= and none=")
+        if min((len(t) for t in terms + [p]), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        query_off, where_of = ([0, len(terms)], [0]) if where is not None else ([0], [-1])
+        if ignore_case:
+            out = self.hit_histogram_where_class_batch(*pack_class_patterns([_ignore_case(p)]), *pack_class_patterns([_ignore_case(t) for t in terms]),
+                                                       query_off, np.array(kinds, np.uint8), where_of, edges, want_counts=True)
+        else:
+            out = self.hit_histogram_where_batch(*pack_patterns([p]), *pack_patterns(terms), query_off, np.array(kinds, np.uint8), where_of, edges,
+                                                 want_counts=True)
+        for st in [out[1][0]] + out[4].tolist():
+            raise_for_status(st)
+        return out[0][0]
 
     def line_text(self, lines):
         """the lines with these ids as a list of str (the boundary excluded); raises for an id that is no line"""

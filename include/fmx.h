@@ -418,6 +418,53 @@ int fmx_hit_histogram_where_class_batch(const fmx_index *idx, const uint16_t *al
                                         const uint8_t *term_kind, int32_t q, const int32_t *where_of, const int32_t *edges, int32_t n_edges,
                                         int32_t *hist, int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *term_status);
 
+/* THE NUMBER BEHIND A PATTERN: STATISTICS PER BUCKET OF LINES (stats sum(size) p95(size) by minute where line has addStoredBlock:
+ * "how much" beside the timeline's "how many") — the host forms of fmx_numbers_of_hits_dev (below: the stage).
+ * THE VALUE OF A HIT: with len the length of the hit's pattern and textLength = fmx_input_length - 1, the hit's window is
+ *     s = min(max(h + len, 0), textLength),   e = min(s + 32, textLength)
+ * (fmx_field_values_batch's window at max_len = 32); its text is what extract(s, e, destination, 0) stores.  Over the window's
+ * code units, with F = frac_digits in [0, 9]: D = the maximal run of '0' .. '9' at the window's start; D == 0 is NOT A NUMBER,
+ * D == 32 is OVERFLOW (the run fills the window and may go on).  With F > 0 and '.' behind the run, up to F digits behind it are
+ * the fraction, k of them; further digits are ignored (truncation, no rounding); without a '.', or with F == 0, k = 0.
+ *     value = int(run) * 10^F + int(fraction) * 10^(F - k)      ("12.5" at F = 0 is 12, "1." at F = 3 is 1000, "251.73" 251730)
+ * value > 2^63 - 1 is OVERFLOW.  There is no sign, no exponent and no thousands separator: the pattern "blk_-" reads the digits
+ * behind a minus.
+ * THE ROWS: fmx_hit_histogram_where_batch's call (its value patterns, terms, query_off, term_kind, where_of, edges, occurrences,
+ * kept, status and term_status) with one addition: edges == NULL with n_edges == 0 means B = 1, every line — then no line table is
+ * needed unless a pattern asks for a query.  Per row = i * B + b, over the kept hits of value pattern i whose line lies in bucket
+ * b and that parse: count[row] (int32); sum_lo[row], sum_hi[row] (uint64): the exact sum = sum_hi * 2^64 + sum_lo; min[row],
+ * max[row] (int64), 0 where count is 0; pct[row * P + j] (int64), P = n_permille in [0, 16], permille[j] in [0, 1000]: the
+ * nearest-rank percentile — with c = count[row] the element of the ascending values at index max(1, ceil(permille[j] * c / 1000))
+ * - 1, in 64-bit integer arithmetic; 0 where c is 0; permille 0 is the min, 1000 the max.  Per pattern: not_number[i], overflow[i]
+ * (int32) = the kept hits IN SOME BUCKET that did not parse, by reason.  For every i
+ *     sum over b of count[i * B + b] + not_number[i] + overflow[i] = the total of row i of fmx_hit_histogram_where_batch
+ * for the same call.  Every output is nullable except count.  On an index built without extraction every status is
+ * FMX_ST_NOT_ENABLED, all rows and counters are zero, occurrences and kept are still filled.  A window the packed extract ran
+ * literally hands its status to its pattern, as in fmx_field_values_batch.
+ * The packed stages up to the filter run as for the hits histogram (skipped with every where_of[i] < 0), then
+ * fmx_numbers_of_hits_dev over the kept hits: about 150 bytes of scratch per kept hit (fmx_numbers_of_hits_scratch_bytes), and no
+ * wait beyond the hits histogram's own — the rows have a known size.  Only the rows and the small per-pattern and per-term arrays
+ * come down.
+ * FMX_E_ARG as fmx_hit_histogram_where_batch (an index without a line table: only when edges are given or a pattern asks for a
+ * query) and for frac_digits outside [0, 9], n_permille outside [0, 16], a permille outside [0, 1000], (int64) n * B above 2^27,
+ * n * B * max(P, 1) above 2^27; FMX_E_NO_DEVICE for a handle that is not resident; FMX_E_NOMEM leaves nothing behind.  n == 0:
+ * FMX_OK, nothing is searched and term_status is zeroed. */
+int fmx_number_stats_where_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *term_pat,
+                                 const int32_t *term_off, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                 const int32_t *where_of, const int32_t *edges, int32_t n_edges, int32_t frac_digits, const int32_t *permille,
+                                 int32_t n_permille, int32_t *count, uint64_t *sum_lo, uint64_t *sum_hi, int64_t *min, int64_t *max,
+                                 int64_t *pct, int32_t *not_number, int32_t *overflow, int32_t *occurrences, int32_t *kept, int32_t *status,
+                                 int32_t *term_status);
+/* ... with class patterns as value patterns and as terms, as fmx_hit_histogram_where_class_batch; a position is one character of
+ * the pattern's length */
+int fmx_number_stats_where_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                       int32_t n, const uint16_t *term_alt, const int32_t *term_pos_off, int32_t term_n_pos,
+                                       const int32_t *term_off, int32_t n_terms, int32_t max_ranges, const int32_t *query_off,
+                                       const uint8_t *term_kind, int32_t q, const int32_t *where_of, const int32_t *edges, int32_t n_edges,
+                                       int32_t frac_digits, const int32_t *permille, int32_t n_permille, int32_t *count, uint64_t *sum_lo,
+                                       uint64_t *sum_hi, int64_t *min, int64_t *max, int64_t *pct, int32_t *not_number, int32_t *overflow,
+                                       int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *term_status);
+
 /* THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY (extract, FM:564-608, batched) — the host form of
  * fmx_extract_packed_offsets_dev + fmx_extract_packed_fill_dev (below: the layout, the statuses, how the work is cut).
  * host buffers, synchronous: text_off = n + 1 int64 (out), text_off[0] = 0; *chars = text_off[n] UTF-16 code units owned by the
@@ -739,6 +786,37 @@ int fmx_lines_histogram_dev(const fmx_index *idx, int32_t q, const int64_t *d_li
                             int32_t n_edges, int32_t *d_hist, void *d_ws, size_t ws_bytes, void *stream);
 int fmx_hits_histogram_dev(const fmx_index *idx, int32_t n, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, const int32_t *edges,
                            int32_t n_edges, int32_t *d_hist, void *d_ws, size_t ws_bytes, void *stream);
+/* THE NUMBER BEHIND A PATTERN over device pointers (the value of a hit, the rows and the invariant: fmx_number_stats_where_batch
+ * above).  Packed hits (d_hit_off, d_locs, n_hits) of n patterns exactly as fmx_hits_histogram_dev takes them — d_hit_off[0] may be
+ * non-zero, slots behind d_hit_off[n] and beyond n_hits are no hits, the order is SA-row order.  term_len (n, the patterns'
+ * lengths), edges (NULL with n_edges == 0: one bucket, every line, no line table needed) and permille are HOST arrays: validated,
+ * and copied into d_ws before the call returns.  d_count, d_sum_lo, d_sum_hi, d_min, d_max get n * B entries, d_pct n * B * P,
+ * d_not_number and d_overflow n; each is nullable except d_count; entries behind them keep the caller's values.  d_status
+ * (nullable, n ints the caller has initialised): a window the packed extract ran literally hands its status to its pattern; on an
+ * index without extraction every status is FMX_ST_NOT_ENABLED and every row and counter zero.
+ * A lane per slot makes the window and the key pattern | bucket (fences and up to 4,096 edges staged in LDS, as the hits
+ * histogram's key kernel); the packed extract fills all windows (redo launch included); a lane per slot parses its window into an
+ * int64 and the key pattern | code, the code in [0, B + 2]: a bucket, B = no bucket, B + 1 = not a number, B + 2 = overflow (the
+ * pattern n for a slot that is no hit); two stable rocPRIM radix sorts, by value over 63 bits and by key over the bits in use, give
+ * the order (key, value); two inclusive scans of the values' low and high halves give the running sums; a lane per (pattern,
+ * bucket) takes two lower bounds in the sorted keys and stores count, min (the first value), max (the last), the 128-bit sum from
+ * two differences, the percentiles by index; a lane per pattern stores not_number and overflow the same way.  Integers only, no
+ * atomics — the result does not depend on scheduling; lanes go to slots or to counters, never to patterns; the grids are
+ * fmx_hit_lines_geometry's and the extract honours `block` and `groups_per_cu`; asynchronous on `stream`, nothing is allocated,
+ * nothing is synchronised beyond the staged host copy of the small arrays.  d_ws: at least fmx_numbers_of_hits_scratch_bytes(n,
+ * n_hits, n_edges, n_permille) bytes (about 150 per slot: the window's 64, four 8-byte sort arrays, the ranges and offsets, the
+ * extract's scratch, rocPRIM's temporary storage); 0 for an empty call or a shape the call refuses.  n == 0: nothing is written;
+ * n_hits == 0: the rows and the per-pattern counters are zeroed and nothing else is written.
+ * FMX_E_ARG for null or negative arguments, n_hits > 2^31 - 1, (int64) n * B above 2^27, n * B * max(P, 1) above 2^27, frac_digits
+ * outside [0, 9], n_permille outside [0, 16], a permille outside [0, 1000], a negative term_len, the edge rules of
+ * fmx_hits_histogram_dev, an index without a line table when edges != NULL, a workspace that is too small (nothing is launched,
+ * nothing is written), a SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident. */
+size_t fmx_numbers_of_hits_scratch_bytes(int32_t n, int64_t n_hits, int32_t n_edges, int32_t n_permille);
+int fmx_numbers_of_hits_dev(const fmx_index *idx, int32_t n, const int32_t *term_len, const int64_t *d_hit_off, const int32_t *d_locs,
+                            int64_t n_hits, const int32_t *edges, int32_t n_edges, int32_t frac_digits, const int32_t *permille,
+                            int32_t n_permille, int32_t *d_count, uint64_t *d_sum_lo, uint64_t *d_sum_hi, int64_t *d_min, int64_t *d_max,
+                            int64_t *d_pct, int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status, void *d_ws, size_t ws_bytes,
+                            void *stream);
 /* CLASS PATTERNS over device pointers (d_alt, d_pos_off, d_pat_off: the three packed arrays of fmx_count_class_batch, in device
  * memory and trusted as the literal device forms trust theirs); asynchronous on `stream`, nothing is allocated or synchronised.
  * THE SEARCH keeps, per pattern, a frontier of SA ranges: the last position gives {C[c], C[c + 1]} of each of its codes, every

@@ -589,6 +589,71 @@ public:
         return h.counts;
     }
 
+    // statistics of the number behind a pattern, per bucket of lines (fmx.h "THE NUMBER BEHIND A PATTERN"): hitHistogramWhereBatch's
+    // patterns, queries, whereOf and edges (no edges at all: one bucket, every line — then a line table is needed only where a
+    // pattern asks for a query).  The number is the run of digits behind the pattern; with fracDigits in [0, 9] a '.' and up to
+    // that many digits more, scaled by 10^fracDigits ("251.73" at 3 is 251730).  Per row = i * B + b over the kept hits that parse:
+    // count, the exact sum = sumHi * 2^64 + sumLo, min, max, and pct[row * P + j] = the nearest-rank percentile permille[j] (up to
+    // 16, in thousandths); notNumber / overflow per pattern: the kept hits in some bucket that did not parse.  Statuses are not
+    // thrown by the batch form; numberStatsWhere answers one pattern and throws them.
+    struct NumberStats {
+        int32_t buckets = 0, permilles = 0;
+        std::vector<int32_t> count;
+        std::vector<uint64_t> sumLo, sumHi;
+        std::vector<int64_t> min, max, pct;
+        std::vector<int32_t> notNumber, overflow, occurrences, kept, status, termStatus;
+        double mean(size_t row) const {  // (a convenience of the host: the sum as a double)
+            return count[row] ? ((double)sumHi[row] * 18446744073709551616.0 + (double)sumLo[row]) / count[row] : 0.0;
+        }
+    };
+    NumberStats numberStatsWhereBatch(const std::vector<std::u16string> &patterns, const std::vector<Query> &queries,
+                                      const std::vector<int32_t> &whereOf, const std::vector<int32_t> &edges,
+                                      const std::vector<int32_t> &permille = {500, 950}, int32_t fracDigits = 0) const {
+        if (whereOf.size() != patterns.size()) throw std::invalid_argument("whereOf has one entry per pattern");
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        flattenQueries(queries, terms, kind, queryOff);
+        std::vector<uint16_t> chars, termChars;
+        std::vector<int32_t> off, termOff;
+        pack(patterns, chars, off);
+        pack(terms, termChars, termOff);
+        NumberStats out;
+        out.buckets = edges.empty() ? 1 : edges.size() > 1 ? (int32_t)edges.size() - 1 : 0;
+        out.permilles = (int32_t)permille.size();
+        const size_t n = patterns.size(), cells = n * (size_t)out.buckets;
+        out.count.assign(cells + 1, 0);
+        out.sumLo.assign(cells + 1, 0);
+        out.sumHi.assign(cells + 1, 0);
+        out.min.assign(cells + 1, 0);
+        out.max.assign(cells + 1, 0);
+        out.pct.assign(cells * permille.size() + 1, 0);
+        for (std::vector<int32_t> *v : {&out.notNumber, &out.overflow, &out.occurrences, &out.kept, &out.status}) v->assign(n + 1, 0);
+        out.termStatus.assign(terms.size(), 0);
+        detail::check(fmx_number_stats_where_batch(h_, chars.data(), off.data(), (int32_t)n, termChars.data(), termOff.data(), (int32_t)terms.size(),
+                                                   queryOff.data(), kind.data(), (int32_t)queries.size(), whereOf.data(),
+                                                   edges.empty() ? nullptr : edges.data(), (int32_t)edges.size(), fracDigits, permille.data(),
+                                                   (int32_t)permille.size(), out.count.data(), out.sumLo.data(), out.sumHi.data(), out.min.data(),
+                                                   out.max.data(), out.pct.data(), out.notNumber.data(), out.overflow.data(),
+                                                   out.occurrences.data(), out.kept.data(), out.status.data(), out.termStatus.data()),
+                      "fmx_number_stats_where_batch");
+        for (std::vector<int32_t> *v : {&out.count, &out.notNumber, &out.overflow, &out.occurrences, &out.kept, &out.status}) v->pop_back();
+        for (std::vector<uint64_t> *v : {&out.sumLo, &out.sumHi}) v->pop_back();
+        for (std::vector<int64_t> *v : {&out.min, &out.max, &out.pct}) v->pop_back();
+        return out;
+    }
+    NumberStats numberStatsWhere(const std::u16string &pattern, const Query &where, const std::vector<int32_t> &edges,
+                                 const std::vector<int32_t> &permille = {500, 950}, int32_t fracDigits = 0) const {
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        for (const std::vector<std::u16string> *g : {&where.all, &where.any, &where.none})
+            for (const std::u16string &t : *g)
+                if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const NumberStats s = numberStatsWhereBatch({pattern}, {where}, {0}, edges, permille, fracDigits);
+        detail::raise_for_status(s.status[0]);
+        for (int st : s.termStatus) detail::raise_for_status(st);
+        return s;
+    }
+
     // the text of ranges and of lines in ONE packed array (fmx.h "THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY"): range / line
     // i is chars[offsets[i] .. offsets[i + 1]) — what extract(start, stop, destination, 0) leaves in destination; memory follows
     // the sum of the lengths.  status[i] is the range's own (not thrown: one range out of the text does not hide the others);

@@ -3992,6 +3992,16 @@ int line_view(const fmx_index *idx, LineView *view) {
     *view = {static_cast<const int32_t *>(idx->d_line_table), idx->line_count, idx->n_cu};
     return FMX_OK;
 }
+int text_view(const fmx_index *idx, TextView *view) {
+    if (const int rc = require_fm_device(idx)) return rc;
+    *view = {line_text_length(idx), idx->dev.enable_extract != 0};
+    return FMX_OK;
+}
+int extract_windows(const fmx_index *idx, const ValuesWindows &w, int32_t n, void *stream) {
+    const int e = launch_extract_packed_offsets(idx->dev, w.start, w.stop, n, w.text_off, w.piece_off, w.status, w.scratch, w.scratch_bytes, stream);
+    if (e) return fail(FMX_E_HIP, std::string("extract packed offsets: ") + hipGetErrorString((hipError_t)e));
+    return extract_packed_fill_impl(idx, w.start, w.stop, n, w.text_off, w.piece_off, -1, w.chars, w.status, w.scratch, static_cast<hipStream_t>(stream));
+}
 int check_query_arrays(int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind) {
     return check_queries(n, q, query_off, term_kind);
 }
@@ -4020,7 +4030,8 @@ int values_between_call(const fmx_index *idx, const ValuesBatch &batch, const ui
     if ((rc = b.block((size_t)(n + 1) * 8, &d_koff)) || (rc = b.block((size_t)r.total * 4 + 8, &d_locs)) ||
         (rc = b.block((size_t)value_hits * 4 + 8, &d_kept)) || (rc = fill_hits(call, r, 0, r.total, d_locs)))
         return rc;
-    const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, d_koff, d_kept, &call, between_block};
+    const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, d_koff, d_kept, &call, between_block, idx,
+                           r.status ? r.status + n_terms : nullptr};
     if ((rc = between(hits, arg))) return rc;
     std::vector<int64_t> kept_off((size_t)n + 1);
     HIP_TRY(hipMemcpyAsync(kept_off.data(), d_koff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -4054,7 +4065,8 @@ int hits_stage_call(const fmx_index *idx, const ValuesBatch &batch, ValuesBetwee
     const hipStream_t st = call.stream.s;
     int32_t *d_locs = nullptr;
     if ((rc = call.blocks.block((size_t)r.total * 4 + 8, &d_locs)) || (rc = fill_hits(call, r, 0, r.total, d_locs))) return rc;
-    const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, nullptr, nullptr, &call, between_block};
+    const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, nullptr, nullptr, &call, between_block, idx,
+                           r.status ? r.status + n_terms : nullptr};
     if ((rc = stage(hits, arg))) return rc;
     if (occurrences && n > 0) HIP_TRY(hipMemcpyAsync(occurrences, r.counts + n_terms, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     if (status && n > 0) HIP_TRY(hipMemcpyAsync(status, r.status + n_terms, (size_t)n * 4, hipMemcpyDeviceToHost, st));

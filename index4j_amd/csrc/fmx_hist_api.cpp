@@ -75,13 +75,8 @@ int check_offsets(const int32_t *off, int32_t n, const char *what) {
     return FMX_OK;
 }
 
-// what the stages need of the call's arguments
-struct HistArgs {
-    const int32_t *query_off;
-    const uint8_t *term_kind;
-    int32_t q;
-    const int32_t *where_of;  // hits form: n entries
-    bool filters;             // hits form: a pattern asks for a query
+// what the stages need of the call's arguments: the queries and the filter (fmx_plan.hpp), then the edges and the outputs
+struct HistArgs : fmx::HitsFilter {
     const int32_t *edges;
     int32_t n_edges;
     int32_t *hist, *line_count;
@@ -89,7 +84,7 @@ struct HistArgs {
 };
 
 // the lines of the q queries from the terms' hits, no limit: line_off (q + 1) and lines on the device
-int query_lines_stage(const fmx::HitsBetween &h, const HistArgs &a, int64_t **d_line_off, int32_t **d_lines, int32_t *d_line_count) {
+int query_lines_stage(const fmx::HitsBetween &h, const fmx::HitsFilter &a, int64_t **d_line_off, int32_t **d_lines, int32_t *d_line_count) {
     const hipStream_t st = static_cast<hipStream_t>(h.stream);
     const int32_t bits = fmx::fm_query_key_width(a.q, h.view->count, fmx::query_lines_max_terms(a.q, a.query_off));
     if (bits > 64) return api_fail(FMX_E_ARG, "the key query | line | term would take " + std::to_string(bits) + " bits (at most 64)");
@@ -138,30 +133,14 @@ int hits_stage(const fmx::HitsBetween &h, void *arg) {
     int32_t *d_hist = nullptr;
     int rc;
     if ((rc = h.block(h.call, cells * 4 + 8, reinterpret_cast<void **>(&d_hist)))) return rc;
-    // the value patterns' part of the packed block: hit_off + n_terms starts at term_hits, not at 0; the slots are all `total`
-    const int64_t *d_off = h.hit_off + h.n_terms;
-    const int32_t *d_locs = h.locs;
-    int64_t n_hits = h.total;
+    const int64_t *d_off = nullptr;
+    const int32_t *d_locs = nullptr;
+    int64_t n_hits = 0;
     if (value_hits == 0) {
         if (cells > 0) HIST_HIP_TRY(hipMemsetAsync(d_hist, 0, cells * 4, st));
         a.kept_off.assign((size_t)h.n + 1, 0);
     } else {
-        if (a.filters) {
-            int64_t *d_line_off = nullptr, *d_koff = nullptr;
-            int32_t *d_lines = nullptr, *d_kept = nullptr;
-            const size_t ws_bytes = fmx::hits_in_lines_scratch_bytes(h.n, h.total);
-            void *ws = nullptr;
-            if ((a.q > 0 && (rc = query_lines_stage(h, a, &d_line_off, &d_lines, nullptr))) ||
-                (rc = h.block(h.call, ((size_t)h.n + 1) * 8, reinterpret_cast<void **>(&d_koff))) ||
-                (rc = h.block(h.call, (size_t)value_hits * 4 + 8, reinterpret_cast<void **>(&d_kept))) || (rc = h.block(h.call, ws_bytes, &ws)))
-                return rc;
-            const int e = fmx::launch_hits_in_lines(h.view->table, h.view->count, h.view->n_cu, h.n, a.where_of, d_line_off, d_lines, 0, INT32_MAX,
-                                                    d_off, d_locs, h.total, d_koff, d_kept, ws, ws_bytes, st);
-            if (e) return api_fail(FMX_E_HIP, std::string("hits in lines: ") + hipGetErrorString((hipError_t)e));
-            d_off = d_koff;
-            d_locs = d_kept;
-            n_hits = value_hits;  // (kept_off[n] <= value_hits: the slots behind are ignored)
-        }
+        if ((rc = fmx::kept_hits_stage(h, a, &d_off, &d_locs, &n_hits))) return rc;
         const size_t ws_bytes = fmx::hits_histogram_scratch_bytes(h.n, n_hits, a.n_edges);
         void *ws = nullptr;
         if ((rc = h.block(h.call, ws_bytes, &ws))) return rc;
@@ -188,7 +167,7 @@ int lines_call_args(const fmx_index *idx, int32_t n, const int32_t *query_off, c
     if (!view.table) return no_line_table();
     const int32_t bits = fmx::fm_query_key_width(q, view.count, fmx::query_lines_max_terms(q, query_off));
     if (bits > 64) return api_fail(FMX_E_ARG, "the key query | line | term would take " + std::to_string(bits) + " bits (at most 64)");
-    *args = HistArgs{query_off, term_kind, q, nullptr, false, edges, n_edges, hist, line_count, {}};
+    *args = HistArgs{{query_off, term_kind, q, nullptr, false}, edges, n_edges, hist, line_count, {}};
     *done = n == 0 || q == 0;
     if (*done) {  // (no terms: no query has a line; nothing is searched)
         zero(hist, (size_t)q * (size_t)(n_edges - 1));
@@ -205,9 +184,8 @@ int hits_call_args(const fmx_index *idx, int32_t n, int32_t n_terms, const int32
         (rc = check_edges(edges, n_edges, n)) || (rc = fmx::line_view(idx, &view)))
         return rc;
     if (!view.table) return no_line_table();  // (the buckets are lines: with or without a filter)
-    bool filters = false;
-    for (int32_t i = 0; i < n; ++i) filters = filters || where_of[i] >= 0;
-    *args = HistArgs{query_off, term_kind, q, where_of, filters, edges, n_edges, hist, nullptr, std::vector<int64_t>((size_t)n + 1)};
+    *args = HistArgs{{query_off, term_kind, q, where_of, fmx::hits_filter_asked(n, where_of)}, edges, n_edges, hist, nullptr,
+                     std::vector<int64_t>((size_t)n + 1)};
     *done = n == 0;
     if (n == 0) zero(term_status, (size_t)n_terms);  // (nothing is searched: the terms are not judged)
     return FMX_OK;
@@ -218,6 +196,108 @@ void kept_of(const HistArgs &args, int32_t n, int32_t *kept) {
 }
 
 }  // namespace
+
+// what the hits forms of this file share with fmx_stats_api.cpp (fmx_plan.hpp)
+namespace fmx {
+
+bool hits_filter_asked(int32_t n, const int32_t *where_of) {
+    for (int32_t i = 0; i < n; ++i)
+        if (where_of[i] >= 0) return true;
+    return false;
+}
+
+int check_hits_filter(int32_t n, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q, const int32_t *where_of) {
+    if (const int rc = check_query_arrays(n_terms, q, query_off, term_kind)) return rc;
+    return check_where_of(n, where_of, q);
+}
+
+int kept_hits_stage(const HitsBetween &h, const HitsFilter &a, const int64_t **d_off, const int32_t **d_locs, int64_t *n_hits) {
+    // the value patterns' part of the packed block: hit_off + n_terms starts at term_hits, not at 0; the slots are all `total`
+    *d_off = h.hit_off + h.n_terms;
+    *d_locs = h.locs;
+    *n_hits = h.total;
+    if (!a.filters) return FMX_OK;
+    const int64_t value_hits = h.total - h.term_hits;
+    int64_t *d_line_off = nullptr, *d_koff = nullptr;
+    int32_t *d_lines = nullptr, *d_kept = nullptr;
+    const size_t ws_bytes = hits_in_lines_scratch_bytes(h.n, h.total);
+    void *ws = nullptr;
+    int rc;
+    if ((a.q > 0 && (rc = query_lines_stage(h, a, &d_line_off, &d_lines, nullptr))) ||
+        (rc = h.block(h.call, ((size_t)h.n + 1) * 8, reinterpret_cast<void **>(&d_koff))) ||
+        (rc = h.block(h.call, (size_t)value_hits * 4 + 8, reinterpret_cast<void **>(&d_kept))) || (rc = h.block(h.call, ws_bytes, &ws)))
+        return rc;
+    const int e = launch_hits_in_lines(h.view->table, h.view->count, h.view->n_cu, h.n, a.where_of, d_line_off, d_lines, 0, INT32_MAX, *d_off,
+                                       *d_locs, h.total, d_koff, d_kept, ws, ws_bytes, static_cast<hipStream_t>(h.stream));
+    if (e) return api_fail(FMX_E_HIP, std::string("hits in lines: ") + hipGetErrorString((hipError_t)e));
+    *d_off = d_koff;
+    *d_locs = d_kept;
+    *n_hits = value_hits;  // (kept_off[n] <= value_hits: the slots behind are ignored)
+    return FMX_OK;
+}
+
+int check_literal_batches(const int32_t *pat_off, int32_t n, const int32_t *term_off, int32_t n_terms) {
+    int rc;
+    if ((n > 0 && (rc = check_offsets(pat_off, n, "pattern"))) || (n_terms > 0 && (rc = check_offsets(term_off, n_terms, "term")))) return rc;
+    return FMX_OK;
+}
+
+int check_class_batches(const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
+                        const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms) {
+    int rc;
+    if ((rc = check_offsets(pos_off, n_pos, "position")) || (rc = check_offsets(pat_off, n, "pattern"))) return rc;
+    if (pat_off[n] > n_pos) return api_fail(FMX_E_ARG, "pattern offsets end behind the positions");
+    if (pos_off[n_pos] > 0 && !alt) return api_fail(FMX_E_ARG, "bad arguments");
+    if (n_terms > 0) {
+        if ((rc = check_offsets(term_pos_off, term_n_pos, "term position")) || (rc = check_offsets(term_off, n_terms, "term"))) return rc;
+        if (term_off[n_terms] > term_n_pos) return api_fail(FMX_E_ARG, "term offsets end behind the positions");
+        if (term_pos_off[term_n_pos] > 0 && !term_alt) return api_fail(FMX_E_ARG, "bad arguments");
+    }
+    return FMX_OK;
+}
+
+// ONE batch: the terms in front, the value patterns behind them
+int merge_literal_batch(const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *term_pat, const int32_t *term_off,
+                        int32_t n_terms, MergedBatch *m, ValuesBatch *batch) {
+    const int64_t term_chars = n_terms > 0 ? (int64_t)term_off[n_terms] - term_off[0] : 0, pat_chars = (int64_t)pat_off[n] - pat_off[0];
+    if (term_chars + pat_chars > INT32_MAX) return api_fail(FMX_E_ARG, "more than 2^31 - 1 characters in one batch");
+    if ((term_chars > 0 && !term_pat) || (pat_chars > 0 && !pat)) return api_fail(FMX_E_ARG, "bad arguments");
+    m->chars.assign((size_t)(term_chars + pat_chars) + 1, 0);
+    m->off.assign((size_t)n_terms + n + 1, 0);
+    for (int32_t t = 0; t < n_terms; ++t) m->off[(size_t)t] = term_off[t] - term_off[0];
+    for (int32_t i = 0; i <= n; ++i) m->off[(size_t)n_terms + i] = (int32_t)(term_chars + (pat_off[i] - pat_off[0]));
+    for (int64_t k = 0; k < term_chars; ++k) m->chars[(size_t)k] = term_pat[term_off[0] + k];
+    for (int64_t k = 0; k < pat_chars; ++k) m->chars[(size_t)(term_chars + k)] = pat[pat_off[0] + k];
+    *batch = ValuesBatch{m->chars.data(), nullptr, 0, m->off.data(), n_terms, n, 0};
+    return FMX_OK;
+}
+
+// ... position by position
+int merge_class_batch(const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
+                      const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges,
+                      MergedBatch *m, ValuesBatch *batch) {
+    m->chars.clear();
+    m->pos.assign(1, 0);
+    m->off.assign(1, 0);
+    auto append = [&](const uint16_t *a, const int32_t *pos, const int32_t *off, int32_t count) {
+        for (int32_t i = 0; i < count; ++i) {
+            for (int32_t j = off[i]; j < off[i + 1]; ++j) {
+                m->chars.insert(m->chars.end(), a + pos[j], a + pos[j + 1]);
+                m->pos.push_back((int32_t)m->chars.size());
+            }
+            m->off.push_back((int32_t)m->pos.size() - 1);
+        }
+    };
+    if ((int64_t)(n_terms > 0 ? term_pos_off[term_n_pos] : 0) + pos_off[n_pos] > INT32_MAX)
+        return api_fail(FMX_E_ARG, "more than 2^31 - 1 alternatives in one batch");
+    if (n_terms > 0) append(term_alt, term_pos_off, term_off, n_terms);
+    append(alt, pos_off, pat_off, n);
+    m->chars.push_back(0);  // (never an empty array)
+    *batch = ValuesBatch{m->chars.data(), m->pos.data(), (int32_t)m->pos.size() - 1, m->off.data(), n_terms, n, max_ranges};
+    return FMX_OK;
+}
+
+}  // namespace fmx
 
 extern "C" {
 
@@ -314,19 +394,11 @@ int fmx_hit_histogram_where_batch(const fmx_index *idx, const uint16_t *pat, con
     HistArgs args;
     bool done = false;
     int rc;
-    if ((n > 0 && (rc = check_offsets(pat_off, n, "pattern"))) || (n_terms > 0 && (rc = check_offsets(term_off, n_terms, "term")))) return rc;
+    if ((rc = fmx::check_literal_batches(pat_off, n, term_off, n_terms))) return rc;
     if ((rc = hits_call_args(idx, n, n_terms, query_off, term_kind, q, where_of, edges, n_edges, hist, term_status, &args, &done)) || done) return rc;
-    const int64_t term_chars = n_terms > 0 ? (int64_t)term_off[n_terms] - term_off[0] : 0, pat_chars = (int64_t)pat_off[n] - pat_off[0];
-    if (term_chars + pat_chars > INT32_MAX) return api_fail(FMX_E_ARG, "more than 2^31 - 1 characters in one batch");
-    if ((term_chars > 0 && !term_pat) || (pat_chars > 0 && !pat)) return api_fail(FMX_E_ARG, "bad arguments");
-    // ONE batch: the terms in front, the value patterns behind them
-    std::vector<uint16_t> all_chars((size_t)(term_chars + pat_chars) + 1);
-    std::vector<int32_t> all_off((size_t)n_terms + n + 1);
-    for (int32_t t = 0; t < n_terms; ++t) all_off[(size_t)t] = term_off[t] - term_off[0];
-    for (int32_t i = 0; i <= n; ++i) all_off[(size_t)n_terms + i] = (int32_t)(term_chars + (pat_off[i] - pat_off[0]));
-    for (int64_t k = 0; k < term_chars; ++k) all_chars[(size_t)k] = term_pat[term_off[0] + k];
-    for (int64_t k = 0; k < pat_chars; ++k) all_chars[(size_t)(term_chars + k)] = pat[pat_off[0] + k];
-    const fmx::ValuesBatch batch{all_chars.data(), nullptr, 0, all_off.data(), n_terms, n, 0};
+    fmx::MergedBatch merged;
+    fmx::ValuesBatch batch;
+    if ((rc = fmx::merge_literal_batch(pat, pat_off, n, term_pat, term_off, n_terms, &merged, &batch))) return rc;
     if ((rc = fmx::hits_stage_call(idx, batch, hits_stage, &args, occurrences, status, nullptr, term_status))) return rc;
     kept_of(args, n, kept);
     return FMX_OK;
@@ -343,35 +415,15 @@ int fmx_hit_histogram_where_class_batch(const fmx_index *idx, const uint16_t *al
         (n > 0 && (!where_of || !hist)) || (n_terms > 0 && (!term_pos_off || !term_off)) || max_ranges < 1 || max_ranges > FMX_CLASS_RANGES_MAX)
         return api_fail(FMX_E_ARG, "bad arguments");
     int rc;
-    if ((rc = check_offsets(pos_off, n_pos, "position")) || (rc = check_offsets(pat_off, n, "pattern"))) return rc;
-    if (pat_off[n] > n_pos) return api_fail(FMX_E_ARG, "pattern offsets end behind the positions");
-    if (pos_off[n_pos] > 0 && !alt) return api_fail(FMX_E_ARG, "bad arguments");
-    if (n_terms > 0) {
-        if ((rc = check_offsets(term_pos_off, term_n_pos, "term position")) || (rc = check_offsets(term_off, n_terms, "term"))) return rc;
-        if (term_off[n_terms] > term_n_pos) return api_fail(FMX_E_ARG, "term offsets end behind the positions");
-        if (term_pos_off[term_n_pos] > 0 && !term_alt) return api_fail(FMX_E_ARG, "bad arguments");
-    }
+    if ((rc = fmx::check_class_batches(alt, pos_off, n_pos, pat_off, n, term_alt, term_pos_off, term_n_pos, term_off, n_terms))) return rc;
     HistArgs args;
     bool done = false;
     if ((rc = hits_call_args(idx, n, n_terms, query_off, term_kind, q, where_of, edges, n_edges, hist, term_status, &args, &done)) || done) return rc;
-    // ONE batch: the terms in front, the value patterns behind them, position by position
-    std::vector<uint16_t> all_alt;
-    std::vector<int32_t> all_pos{0}, all_pat{0};
-    auto append = [&](const uint16_t *a, const int32_t *pos, const int32_t *off, int32_t count) {
-        for (int32_t i = 0; i < count; ++i) {
-            for (int32_t j = off[i]; j < off[i + 1]; ++j) {
-                all_alt.insert(all_alt.end(), a + pos[j], a + pos[j + 1]);
-                all_pos.push_back((int32_t)all_alt.size());
-            }
-            all_pat.push_back((int32_t)all_pos.size() - 1);
-        }
-    };
-    if ((int64_t)(n_terms > 0 ? term_pos_off[term_n_pos] : 0) + pos_off[n_pos] > INT32_MAX)
-        return api_fail(FMX_E_ARG, "more than 2^31 - 1 alternatives in one batch");
-    if (n_terms > 0) append(term_alt, term_pos_off, term_off, n_terms);
-    append(alt, pos_off, pat_off, n);
-    all_alt.push_back(0);  // (never an empty array)
-    const fmx::ValuesBatch batch{all_alt.data(), all_pos.data(), (int32_t)all_pos.size() - 1, all_pat.data(), n_terms, n, max_ranges};
+    fmx::MergedBatch merged;
+    fmx::ValuesBatch batch;
+    if ((rc = fmx::merge_class_batch(alt, pos_off, n_pos, pat_off, n, term_alt, term_pos_off, term_n_pos, term_off, n_terms, max_ranges, &merged,
+                                     &batch)))
+        return rc;
     if ((rc = fmx::hits_stage_call(idx, batch, hits_stage, &args, occurrences, status, nullptr, term_status))) return rc;
     kept_of(args, n, kept);
     return FMX_OK;

@@ -162,6 +162,20 @@ class FmIndexBuilder:
         return FmIndex(text, self._sample_rate, self._enable_extraction, device=device, build_device=self._build_device)
 
 
+class NumberStats:
+    """row i of a number_stats_where_batch answer: count, min, max (B), pct (B, P) as numpy arrays, sum as exact Python ints"""
+
+    def __init__(self, out, i):
+        self.count, self.min, self.max, self.pct = out["count"][i], out["min"][i], out["max"][i], out["pct"][i]
+        self.sum = [(int(hi) << 64) | int(lo) for lo, hi in zip(out["sum_lo"][i], out["sum_hi"][i])]
+        self.not_number, self.overflow = int(out["not_number"][i]), int(out["overflow"][i])
+        self.occurrences, self.kept = int(out["occurrences"][i]), int(out["kept"][i])
+
+    def mean(self):
+        """sum / count per bucket as floats (nan where a bucket is empty): a convenience of the host"""
+        return np.array([s / c if c else float("nan") for s, c in zip(self.sum, self.count.tolist())], dtype=np.float64)
+
+
 class FmIndex:
     """fm/FmIndex.java query surface.  `device=None` keeps the index on the host (build / save /
     load only); any query then fails loudly."""
@@ -689,6 +703,57 @@ class FmIndex:
                                          term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms, int(max_ranges)), n, n_terms,
                                         query_off, term_kind, where_of, edges, want_counts)
 
+    # ---- statistics of the number behind a pattern, per bucket of lines (fmx.h "THE NUMBER BEHIND A PATTERN") ----
+    def _number_stats_call(self, call, where, args, n, n_terms, query_off, term_kind, where_of, edges, permille, frac_digits):
+        query_off, term_kind, where_of, q, _, _ = self._where_arrays(n, n_terms, query_off, term_kind, where_of, None)
+        if edges is None:
+            edges_ptr, n_edges, B = None, 0, 1
+        else:
+            edges, B = self._edges(edges)
+            edges_ptr, n_edges = edges.ctypes.data, len(edges)
+        permille = np.ascontiguousarray(permille, dtype=np.int32).reshape(-1)
+        P = len(permille)
+        count = np.zeros((n, B), dtype=np.int32)
+        sum_lo, sum_hi = np.zeros((n, B), dtype=np.uint64), np.zeros((n, B), dtype=np.uint64)
+        vmin, vmax = np.zeros((n, B), dtype=np.int64), np.zeros((n, B), dtype=np.int64)
+        pct = np.zeros((n, B, P), dtype=np.int64)
+        not_number, overflow, occurrences, kept, status = (np.zeros(n, dtype=np.int32) for _ in range(5))
+        term_status = np.zeros(n_terms, dtype=np.int32)
+        check(call(self._h, *args, query_off.ctypes.data, term_kind.ctypes.data, q, where_of.ctypes.data, edges_ptr, n_edges, int(frac_digits),
+                   permille.ctypes.data, P, count.ctypes.data, sum_lo.ctypes.data, sum_hi.ctypes.data, vmin.ctypes.data, vmax.ctypes.data,
+                   pct.ctypes.data, not_number.ctypes.data, overflow.ctypes.data, occurrences.ctypes.data, kept.ctypes.data, status.ctypes.data,
+                   term_status.ctypes.data), where)
+        return dict(count=count, sum_lo=sum_lo, sum_hi=sum_hi, min=vmin, max=vmax, pct=pct, not_number=not_number, overflow=overflow,
+                    occurrences=occurrences, kept=kept, status=status, term_status=term_status)
+
+    def number_stats_where_batch(self, chars, offsets, term_chars, term_offsets, query_off, term_kind, where_of, edges=None, permille=(500, 950),
+                                 frac_digits=0):
+        """statistics of the number behind every hit of every pattern per bucket of lines, only within the lines of a query
+        (fmx_number_stats_where_batch): hit_histogram_where_batch's patterns, terms, query_off, term_kind, where_of and edges
+        (edges=None: one bucket, every line).  The number is the run of digits behind the pattern, with frac_digits in [0, 9] a
+        '.' and up to that many digits more, scaled by 10^frac_digits; permille: up to 16 nearest-rank percentiles in
+        thousandths.  Returns a dict of arrays: count (n, B) int32; sum_lo, sum_hi (n, B) uint64, the exact sum sum_hi * 2^64 +
+        sum_lo; min, max (n, B) int64; pct (n, B, P) int64; not_number, overflow, occurrences, kept, status (n); term_status."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        term_chars = np.ascontiguousarray(term_chars, dtype=np.uint16)
+        term_offsets = np.ascontiguousarray(term_offsets, dtype=np.int32)
+        n, n_terms = len(offsets) - 1, len(term_offsets) - 1
+        return self._number_stats_call(lib.fmx_number_stats_where_batch, "fmx_number_stats_where_batch",
+                                       (chars.ctypes.data, offsets.ctypes.data, n, term_chars.ctypes.data, term_offsets.ctypes.data, n_terms), n,
+                                       n_terms, query_off, term_kind, where_of, edges, permille, frac_digits)
+
+    def number_stats_where_class_batch(self, alt, pos_off, pat_off, term_alt, term_pos_off, term_pat_off, query_off, term_kind, where_of, edges=None,
+                                       permille=(500, 950), frac_digits=0, max_ranges=CLASS_RANGES_DEFAULT):
+        """number_stats_where_batch with class patterns as value patterns and as terms (fmx_number_stats_where_class_batch); same
+        returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        term_alt, term_pos_off, term_pat_off, term_n_pos, n_terms = self._class_arrays(term_alt, term_pos_off, term_pat_off)
+        return self._number_stats_call(lib.fmx_number_stats_where_class_batch, "fmx_number_stats_where_class_batch",
+                                       (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, term_alt.ctypes.data,
+                                        term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms, int(max_ranges)), n, n_terms,
+                                       query_off, term_kind, where_of, edges, permille, frac_digits)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -982,6 +1047,34 @@ class FmIndex:
         for st in [out[1][0]] + out[4].tolist():
             raise_for_status(st)
         return out[0][0]
+
+    def number_stats(self, pattern, edges=None, where=None, permille=(500, 950), frac_digits=0, ignore_case=False):
+        """sum, min, max and percentiles of the number behind `pattern` per bucket of lines (edges as in hit_histogram; None: one
+        bucket, every line), with where=dict(all=, any=, none=) only over the hits in the lines that match that query: stats
+        sum(size) p95(size) by minute where line has addStoredBlock.  "size 67108864" is 67108864; with frac_digits=3 "251.73" is
+        251730.  Returns a NumberStats: count, sum (Python ints, exact), min, max (B), pct (B, P), mean(), and not_number,
+        overflow, occurrences, kept as ints.  Only the rows come down."""
+        p = as_chars(pattern)
+        terms, kinds = [], []
+        for kind, word in enumerate(("all", "any", "none")):
+            group = (where or {}).get(word, ())
+            for t in ([group] if isinstance(group, str) else group):  # (a lone str is one term)
+                terms.append(as_chars(t))
+                kinds.append(kind)
+        if where is not None and set(where) - {"all", "any", "none"}:
+            raise ValueError("where takes all=, any= and none=")
+        if min((len(t) for t in terms + [p]), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        query_off, where_of = ([0, len(terms)], [0]) if where is not None else ([0], [-1])
+        if ignore_case:
+            out = self.number_stats_where_class_batch(*pack_class_patterns([_ignore_case(p)]), *pack_class_patterns([_ignore_case(t) for t in terms]),
+                                                      query_off, np.array(kinds, np.uint8), where_of, edges, permille, frac_digits)
+        else:
+            out = self.number_stats_where_batch(*pack_patterns([p]), *pack_patterns(terms), query_off, np.array(kinds, np.uint8), where_of, edges,
+                                                permille, frac_digits)
+        for st in [out["status"][0]] + out["term_status"].tolist():
+            raise_for_status(st)
+        return NumberStats(out, 0)
 
     def line_text(self, lines):
         """the lines with these ids as a list of str (the boundary excluded); raises for an id that is no line"""

@@ -119,3 +119,172 @@ def assert_is_reference_array(text, sa):
     assert (np.sort(sa) == np.arange(n + 1)).all()
     for i in range(1, n):
         assert suffix_less(text, int(sa[i]), int(sa[i + 1])), i
+
+
+# ---- the edge table: texts at the fence table's, the sort's and the locate scan's edges, one pattern set per text ----
+
+NAIVE_MAX = 4200  # naive_suffix_array holds every suffix as a key: for texts up to here only
+
+
+def naive_suffix_array(text):
+    """[n] + sorted(range(n), key=lambda i: text[i:]) as int32: independent of SA-IS and of the device.  The keys are the
+    suffixes' big-endian bytes, whose order is the order of the uint16 sequences (a proper prefix first, as compareTo)."""
+    t = np.ascontiguousarray(text, dtype=np.uint16)
+    n = len(t)
+    assert n <= NAIVE_MAX
+    b = t.astype(">u2").tobytes()
+    return np.array([n] + sorted(range(n), key=lambda i: b[2 * i:]), dtype=np.int32)
+
+
+def _fibonacci_word(n):
+    a, b = "a", "ab"
+    while len(b) < n:
+        a, b = b, b + a
+    return b[:n]
+
+
+def _edge_texts():
+    from common import hdfs_text
+
+    u16 = lambda s: np.frombuffer(s.encode("utf-16-le"), dtype=np.uint16).copy()
+    word = np.random.default_rng(17).integers(0, 3, 17) + ord("a")
+    nul13 = [0, 5, 0, 0, 5, 5, 0, 1, 0, 0, 0, 5, 0]  # the text of test_text_with_nul_and_short_suffixes
+    mix = np.array([0, 0, 1, 0xD800, 0xFFFF])[np.random.default_rng(257).integers(0, 5, 257)]
+    texts = {
+        "empty": u16(""),
+        "x": u16("x"),
+        "ba": u16("ba"),
+        "a300": u16("a" * 300),
+        "a4096": u16("a" * 4096),
+        "ab2048": u16("ab" * 2048),
+        "word17x20": np.tile(word, 20),
+        "fibonacci4181": u16(_fibonacci_word(4181)),
+        "nul40": np.zeros(40),
+        "nulmix257": mix,
+        "binary4097": np.random.default_rng(4097).integers(0, 2, 4097),  # one more than 4,096 fences: shift 1, a partial group
+        "nul13": np.array(nul13),
+        "hdfs20000": u16(hdfs_text())[:20000],
+    }
+    return {k: np.ascontiguousarray(v, dtype=np.uint16) for k, v in texts.items()}
+
+
+EDGE_TEXTS = _edge_texts()
+NUL_TEXTS = ("nul40", "nulmix257", "nul13")
+EDGE_SEED = 20
+
+
+def fence_rows(n, most, chars):
+    """(n_fences, shift) as sa_fence_settings derives them, and whether the key table fits the 64 KiB that are staged"""
+    s = 0
+    while most > 0 and ((n + (1 << s) - 1) >> s) > most:
+        s += 1
+    nf = ((n + (1 << s) - 1) >> s) if most > 0 else 0
+    return nf, s, nf * chars * 2 <= 64 * 1024
+
+
+def edge_patterns(text, sa, rng):
+    """the pattern set of one text (uint16 arrays): the fixed ones first (edge_fixed_patterns), then 300 substrings in four
+    forms each, then the keys of about 64 fence rows of the default table cut at, below and above K = 8 and K = 16"""
+    t = np.ascontiguousarray(text, dtype=np.uint16)
+    n = len(t)
+    pats = edge_fixed_patterns(t, sa)
+    for _ in range(300 if n else 0):
+        ln = int(rng.integers(1, min(39, n) + 1))
+        s = int(rng.integers(0, n - ln + 1))
+        cut = t[s:s + ln]
+        up, down = cut.copy(), cut.copy()
+        up[-1] = (int(cut[-1]) + 1) & 0xFFFF  # (0xFFFF + 1 = 0, 0 - 1 = 0xFFFF)
+        down[-1] = (int(cut[-1]) - 1) & 0xFFFF
+        pats += [cut, up, down, np.append(cut, np.uint16(0))]
+    _, shift, _ = fence_rows(n, 4096, 8)
+    step = -(-max(1, n // 64) >> shift) << shift  # a multiple of the fence distance: every row taken is a fence
+    for j in range(0, n, step):
+        pos = int(sa[j])
+        pats += [t[pos:pos + ln] for ln in (1, 7, 8, 9, 15, 16, 17)]
+    return pats
+
+
+def edge_fixed_patterns(text, sa):
+    """empty, [0], [0xFFFF], the whole text, the text plus its first char and plus '\\0' (longer than every suffix), and the
+    largest suffix itself"""
+    t = np.ascontiguousarray(text, dtype=np.uint16)
+    n = len(t)
+    z = np.zeros(1, np.uint16)
+    return [t[:0], z, np.array([0xFFFF], np.uint16), t, np.concatenate([t, t[:1]]), np.concatenate([t, z]), t[int(sa[n]):]]
+
+
+def occurrences16(text, p):
+    """how often p occurs in text (the empty pattern: at every position and at the end), by comparing at every position"""
+    n, m = len(text), len(p)
+    if m > n:
+        return 0
+    hit = np.ones(n - m + 1, dtype=bool)
+    for k in range(m):
+        hit &= text[k:k + n - m + 1] == p[k]
+    return int(hit.sum())
+
+
+class EdgeCase:
+    """one text of the table: its array (naive_suffix_array up to NAIVE_MAX chars, else the host's SA-IS checked by
+    assert_is_reference_array), its patterns, their (left, right) by ref_left_right, and what the set was checked to hold"""
+
+    def __init__(self, name):
+        self.name = name
+        self.text = EDGE_TEXTS[name]
+        n = len(self.text)
+        if n <= NAIVE_MAX:
+            self.sa = naive_suffix_array(self.text)
+        else:
+            import index4j_amd as ia
+
+            self.sa = ia.SuffixArray(self.text, device=None, build_device=-1).construct().getSuffixArray()
+            assert_is_reference_array(self.text, self.sa)
+        self.pats = edge_patterns(self.text, self.sa, np.random.default_rng(EDGE_SEED))
+        tl, sl = self.text.tolist(), self.sa.tolist()
+        lr = np.array([ref_left_right(tl, sl, p.tolist()) for p in self.pats], dtype=np.int32).reshape(-1, 2)
+        self.left, self.right = lr[:, 0].copy(), lr[:, 1].copy()
+        self.counts = self.right - self.left
+        self.pat, self.off = pack(self.pats)
+        self.stats = self._non_vacuity()
+
+    def _non_vacuity(self):
+        """from the reference alone: patterns with and without hits, quirk hits, and (NUL texts) short fences / real NULs"""
+        t, sa, n = self.text, self.sa, len(self.text)
+        top = int(sa[n])
+        quirk = 0
+        for p, c in zip(self.pats, self.counts):
+            if len(p) <= n - top and (t[top:top + len(p)] == p).all():  # the largest suffix starts with p
+                assert int(c) == occurrences16(t, p) - 1, self.name
+                quirk += 1
+        nf, shift, _ = fence_rows(n, 4096, 8)
+        short = real_nul = 0
+        for j in range(nf):
+            pos = int(sa[j << shift])
+            flen = min(8, n - pos)
+            short += flen < 8
+            real_nul += bool((t[pos:pos + flen] == 0).any())
+        stats = {"patterns": len(self.pats), "hits": int((self.counts > 0).sum()), "misses": int((self.counts == 0).sum()),
+                 "quirk": quirk, "short_fences": int(short), "nul_fences": int(real_nul)}
+        if n >= 40:
+            assert stats["hits"] >= 50 and stats["misses"] >= 50 and quirk >= 1, (self.name, stats)
+        if self.name in NUL_TEXTS:
+            assert short >= 1 and real_nul >= 1, (self.name, stats)
+        return stats
+
+
+def pack(pats):
+    """(chars, offsets) of a list of uint16 patterns, in the layout the batch calls take"""
+    off = np.zeros(len(pats) + 1, dtype=np.int32)
+    np.cumsum([len(p) for p in pats], out=off[1:])
+    chars = np.concatenate([np.asarray(p, dtype=np.uint16) for p in pats] + [np.zeros(0, np.uint16)])
+    return np.ascontiguousarray(chars, dtype=np.uint16), off
+
+
+_CASES = {}
+
+
+def edge_case(name):
+    """the EdgeCase of a text, computed once per process and never changed"""
+    if name not in _CASES:
+        _CASES[name] = EdgeCase(name)
+    return _CASES[name]

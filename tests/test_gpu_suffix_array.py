@@ -190,10 +190,22 @@ def test_launch_shapes(block, gpc, tmp_path_factory):
         ia.lib.fmx_set_option(b"groups_per_cu", ia._lib.ENV_OPTIONS.get("groups_per_cu", 16))
 
 
-@pytest.mark.parametrize("fences,chars", [(0, 8), (4096, 8), (8192, 4), (32768, 1)])
-def test_fence_settings_change_no_answer(fences, chars):
+@pytest.fixture(scope="module")
+def fence_reference(tmp_path_factory):
+    """the text and patterns of test_fence_settings_change_no_answer, and right - left of every pattern by the search routines
+    on the host (no fence table) over the array of host SA-IS: nothing of it comes from the device"""
+    sim = sim_lib(tmp_path_factory.mktemp("sahostsim"))
     text = ia.synth_log(1 << 20, seed=13)
     pat, off, _ = ia.synth_patterns(text, 12, 200000, seed=5)
+    sa = ia.SuffixArray(text, device=None, build_device=-1).construct().getSuffixArray()
+    left, right, nf = sim_search(sim, text, sa, [pat[off[i]:off[i + 1]] for i in range(len(off) - 1)], most=0)
+    assert nf == 0
+    return text, pat, off, right - left
+
+
+@pytest.mark.parametrize("fences,chars", [(0, 8), (4096, 8), (8192, 4), (32768, 1)])
+def test_fence_settings_change_no_answer(fences, chars, fence_reference):
+    text, pat, off, exp = fence_reference
     base = None
     try:
         assert ia.lib.fmx_set_option(b"sa_fences", fences) == 0
@@ -205,3 +217,4 @@ def test_fence_settings_change_no_answer(fences, chars):
         ia.lib.fmx_set_option(b"sa_fence_chars", 8)
     base = ia.SuffixArray(text, device=0).construct().count_batch(pat, off)
     assert (got == base).all()
+    assert (got == exp).all() and (base == exp).all(), int(np.nonzero((got != exp) | (base != exp))[0][0])

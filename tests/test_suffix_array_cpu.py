@@ -13,7 +13,8 @@ import pytest
 
 import index4j_amd as ia
 from common import GOLDEN, hdfs_text
-from sa_cases import (BANANA, ROOT, assert_is_reference_array, ref_left_right, reference_draws, sim_lib, sim_search)
+from sa_cases import (BANANA, EDGE_TEXTS, NAIVE_MAX, ROOT, assert_is_reference_array, edge_case, fence_rows,
+                      naive_suffix_array, ref_left_right, reference_draws, sim_lib, sim_search)
 
 
 def host_sa(text):
@@ -117,6 +118,24 @@ def test_text_with_nul_and_short_suffixes(sim):
         for chars in (1, 2, 3, 8):
             left, right, _ = sim_search(sim, t, sa, pats, most=most, chars=chars)
             assert [(int(a), int(b)) for a, b in zip(left, right)] == exp, (most, chars)
+
+
+def test_edge_table(sim):
+    """every text of sa_cases.EDGE_TEXTS with its whole pattern set through the device search routines, at fence tables from
+    none to one fence per row and keys of 1 to 16 chars (odd ones too), against ref_left_right; and host SA-IS against the
+    naive sort.  What each set was checked to hold (from the reference alone) is printed."""
+    for name in EDGE_TEXTS:
+        c = edge_case(name)
+        print(name, c.stats)
+        if len(c.text) <= NAIVE_MAX:
+            assert host_sa(c.text).getSuffixArray().tolist() == naive_suffix_array(c.text).tolist(), name
+        for most in (0, 1, 2, 16, 64, 4096, 32768):
+            for chars in (1, 2, 3, 8, 15, 16):
+                left, right, nf = sim_search(sim, c.text, c.sa, c.pats, most=most, chars=chars)
+                assert nf == fence_rows(len(c.text), most, chars)[0], (name, most, chars)
+                bad = np.nonzero((left != c.left) | (right != c.right))[0]
+                assert len(bad) == 0, (name, most, chars, c.pats[bad[0]].tolist(), int(left[bad[0]]), int(right[bad[0]]),
+                                       int(c.left[bad[0]]), int(c.right[bad[0]]))
 
 
 def test_stream_bytes_of_banana():

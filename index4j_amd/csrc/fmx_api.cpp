@@ -5,6 +5,7 @@
 #include "fmx_device.hpp"
 #include "fmx_build_stage.hpp"
 #include "fmx_hit_values.hpp"
+#include "fmx_host_stage.hpp"
 #include "fmx_model.hpp"
 #include "fmx_options.hpp"
 #include "fmx_plan.hpp"
@@ -719,20 +720,10 @@ struct Scratch {
 
 }  // namespace
 
-// The ABI never throws (an exception crossing into a JVM through JNI aborts it): every entry point that returns a status runs
-// inside this guard.  What can throw in here: allocations sized by the caller's data, thread creation.
-template <class F>
-static int guarded(F &&body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        return fail(FMX_E_UNSUPPORTED, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(FMX_E_UNSUPPORTED, std::string("internal error: ") + e.what());
-    }
-}
+using fmx::guarded;  // (fmx_abi.hpp: every entry point that returns a status runs inside this guard)
 
-// fmx_multi.cpp: a shard's failure, reported by a worker thread, becomes the CALLING thread's fmx_last_error
+// fmx_abi.hpp: `fail` for the other files of the C-ABI layer (fmx_multi.cpp: a shard's failure, reported by a worker thread, becomes
+// the CALLING thread's fmx_last_error)
 namespace fmx {
 int api_fail(int code, const std::string &msg) { return fail(code, msg); }
 // fmx_sa_api.cpp: a SuffixArray behind an fmx_index handle
@@ -2121,8 +2112,7 @@ static int packed_finish(PackedCall &call, RangeStage &r, int32_t *counts, int32
 
 // ---- lines: the line table of a resident index, packed hits -> packed distinct lines (fmx_hit_lines.hip) ------------------------
 static int require_line_table(const fmx_index *idx) {
-    if (!idx->d_line_table) return fail(FMX_E_ARG, "the index has no line table (call fmx_line_table_build)");
-    return FMX_OK;
+    return idx->d_line_table ? FMX_OK : fmx::no_line_table();
 }
 // the text as the caller handed it over: getInputLength() counts the terminator the constructor appends (FM:300-305)
 static int32_t line_text_length(const fmx_index *idx) { return idx->hdr.length > 0 ? (int32_t)idx->hdr.length - 1 : 0; }
@@ -2284,9 +2274,7 @@ static int check_queries(int32_t n, int32_t q, const int32_t *query_off, const u
     return FMX_OK;
 }
 static int check_query_key_width(const fmx_index *idx, int32_t q, const int32_t *query_off) {
-    const int32_t bits = fmx::fm_query_key_width(q, idx->line_count, fmx::query_lines_max_terms(q, query_off));
-    if (bits > 64) return fail(FMX_E_ARG, "the key query | line | term would take " + std::to_string(bits) + " bits (at most 64)");
-    return FMX_OK;
+    return fmx::check_query_key_width(q, idx->line_count, query_off);
 }
 
 size_t fmx_query_lines_scratch_bytes(int32_t n, int32_t q, int64_t n_hits) { return fmx::query_lines_scratch_bytes(n, q, n_hits); }
@@ -3982,7 +3970,7 @@ int fmx_field_values_class_batch(const fmx_index *idx, const uint16_t *alt, cons
     });
 }
 
-// fmx_where_api.cpp's way into the sequence above (fmx_plan.hpp: values_between_call): ONE range stage over the merged batch — the
+// fmx_where_api.cpp's way into the sequence above (fmx_host_stage.hpp: values_between_call): ONE range stage over the merged batch — the
 // terms' hits in front, hit_off[n_terms] comes down with the total —, every hit into one block, the caller's stage, ONE wait for
 // kept_off, the values stages over the kept hits.  occurrences / status are the value patterns', term_status the terms'.
 extern "C++" {
@@ -4006,30 +3994,35 @@ int check_query_arrays(int32_t n, int32_t q, const int32_t *query_off, const uin
     return check_queries(n, q, query_off, term_kind);
 }
 static int between_block(void *call, size_t bytes, void **out) { return static_cast<PackedCall *>(call)->blocks.block(bytes, out); }
-int values_between_call(const fmx_index *idx, const ValuesBatch &batch, const uint16_t *stop, int32_t n_stop, int32_t max_len,
-                        ValuesBetweenFn between, void *arg, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
-                        int32_t *occurrences, int32_t *status, int32_t *kept, int32_t *term_status) {
-    const int32_t n_terms = batch.n_terms, n = batch.n, n_all = n_terms + n;
-    PackedCall call(idx);
-    RangeStage r;
-    ValuesShape shape;
-    LineView view;
-    r.mark = n_terms;
-    const bool want_status = status || term_status;
-    int rc = line_view(idx, &view);
+// what both calls begin with: the line view, the range stage over the merged batch (hit_off[n_terms] comes down with the total),
+// the refusal of more hits than one block holds, the block for every hit and the fill
+static int merged_hits(PackedCall &call, const ValuesBatch &batch, bool want_status, LineView &view, RangeStage &r, int32_t **d_locs) {
+    const int32_t n_all = batch.n_terms + batch.n;
+    r.mark = batch.n_terms;
+    int rc = line_view(call.blocks.idx, &view);
     if (rc) return rc;
     rc = batch.pos_off ? class_ranges(call, batch.chars, batch.pos_off, batch.n_pos, batch.pat_off, n_all, batch.max_ranges, true, want_status, r)
                        : literal_ranges(call, batch.chars, batch.pat_off, n_all, -1, true, false, want_status, r);
     if (rc) return rc;
     if (r.total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
-    Scratch &b = call.blocks;
-    const hipStream_t st = call.stream.s;
-    const int64_t value_hits = r.total - r.mark_total;
+    if ((rc = call.blocks.block((size_t)r.total * 4 + 8, d_locs))) return rc;
+    return fill_hits(call, r, 0, r.total, *d_locs);
+}
+int values_between_call(const fmx_index *idx, const ValuesBatch &batch, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                        ValuesBetweenFn between, void *arg, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
+                        int32_t *occurrences, int32_t *status, int32_t *kept, int32_t *term_status) {
+    const int32_t n_terms = batch.n_terms, n = batch.n;
+    PackedCall call(idx);
+    RangeStage r;
+    ValuesShape shape;
+    LineView view;
     int32_t *d_locs = nullptr, *d_kept = nullptr;
     int64_t *d_koff = nullptr;
-    if ((rc = b.block((size_t)(n + 1) * 8, &d_koff)) || (rc = b.block((size_t)r.total * 4 + 8, &d_locs)) ||
-        (rc = b.block((size_t)value_hits * 4 + 8, &d_kept)) || (rc = fill_hits(call, r, 0, r.total, d_locs)))
+    int rc;
+    if ((rc = merged_hits(call, batch, status || term_status, view, r, &d_locs)) || (rc = call.blocks.block((size_t)(n + 1) * 8, &d_koff)) ||
+        (rc = call.blocks.block((size_t)(r.total - r.mark_total) * 4 + 8, &d_kept)))
         return rc;
+    const hipStream_t st = call.stream.s;
     const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, d_koff, d_kept, &call, between_block, idx,
                            r.status ? r.status + n_terms : nullptr};
     if ((rc = between(hits, arg))) return rc;
@@ -4044,27 +4037,20 @@ int values_between_call(const fmx_index *idx, const ValuesBatch &batch, const ui
     if (status) HIP_TRY(hipMemcpyAsync(status, r.status + n_terms, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     if (term_status && n_terms > 0) HIP_TRY(hipMemcpyAsync(term_status, r.status, (size_t)n_terms * 4, hipMemcpyDeviceToHost, st));
     if ((rc = packed_finish(call, r, nullptr, nullptr, nullptr, counts))) return rc;
-    for (int32_t i = 0; i < n && kept; ++i) kept[i] = (int32_t)(kept_off[(size_t)i + 1] - kept_off[(size_t)i]);
+    kept_of(kept_off.data(), n, kept);
     values_hand_over(shape, counts, text_off, chars);
     return FMX_OK;
 }
 int hits_stage_call(const fmx_index *idx, const ValuesBatch &batch, ValuesBetweenFn stage, void *arg, int32_t *occurrences, int32_t *status,
                     int32_t *term_occurrences, int32_t *term_status) {
-    const int32_t n_terms = batch.n_terms, n = batch.n, n_all = n_terms + n;
+    const int32_t n_terms = batch.n_terms, n = batch.n;
     PackedCall call(idx);
     RangeStage r;
     LineView view;
-    r.mark = n_terms;
-    const bool want_status = status || term_status;
-    int rc = line_view(idx, &view);
-    if (rc) return rc;
-    rc = batch.pos_off ? class_ranges(call, batch.chars, batch.pos_off, batch.n_pos, batch.pat_off, n_all, batch.max_ranges, true, want_status, r)
-                       : literal_ranges(call, batch.chars, batch.pat_off, n_all, -1, true, false, want_status, r);
-    if (rc) return rc;
-    if (r.total > 0x7fffffff) return fail(FMX_E_ARG, "more than 2^31 - 1 hits in one batch");
-    const hipStream_t st = call.stream.s;
     int32_t *d_locs = nullptr;
-    if ((rc = call.blocks.block((size_t)r.total * 4 + 8, &d_locs)) || (rc = fill_hits(call, r, 0, r.total, d_locs))) return rc;
+    int rc;
+    if ((rc = merged_hits(call, batch, status || term_status, view, r, &d_locs))) return rc;
+    const hipStream_t st = call.stream.s;
     const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, nullptr, nullptr, &call, between_block, idx,
                            r.status ? r.status + n_terms : nullptr};
     if ((rc = stage(hits, arg))) return rc;

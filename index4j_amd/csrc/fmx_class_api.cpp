@@ -2,20 +2,13 @@
 // fmx_class_search.hip's launchers: argument checks, the image form, the launch.  Of a handle this file sees what fmx::class_view
 // hands out.  The host forms (fmx_count_class_batch, fmx_locate_all_class_batch, fmx_match_query_class_batch) run these stages from
 // fmx_api.cpp, in the one sequence of the packed host forms.
-#include "../../include/fmx.h"
 #include "fmx_device.hpp"
-#include "fmx_plan.hpp"
+#include "fmx_host_stage.hpp"
 
 #include <hip/hip_runtime.h>
 
-#include <climits>
-#include <exception>
-#include <new>
-#include <string>
-
 namespace fmx {
 #include "fmx_kernel_api.hpp"
-int api_fail(int code, const std::string &msg);  // fmx_api.cpp: the calling thread's fmx_last_error
 }  // namespace fmx
 namespace fmxc {
 #include "fmx_kernel_api.hpp"
@@ -24,26 +17,7 @@ namespace fmxc {
 namespace {
 
 using fmx::api_fail;
-
-template <class F>
-int guarded(F &&body) {  // (the ABI never throws)
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        return api_fail(FMX_E_UNSUPPORTED, "out of host memory");
-    } catch (const std::exception &e) {
-        return api_fail(FMX_E_UNSUPPORTED, std::string("internal error: ") + e.what());
-    }
-}
-
-#define CLASS_HIP_TRY(expr)                                                                  \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            (void)hipGetLastError();                                                         \
-            return api_fail(FMX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-        }                                                                                    \
-    } while (0)
+using fmx::guarded;
 
 int launch_search(const fmx::ClassView &v, const uint16_t *alt, const int32_t *pos_off, const int32_t *pat_off, int32_t n, int32_t max_ranges,
                   int64_t *range_cnt, int32_t *counts, int32_t *status, const int64_t *range_off, int32_t *ranges, hipStream_t st) {
@@ -73,7 +47,7 @@ int fmx_class_ranges_count_dev(const fmx_index *idx, const uint16_t *d_alt, cons
     if (const int rc = fmx::class_view(idx, &view)) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     if (n == 0) {
-        CLASS_HIP_TRY(hipMemsetAsync(d_range_off, 0, sizeof(int64_t), st));
+        FMX_HIP_TRY(hipMemsetAsync(d_range_off, 0, sizeof(int64_t), st));
         return FMX_OK;
     }
     if (scratch_bytes < fmx::class_ranges_scratch_bytes(n)) return api_fail(FMX_E_ARG, "scratch smaller than fmx_class_ranges_scratch_bytes");
@@ -110,8 +84,8 @@ int fmx_class_hit_offsets_dev(const fmx_index *idx, int32_t n, const int64_t *d_
     if (const int rc = fmx::class_view(idx, &view)) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     if (n == 0) {
-        CLASS_HIP_TRY(hipMemsetAsync(d_hit_off, 0, sizeof(int64_t), st));
-        CLASS_HIP_TRY(hipMemsetAsync(d_range_hit_off, 0, sizeof(int64_t), st));
+        FMX_HIP_TRY(hipMemsetAsync(d_hit_off, 0, sizeof(int64_t), st));
+        FMX_HIP_TRY(hipMemsetAsync(d_range_hit_off, 0, sizeof(int64_t), st));
         return FMX_OK;
     }
     if (scratch_bytes < fmx::hit_offsets_scratch_bytes((int32_t)m)) return api_fail(FMX_E_ARG, "scratch smaller than fmx_class_hit_offsets_scratch_bytes");

@@ -1,0 +1,140 @@
+// fmx_host_stage.hpp — the host-stage layer of the C ABI: what the feature files (fmx_class_api.cpp, fmx_where_api.cpp,
+// fmx_hist_api.cpp, fmx_stats_api.cpp) see of a handle and of the packed host sequence of fmx_api.cpp, and what they share among
+// themselves.  Host code only: no .hip file includes it.
+//   fmx_api.cpp          the views of a handle, extract_windows, check_query_arrays, values_between_call, hits_stage_call
+//   fmx_host_batch.cpp   the checks of a call's HOST arrays and the merge of terms and value patterns into ONE batch: no HIP
+//                        runtime call, so that the CPU suite links it as plain C++ (tests/cpp/san_merged_batch.cpp)
+//   fmx_host_stage.cpp   the stages on the device: the lines of the queries, the filter over the value patterns' hits
+// Every function that returns int returns an FMX_* code (fmx::api_fail has set the message).
+#pragma once
+
+#include "fmx_abi.hpp"
+#include "fmx_plan.hpp"
+
+#include <climits>
+#include <vector>
+
+namespace fmx {
+
+// ---- fmx_api.cpp: a resident FM handle after the checks of every FM device entry point (0 = *view is filled) -------------------
+// the image a class search launches over
+struct ClassView {
+    const DevIndex *dev;
+    int n_cu, device;
+    bool compact;
+};
+int class_view(const ::fmx_index *idx, ClassView *view);
+// the line table (table == nullptr: fmx_line_table_build has not run)
+struct LineView {
+    const int32_t *table;
+    int32_t count;  // boundaries in the table
+    int n_cu;
+};
+int line_view(const ::fmx_index *idx, LineView *view);
+// what the windows of hits need
+struct TextView {
+    int32_t text_len;  // getInputLength() - 1
+    bool extract;      // built with extraction
+};
+int text_view(const ::fmx_index *idx, TextView *view);
+// both stages of the packed extract over n ranges on the device (the launcher the values stage uses), into the regions of a
+// ValuesWindows
+int extract_windows(const ::fmx_index *idx, const ValuesWindows &w, int32_t n, void *stream);
+// the HOST arrays that cut n terms into q queries, as fmx_match_query_batch judges them (its return value)
+int check_query_arrays(int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind);
+
+// ---- fmx_api.cpp: the packed host sequence over a MERGED batch -----------------------------------------------------------------
+// values_between_call: a range stage, the fill, the values stages, ONE result allocation, the per-pattern arrays, the last wait,
+// over n_terms filter terms in front and n value patterns behind them — literal (pos_off == nullptr: chars / pat_off are
+// fmx_count_batch's) or class (alt / pos_off / pat_off are fmx_count_class_batch's) — with a stage of the caller's between the fill
+// and the values stages.  `between` sees every hit of the merged batch on the device and leaves the value patterns' kept hits as
+// (kept_off, kept_locs), asynchronously on `stream`; its device blocks come from block() and live until the call has synchronised.
+struct HitsBetween {
+    const LineView *view;
+    void *stream;
+    int32_t n_terms, n;
+    const int64_t *hit_off;      // n_terms + n + 1 (device)
+    const int32_t *locs;         // `total` hits (device)
+    int64_t term_hits, total;    // hit_off[n_terms], hit_off[n_terms + n]
+    int64_t *kept_off;           // n + 1 (device, out)
+    int32_t *kept_locs;          // room for total - term_hits (device, out)
+    void *call;
+    int (*block)(void *call, size_t bytes, void **out);
+    const ::fmx_index *idx;      // the handle of the call
+    int32_t *status;             // the value patterns' statuses (device, n; nullptr: the call asks for none)
+};
+struct ValuesBatch {
+    const uint16_t *chars;
+    const int32_t *pos_off;  // nullptr: literal patterns
+    int32_t n_pos;
+    const int32_t *pat_off;
+    int32_t n_terms, n, max_ranges;
+};
+typedef int (*ValuesBetweenFn)(const HitsBetween &hits, void *arg);
+int values_between_call(const ::fmx_index *idx, const ValuesBatch &batch, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                        ValuesBetweenFn between, void *arg, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
+                        int32_t *occurrences, int32_t *status, int32_t *kept, int32_t *term_status);
+// hits_stage_call: the same sequence up to the caller's stage and no further — ONE range stage over the merged batch, every hit
+// into one block, `stage`, the per-pattern arrays, the last wait.  kept_off / kept_locs of HitsBetween are NULL: the stage takes
+// what it needs from block().  What it copies to the host asynchronously on `stream` has arrived when the call returns FMX_OK.
+// occurrences / status are the value patterns', term_occurrences / term_status the terms' (each nullable).
+int hits_stage_call(const ::fmx_index *idx, const ValuesBatch &batch, ValuesBetweenFn stage, void *arg, int32_t *occurrences, int32_t *status,
+                    int32_t *term_occurrences, int32_t *term_status);
+
+// ---- fmx_host_batch.cpp: the HOST arrays of a call ------------------------------------------------------------------------------
+int no_line_table();  // the refusal of a call that needs the line table of an index without one
+// offsets that start at or above 0 and never decrease (what the range stages ask of theirs: judged ahead of the merge)
+int check_offsets(const int32_t *off, int32_t n, const char *what);
+// the offset arrays of the value patterns and of the terms, literal and class
+int check_literal_batches(const int32_t *pat_off, int32_t n, const int32_t *term_off, int32_t n_terms);
+int check_class_batches(const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
+                        const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms);
+// ONE batch, the terms in front, the value patterns behind them; *batch points into *m.  The offsets have been judged.
+struct MergedBatch {
+    std::vector<uint16_t> chars;
+    std::vector<int32_t> pos, off;
+};
+int merge_literal_batch(const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *term_pat, const int32_t *term_off,
+                        int32_t n_terms, MergedBatch *m, ValuesBatch *batch);
+int merge_class_batch(const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
+                      const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges,
+                      MergedBatch *m, ValuesBatch *batch);
+// the queries, which query each value pattern asks for and the window of lines
+struct HitsFilter {
+    const int32_t *query_off;
+    const uint8_t *term_kind;
+    int32_t q;
+    const int32_t *where_of;   // n entries, each -1 .. q - 1
+    int32_t line_lo, line_hi;  // the window of lines (0 .. INT32_MAX: every line)
+    bool filters;              // hits_filter_asked
+};
+// the call filters at all: a pattern asks for a query, or the window is not 0 .. INT32_MAX
+bool hits_filter_asked(int32_t n, const int32_t *where_of, int32_t line_lo = 0, int32_t line_hi = INT32_MAX);
+int check_where_of(int32_t n, const int32_t *where_of, int32_t q);
+// edges by fmx_line_hist.hpp's rules (n_edges >= 2, edges[0] >= 0, never decreasing)
+int check_edges_array(const int32_t *edges, int32_t n_edges);
+
+// kept[i] = kept_off[i + 1] - kept_off[i] (kept nullable); a[0, count) = 0 (a nullable)
+inline void kept_of(const int64_t *kept_off, int32_t n, int32_t *kept) {
+    for (int32_t i = 0; i < n && kept; ++i) kept[i] = (int32_t)(kept_off[(size_t)i + 1] - kept_off[(size_t)i]);
+}
+template <class T>
+void zero(T *a, size_t count) {
+    for (size_t i = 0; i < count && a; ++i) a[i] = 0;
+}
+
+// ---- fmx_host_stage.cpp: inside a stage of values_between_call / hits_stage_call ------------------------------------------------
+// the refusal of queries whose sort key query | line | term is wider than 64 bits (count: the boundaries of the line table)
+int check_query_key_width(int32_t q, int32_t count, const int32_t *query_off);
+// the lines of the f.q > 0 queries from the terms' hits, no limit: *d_line_off (q + 1) and *d_lines on the device, from block();
+// d_line_count (device, q entries; nullable)
+int query_lines_stage(const HitsBetween &h, const HitsFilter &f, int64_t **d_line_off, int32_t **d_lines, int32_t *d_line_count);
+// the value patterns' hits that pass the filter, into (kept_off: n + 1, kept_locs: room for total - term_hits): the lines of the
+// queries where the call filters and has queries, then fmx_hits_in_lines_dev's launcher.  A call that does not filter runs it
+// without a line table (every hit is kept), so an index without one still answers.  h.n > 0 and a value pattern has a hit.
+int hits_in_lines_stage(const HitsBetween &h, const HitsFilter &f, int64_t *kept_off, int32_t *kept_locs);
+// the same for a stage that reads the hits where they lie: (*d_off: n + 1, *d_locs, *n_hits slots) — the packed block's own part
+// when the call does not filter, else what hits_in_lines_stage keeps, in blocks from block()
+int kept_hits_stage(const HitsBetween &h, const HitsFilter &f, const int64_t **d_off, const int32_t **d_locs, int64_t *n_hits);
+
+}  // namespace fmx

@@ -4,7 +4,7 @@
 // shards (fmx_shard_range), shard r runs the SINGLE-index entry point on replica r from a host thread of its own, and stores
 // into its own slice of the caller's arrays.  No collective, no exchange on the query path (SURVEY 8e scheme (i)); the image
 // itself travels once, in fmx_replicate (fmx_api.cpp).  Everything here sits on top of the public C ABI.
-#include "../../include/fmx.h"
+#include "fmx_abi.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -17,10 +17,6 @@
 #include <thread>
 #include <utility>
 #include <vector>
-
-namespace fmx {
-int api_fail(int code, const std::string &msg);  // fmx_api.cpp: sets the calling thread's fmx_last_error
-}
 
 namespace {
 

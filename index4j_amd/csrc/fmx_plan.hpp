@@ -1,12 +1,10 @@
-// fmx_plan.hpp — what the plan stage of a batch (fmx_kernels.hip: k_plan_codes, k_plan_scatter) hands to k_count.
-// Shared by the launchers and the C-ABI layer.
+// fmx_plan.hpp — what the plan stage of a batch (fmx_kernels.hip: k_plan_codes, k_plan_scatter) hands to k_count, and the
+// launchers of the .hip files that are compiled once.  Shared by the launchers and the C-ABI layer; what only the C-ABI layer
+// sees — the views of a handle, the packed host sequence, the merged batch — lives in fmx_host_stage.hpp.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
-#include <vector>
-
-struct fmx_index;  // the handle of include/fmx.h (class_view)
 
 namespace fmx {
 
@@ -71,14 +69,6 @@ int launch_class_range_offsets(void *scratch, size_t scratch_bytes, int32_t n, i
 int launch_class_hit_offsets(const int32_t *ranges, int32_t m, const int64_t *range_off, int32_t n, int64_t *range_hit_off,
                              int64_t *hit_off, void *scratch, size_t scratch_bytes, void *stream);
 int launch_class_fold_status(const int64_t *range_off, int32_t n, int32_t m, const int32_t *range_status, int32_t *status, void *stream);
-// fmx_api.cpp, for fmx_class_api.cpp: the resident FM image behind a handle, after the checks of every FM device entry point
-// (their return value; 0 = *view is filled)
-struct ClassView {
-    const DevIndex *dev;
-    int n_cu, device;
-    bool compact;
-};
-int class_view(const ::fmx_index *idx, ClassView *view);
 
 // fmx_hit_lines.hip — the line table of a resident index and packed hits -> packed distinct lines (fmx_line_table_build,
 // fmx_line_bounds_*, fmx_lines_of_hits_dev).  Compiled once, like fmx_hit_offsets.hip.  The launchers return a hipError_t as int;
@@ -175,7 +165,7 @@ int launch_hits_histogram(const int32_t *T, int32_t count, int n_cu, int32_t n, 
 // [0, 1000]) are HOST arrays; they are judged again and copied into the workspace before launch_numbers_ranges returns.  The C-ABI
 // layer runs three steps on one stream over one workspace, as for the values stage:
 //   launch_numbers_ranges  window [s, e) and key pattern | bucket of every slot, into the regions numbers_windows names;
-//   the packed extract     extract_windows (below) over those n_hits ranges;
+//   the packed extract     extract_windows (fmx_host_stage.hpp) over those n_hits ranges;
 //   launch_numbers_rows    the parse, the two sorts, the two running sums, the rows (count is required, every other output
 //                          nullable) and the per-pattern counters; status (nullable): a window the extract ran literally hands its
 //                          status to its pattern.
@@ -190,93 +180,5 @@ int launch_numbers_ranges(const int32_t *T, int32_t count, int32_t text_len, int
 int launch_numbers_rows(int n_cu, int32_t n, const int64_t *hit_off, int64_t n_hits, int32_t n_edges, int32_t frac_digits, int32_t n_permille,
                         int32_t *count, uint64_t *sum_lo, uint64_t *sum_hi, int64_t *min, int64_t *max, int64_t *pct, int32_t *not_number,
                         int32_t *overflow, int32_t *status, void *ws, size_t ws_bytes, void *stream);
-
-// fmx_api.cpp, for fmx_where_api.cpp.  line_view: the line table of a resident FM handle after the checks of every FM device entry
-// point (their return value; 0 = *view is filled; table == nullptr: fmx_line_table_build has not run).
-struct LineView {
-    const int32_t *table;
-    int32_t count;  // boundaries in the table
-    int n_cu;
-};
-int line_view(const ::fmx_index *idx, LineView *view);
-// fmx_api.cpp, for fmx_stats_api.cpp.  text_view: what the windows of hits need of a resident FM handle, after the same checks.
-// extract_windows: both stages of the packed extract over n ranges on the device (the launcher the values stage uses), into the
-// regions of a ValuesWindows; an FMX_* code (the message is set).
-struct TextView {
-    int32_t text_len;  // getInputLength() - 1
-    bool extract;      // built with extraction
-};
-int text_view(const ::fmx_index *idx, TextView *view);
-int extract_windows(const ::fmx_index *idx, const ValuesWindows &w, int32_t n, void *stream);
-// the HOST arrays that cut n terms into q queries, as fmx_match_query_batch judges them (its return value)
-int check_query_arrays(int32_t n, int32_t q, const int32_t *query_off, const uint8_t *term_kind);
-// values_between_call: the packed host sequence of the values forms (a range stage, the fill, the values stages, ONE result
-// allocation, the per-pattern arrays, the last wait) over a MERGED batch — n_terms filter terms in front, then n value patterns,
-// literal (pos_off == nullptr: chars / pat_off are fmx_count_batch's) or class (alt / pos_off / pat_off are fmx_count_class_batch's)
-// — with a stage of the caller's between the fill and the values stages.  `between` sees every hit of the merged batch on the
-// device and leaves the value patterns' kept hits as (kept_off, kept_locs), asynchronously on `stream`; its device blocks come
-// from block() and live until the call has synchronised.  It returns an FMX_* code (fmx::api_fail sets the message).
-struct HitsBetween {
-    const LineView *view;
-    void *stream;
-    int32_t n_terms, n;
-    const int64_t *hit_off;      // n_terms + n + 1 (device)
-    const int32_t *locs;         // `total` hits (device)
-    int64_t term_hits, total;    // hit_off[n_terms], hit_off[n_terms + n]
-    int64_t *kept_off;           // n + 1 (device, out)
-    int32_t *kept_locs;          // room for total - term_hits (device, out)
-    void *call;
-    int (*block)(void *call, size_t bytes, void **out);
-    const ::fmx_index *idx;      // the handle of the call
-    int32_t *status;             // the value patterns' statuses (device, n; nullptr: the call asks for none)
-};
-struct ValuesBatch {
-    const uint16_t *chars;
-    const int32_t *pos_off;  // nullptr: literal patterns
-    int32_t n_pos;
-    const int32_t *pat_off;
-    int32_t n_terms, n, max_ranges;
-};
-typedef int (*ValuesBetweenFn)(const HitsBetween &hits, void *arg);
-int values_between_call(const ::fmx_index *idx, const ValuesBatch &batch, const uint16_t *stop, int32_t n_stop, int32_t max_len,
-                        ValuesBetweenFn between, void *arg, int64_t *val_off, int32_t **counts, int64_t **text_off, uint16_t **chars,
-                        int32_t *occurrences, int32_t *status, int32_t *kept, int32_t *term_status);
-// hits_stage_call, for fmx_hist_api.cpp: the same sequence up to the caller's stage and no further — ONE range stage over the merged
-// batch, every hit into one block, `stage`, the per-pattern arrays, the last wait.  kept_off / kept_locs of HitsBetween are NULL:
-// the stage takes what it needs from block().  What it copies to the host asynchronously on `stream` has arrived when the call
-// returns FMX_OK.  occurrences / status are the value patterns', term_occurrences / term_status the terms' (each nullable).
-int hits_stage_call(const ::fmx_index *idx, const ValuesBatch &batch, ValuesBetweenFn stage, void *arg, int32_t *occurrences, int32_t *status,
-                    int32_t *term_occurrences, int32_t *term_status);
-
-// fmx_hist_api.cpp, for fmx_stats_api.cpp: what the hits forms over hits_stage_call share.  Each returns an FMX_* code (the message
-// is set).
-//   HitsFilter             the HOST arrays of the queries and which query each value pattern asks for; filters: one does
-//   check_hits_filter      check_query_arrays, then where_of (n entries, each -1 .. q - 1)
-//   kept_hits_stage        inside a stage: the value patterns' hits as (*d_off: n + 1, *d_locs, *n_hits slots) — the lines of the
-//                          queries and fmx_hits_in_lines_dev's filter where the call filters, else the packed block's own part
-//   check_*_batches        the offset arrays of the value patterns and of the terms, as the range stages ask of theirs
-//   merge_*_batch          ONE batch, the terms in front, the value patterns behind them; *batch points into *m
-struct HitsFilter {
-    const int32_t *query_off;
-    const uint8_t *term_kind;
-    int32_t q;
-    const int32_t *where_of;  // n entries
-    bool filters;             // a pattern asks for a query
-};
-bool hits_filter_asked(int32_t n, const int32_t *where_of);
-int check_hits_filter(int32_t n, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q, const int32_t *where_of);
-int kept_hits_stage(const HitsBetween &h, const HitsFilter &f, const int64_t **d_off, const int32_t **d_locs, int64_t *n_hits);
-struct MergedBatch {
-    std::vector<uint16_t> chars;
-    std::vector<int32_t> pos, off;
-};
-int check_literal_batches(const int32_t *pat_off, int32_t n, const int32_t *term_off, int32_t n_terms);
-int check_class_batches(const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
-                        const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms);
-int merge_literal_batch(const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *term_pat, const int32_t *term_off,
-                        int32_t n_terms, MergedBatch *m, ValuesBatch *batch);
-int merge_class_batch(const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
-                      const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges,
-                      MergedBatch *m, ValuesBatch *batch);
 
 }  // namespace fmx

@@ -5,7 +5,7 @@
 // Construction (SA:89-91): the reference calls jsuffixarrays' SuffixArrays.create (QSufSort), whose array has n + 1 entries,
 // the empty suffix n first.  That is the suffix array of text -> 1 + rank(char) with a unique 0 appended, which is unique:
 // the device's prefix doubling (fmx_sa_gpu.hip) and the host's SA-IS (fmx_sais.hpp) both give it.
-#include "../../include/fmx.h"
+#include "fmx_abi.hpp"
 #include "fmx_build_stage.hpp"
 #include "fmx_sa_index.hpp"
 #include "fmx_sais.hpp"
@@ -31,26 +31,6 @@ struct DevBuf {
     }
 };
 
-#define SA_HIP(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            (void)hipGetLastError();                                                               \
-            return api_fail(FMX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-        }                                                                                          \
-    } while (0)
-
-template <class F>
-int guarded(F &&body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        return api_fail(FMX_E_UNSUPPORTED, "out of host memory");
-    } catch (const std::exception &e) {
-        return api_fail(FMX_E_UNSUPPORTED, std::string("internal error: ") + e.what());
-    }
-}
-
 int stage_code(int rc) { return rc == -5 ? FMX_E_NO_DEVICE : rc == -1 ? FMX_E_ARG : FMX_E_HIP; }
 
 size_t fence_key_bytes(int32_t n_fences, int32_t chars) { return ((size_t)n_fences * chars * 2 + 15) / 16 * 16; }
@@ -70,11 +50,11 @@ int workspace(SaIndex &s, void *stream, size_t bytes, void **out) {
     auto &slot = s.ws[stream];
     if (slot.second < bytes) {
         if (slot.first) {
-            SA_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+            FMX_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
             (void)hipFree(slot.first);
             slot = {nullptr, 0};
         }
-        SA_HIP(hipMalloc(&slot.first, bytes));
+        FMX_HIP_TRY(hipMalloc(&slot.first, bytes));
         slot.second = bytes;
     }
     *out = slot.first;
@@ -126,28 +106,28 @@ int query_host(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off
         if (pat_off[i + 1] < pat_off[i]) return api_fail(FMX_E_ARG, "pattern offsets must start at >= 0 and never decrease");
     const size_t chars = (size_t)pat_off[n];
     if (chars && !pat) return api_fail(FMX_E_ARG, "bad arguments");
-    SA_HIP(hipSetDevice(s->device));
+    FMX_HIP_TRY(hipSetDevice(s->device));
     const size_t n_locs = locate ? (size_t)n * (size_t)max_matches : 0;
     DevBuf d_pat, d_off, d_counts, d_found, d_locs, d_scratch;
-    SA_HIP(d_pat.alloc(chars * 2));
-    SA_HIP(d_off.alloc(((size_t)n + 1) * 4));
-    if (counts) SA_HIP(d_counts.alloc((size_t)n * 4));
+    FMX_HIP_TRY(d_pat.alloc(chars * 2));
+    FMX_HIP_TRY(d_off.alloc(((size_t)n + 1) * 4));
+    if (counts) FMX_HIP_TRY(d_counts.alloc((size_t)n * 4));
     if (locate) {
-        SA_HIP(d_found.alloc((size_t)n * 4));
-        SA_HIP(d_locs.alloc(n_locs * 4));
-        SA_HIP(d_scratch.alloc(query_scratch_bytes(n, max_matches)));
-        if (n_locs) SA_HIP(hipMemcpy(d_locs.p, locs, n_locs * 4, hipMemcpyHostToDevice));  // slots past `found` keep their values
+        FMX_HIP_TRY(d_found.alloc((size_t)n * 4));
+        FMX_HIP_TRY(d_locs.alloc(n_locs * 4));
+        FMX_HIP_TRY(d_scratch.alloc(query_scratch_bytes(n, max_matches)));
+        if (n_locs) FMX_HIP_TRY(hipMemcpy(d_locs.p, locs, n_locs * 4, hipMemcpyHostToDevice));  // slots past `found` keep their values
     }
-    if (chars) SA_HIP(hipMemcpy(d_pat.p, pat, chars * 2, hipMemcpyHostToDevice));
-    SA_HIP(hipMemcpy(d_off.p, pat_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
+    if (chars) FMX_HIP_TRY(hipMemcpy(d_pat.p, pat, chars * 2, hipMemcpyHostToDevice));
+    FMX_HIP_TRY(hipMemcpy(d_off.p, pat_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
     rc = query_dev(*s, d_pat.as<uint16_t>(), d_off.as<int32_t>(), n, max_matches, d_locs.as<int32_t>(), d_found.as<int32_t>(),
                    d_counts.as<int32_t>(), d_scratch.p, query_scratch_bytes(n, max_matches), nullptr);
     if (rc) return rc;
-    SA_HIP(hipDeviceSynchronize());
-    if (counts) SA_HIP(hipMemcpy(counts, d_counts.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    FMX_HIP_TRY(hipDeviceSynchronize());
+    if (counts) FMX_HIP_TRY(hipMemcpy(counts, d_counts.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (locate) {
-        SA_HIP(hipMemcpy(found, d_found.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (n_locs) SA_HIP(hipMemcpy(locs, d_locs.p, n_locs * 4, hipMemcpyDeviceToHost));
+        FMX_HIP_TRY(hipMemcpy(found, d_found.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (n_locs) FMX_HIP_TRY(hipMemcpy(locs, d_locs.p, n_locs * 4, hipMemcpyDeviceToHost));
     }
     return FMX_OK;
 }
@@ -391,7 +371,7 @@ int fmx_sa_count_batch_dev(const fmx_index *idx, const uint16_t *d_pat, const in
         if (rc) return rc;
         rc = fmx::check_batch(n, -1, n == 0 || (d_pat_off && d_counts));
         if (rc || n == 0) return rc;
-        SA_HIP(hipSetDevice(s->device));
+        FMX_HIP_TRY(hipSetDevice(s->device));
         return fmx::query_dev(*s, d_pat, d_pat_off, n, -1, nullptr, nullptr, d_counts, nullptr, 0, stream);
     });
 }
@@ -405,7 +385,7 @@ int fmx_sa_locate_batch_dev(const fmx_index *idx, const uint16_t *d_pat, const i
         if (max_matches < 0) return api_fail(FMX_E_ARG, "max_matches < 0");
         rc = fmx::check_batch(n, max_matches, n == 0 || (d_pat_off && d_found && (d_locs || max_matches == 0)));
         if (rc || n == 0) return rc;
-        SA_HIP(hipSetDevice(s->device));
+        FMX_HIP_TRY(hipSetDevice(s->device));
         const size_t bytes = fmx::query_scratch_bytes(n, max_matches);
         void *scratch = nullptr;
         rc = fmx::workspace(*s, stream, bytes, &scratch);
@@ -431,12 +411,12 @@ int fmx_bwt(const uint16_t *text, int32_t n, int build_device, uint16_t *bwt) {
             if (rc) return api_fail(rc, err);
             fmx::DevBuf owner, d_text1, d_out;
             owner.p = d_sa;
-            SA_HIP(d_text1.alloc((size_t)n1 * 2));
-            SA_HIP(d_out.alloc((size_t)n1 * 2));
-            SA_HIP(hipMemcpy(d_text1.p, text1.data(), (size_t)n1 * 2, hipMemcpyHostToDevice));
+            FMX_HIP_TRY(d_text1.alloc((size_t)n1 * 2));
+            FMX_HIP_TRY(d_out.alloc((size_t)n1 * 2));
+            FMX_HIP_TRY(hipMemcpy(d_text1.p, text1.data(), (size_t)n1 * 2, hipMemcpyHostToDevice));
             const int e = fmx::launch_bwt_gather(d_sa, d_text1.as<uint16_t>(), n1, d_out.as<uint16_t>(), nullptr);
             if (e) return api_fail(FMX_E_HIP, std::string("k_bwt_gather launch: ") + hipGetErrorString((hipError_t)e));
-            SA_HIP(hipMemcpy(bwt, d_out.p, (size_t)n1 * 2, hipMemcpyDeviceToHost));
+            FMX_HIP_TRY(hipMemcpy(bwt, d_out.p, (size_t)n1 * 2, hipMemcpyDeviceToHost));
             return FMX_OK;
         }
         std::vector<int32_t> sa((size_t)n1 + 1);

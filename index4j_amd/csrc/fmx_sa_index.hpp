@@ -66,7 +66,6 @@ int sa_to_device(SaIndex &s, int device, std::string &err);
 // fmx_api.cpp: the handle of a SuffixArray, and the SuffixArray of a handle (nullptr: another kind of handle)
 fmx_index *sa_handle(std::unique_ptr<SaIndex> sa);
 SaIndex *sa_of(const fmx_index *idx);
-int api_fail(int code, const std::string &msg);
 
 // fmx_sa_query.hip
 int sa_fence_settings(int32_t n, int32_t *n_fences, int32_t *shift, int32_t *chars);  // from the options; -1: too big for LDS

@@ -3,49 +3,20 @@
 // forms fmx_number_stats_where_batch / fmx_number_stats_where_class_batch.  Of a handle this file sees what fmx::line_view and
 // fmx::text_view hand out; the host forms run the packed sequence of fmx_api.cpp up to the stage of this file
 // (fmx::hits_stage_call), as fmx_hit_histogram_where_batch does: the lines of the queries and the filter over the value patterns'
-// hits (fmx::kept_hits_stage, skipped when no pattern asks for a query), then the numbers stage over what is kept.  Only the rows
-// and the small per-pattern and per-term arrays come down.
-#include "../../include/fmx.h"
+// hits (fmx::kept_hits_stage, skipped when no pattern asks for a query), then the numbers stage over what is kept.  The checks of
+// the batches, their merge and that stage are the host-stage layer's (fmx_host_stage.hpp).  Only the rows and the small per-pattern
+// and per-term arrays come down.
 #include "fmx_hit_numbers.hpp"
-#include "fmx_plan.hpp"
+#include "fmx_host_stage.hpp"
 
 #include <hip/hip_runtime.h>
-
-#include <climits>
-#include <exception>
-#include <new>
-#include <string>
-#include <vector>
-
-namespace fmx {
-int api_fail(int code, const std::string &msg);  // fmx_api.cpp: the calling thread's fmx_last_error
-}  // namespace fmx
 
 namespace {
 
 using fmx::api_fail;
-
-template <class F>
-int guarded(F &&body) {  // (the ABI never throws)
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        return api_fail(FMX_E_UNSUPPORTED, "out of host memory");
-    } catch (const std::exception &e) {
-        return api_fail(FMX_E_UNSUPPORTED, std::string("internal error: ") + e.what());
-    }
-}
-
-#define STATS_HIP_TRY(expr)                                                                  \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess) {                                                             \
-            (void)hipGetLastError();                                                         \
-            return api_fail(FMX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-        }                                                                                    \
-    } while (0)
-
-int no_line_table() { return api_fail(FMX_E_ARG, "the index has no line table (call fmx_line_table_build)"); }
+using fmx::guarded;
+using fmx::no_line_table;
+using fmx::zero;
 
 // the shape of the answer and the HOST arrays that cut it: the edges (none at all: one bucket, every line), the permilles
 struct Shape {
@@ -62,14 +33,8 @@ int check_shape(int32_t n, const int32_t *edges, int32_t n_edges, int32_t frac_d
         case 1: return api_fail(FMX_E_ARG, "n_permille is outside [0, 16]");
         default: return api_fail(FMX_E_ARG, "a permille is outside [0, 1000]");
     }
-    if (edges || n_edges != 0) {
-        switch (fmx::fm_hist_edges_bad(edges, n_edges)) {
-            case 0: break;
-            case 1: return api_fail(FMX_E_ARG, "fewer than 2 edges");
-            case 2: return api_fail(FMX_E_ARG, "the first edge is negative");
-            default: return api_fail(FMX_E_ARG, "the edges decrease");
-        }
-    }
+    if (edges || n_edges != 0)
+        if (const int rc = fmx::check_edges_array(edges, n_edges)) return rc;
     *s = Shape{edges, n_edges, edges ? n_edges - 1 : 1, frac_digits, permille, n_permille};
     const int64_t cells = (int64_t)n * s->B;
     if (cells > fmx::kHistCellsMax) return api_fail(FMX_E_ARG, "more than 2^27 rows in one call (patterns * buckets)");
@@ -89,12 +54,12 @@ struct Rows {
 // rows and per-pattern counters of the device, all zero
 int zero_rows(const Rows &r, int32_t n, const Shape &s, hipStream_t st) {
     const size_t cells = s.cells(n);
-    if (cells > 0) STATS_HIP_TRY(hipMemsetAsync(r.count, 0, cells * 4, st));
+    if (cells > 0) FMX_HIP_TRY(hipMemsetAsync(r.count, 0, cells * 4, st));
     for (void *p : {(void *)r.sum_lo, (void *)r.sum_hi, (void *)r.min, (void *)r.max})
-        if (p && cells > 0) STATS_HIP_TRY(hipMemsetAsync(p, 0, cells * 8, st));
-    if (r.pct && cells * (size_t)s.P > 0) STATS_HIP_TRY(hipMemsetAsync(r.pct, 0, cells * (size_t)s.P * 8, st));
+        if (p && cells > 0) FMX_HIP_TRY(hipMemsetAsync(p, 0, cells * 8, st));
+    if (r.pct && cells * (size_t)s.P > 0) FMX_HIP_TRY(hipMemsetAsync(r.pct, 0, cells * (size_t)s.P * 8, st));
     for (int32_t *p : {r.not_number, r.overflow})
-        if (p && n > 0) STATS_HIP_TRY(hipMemsetAsync(p, 0, (size_t)n * 4, st));
+        if (p && n > 0) FMX_HIP_TRY(hipMemsetAsync(p, 0, (size_t)n * 4, st));
     return FMX_OK;
 }
 
@@ -138,10 +103,6 @@ struct StatsArgs {
     std::vector<int64_t> kept_off;  // n + 1, filled when the call has synchronised
 };
 
-template <class T>
-void zero(T *a, size_t count) {
-    for (size_t i = 0; i < count && a; ++i) a[i] = 0;
-}
 void zero_host_rows(const Rows &r, int32_t n, const Shape &s) {
     const size_t cells = s.cells(n);
     zero(r.count, cells);
@@ -187,18 +148,18 @@ int stats_stage(const fmx::HitsBetween &h, void *arg) {
     void *ws = nullptr;
     if (ws_bytes > 0 && (rc = h.block(h.call, ws_bytes, &ws))) return rc;
     if ((rc = numbers_impl(h.idx, *h.view, a.text, h.n, a.term_len.data(), d_off, d_locs, n_hits, s, d, h.status, ws, ws_bytes, st))) return rc;
-    STATS_HIP_TRY(hipMemcpyAsync(a.kept_off.data(), d_off, ((size_t)h.n + 1) * 8, hipMemcpyDeviceToHost, st));
+    FMX_HIP_TRY(hipMemcpyAsync(a.kept_off.data(), d_off, ((size_t)h.n + 1) * 8, hipMemcpyDeviceToHost, st));
     auto down = [&](void *host, const void *dev, size_t bytes) -> hipError_t {
         return host && bytes > 0 ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
     };
-    STATS_HIP_TRY(down(a.host.count, d.count, cells * 4));
-    STATS_HIP_TRY(down(a.host.sum_lo, d.sum_lo, cells * 8));
-    STATS_HIP_TRY(down(a.host.sum_hi, d.sum_hi, cells * 8));
-    STATS_HIP_TRY(down(a.host.min, d.min, cells * 8));
-    STATS_HIP_TRY(down(a.host.max, d.max, cells * 8));
-    STATS_HIP_TRY(down(a.host.pct, d.pct, pcts * 8));
-    STATS_HIP_TRY(down(a.host.not_number, d.not_number, (size_t)h.n * 4));
-    STATS_HIP_TRY(down(a.host.overflow, d.overflow, (size_t)h.n * 4));
+    FMX_HIP_TRY(down(a.host.count, d.count, cells * 4));
+    FMX_HIP_TRY(down(a.host.sum_lo, d.sum_lo, cells * 8));
+    FMX_HIP_TRY(down(a.host.sum_hi, d.sum_hi, cells * 8));
+    FMX_HIP_TRY(down(a.host.min, d.min, cells * 8));
+    FMX_HIP_TRY(down(a.host.max, d.max, cells * 8));
+    FMX_HIP_TRY(down(a.host.pct, d.pct, pcts * 8));
+    FMX_HIP_TRY(down(a.host.not_number, d.not_number, (size_t)h.n * 4));
+    FMX_HIP_TRY(down(a.host.overflow, d.overflow, (size_t)h.n * 4));
     return FMX_OK;
 }
 
@@ -208,21 +169,17 @@ int stats_call_args(const fmx_index *idx, int32_t n, int32_t n_terms, const int3
                     int32_t n_permille, const Rows &host, int32_t *term_status, StatsArgs *args, bool *done) {
     fmx::LineView view;
     int rc;
-    if ((rc = fmx::check_hits_filter(n, n_terms, query_off, term_kind, q, where_of)) ||
+    if ((rc = fmx::check_query_arrays(n_terms, q, query_off, term_kind)) || (rc = fmx::check_where_of(n, where_of, q)) ||
         (rc = check_shape(n, edges, n_edges, frac_digits, permille, n_permille, &args->shape)) || (rc = fmx::line_view(idx, &view)) ||
         (rc = fmx::text_view(idx, &args->text)))
         return rc;
-    args->filter = fmx::HitsFilter{query_off, term_kind, q, where_of, fmx::hits_filter_asked(n, where_of)};
+    args->filter = fmx::HitsFilter{query_off, term_kind, q, where_of, 0, INT32_MAX, fmx::hits_filter_asked(n, where_of)};
     if ((edges || args->filter.filters) && !view.table) return no_line_table();  // (the buckets and the filter are lines)
     args->host = host;
     args->kept_off.assign((size_t)n + 1, 0);
     *done = n == 0;
     if (n == 0) zero(term_status, (size_t)n_terms);  // (nothing is searched: the terms are not judged)
     return FMX_OK;
-}
-
-void kept_of(const StatsArgs &args, int32_t n, int32_t *kept) {
-    for (int32_t i = 0; i < n && kept; ++i) kept[i] = (int32_t)(args.kept_off[(size_t)i + 1] - args.kept_off[(size_t)i]);
 }
 
 }  // namespace
@@ -282,7 +239,7 @@ int fmx_number_stats_where_batch(const fmx_index *idx, const uint16_t *pat, cons
     if ((rc = fmx::merge_literal_batch(pat, pat_off, n, term_pat, term_off, n_terms, &merged, &batch))) return rc;
     for (int32_t i = 0; i < n; ++i) args.term_len.push_back(pat_off[i + 1] - pat_off[i]);
     if ((rc = fmx::hits_stage_call(idx, batch, stats_stage, &args, occurrences, status, nullptr, term_status))) return rc;
-    kept_of(args, n, kept);
+    fmx::kept_of(args.kept_off.data(), n, kept);
     return FMX_OK;
     });
 }
@@ -313,7 +270,7 @@ int fmx_number_stats_where_class_batch(const fmx_index *idx, const uint16_t *alt
         return rc;
     for (int32_t i = 0; i < n; ++i) args.term_len.push_back(pat_off[i + 1] - pat_off[i]);  // (a position is a character)
     if ((rc = fmx::hits_stage_call(idx, batch, stats_stage, &args, occurrences, status, nullptr, term_status))) return rc;
-    kept_of(args, n, kept);
+    fmx::kept_of(args.kept_off.data(), n, kept);
     return FMX_OK;
     });
 }

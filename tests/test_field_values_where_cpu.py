@@ -294,6 +294,22 @@ def test_sanitized_build(simdir, hd, synth):
     sim_case(simdir, "synth", os_, Ts, ["k=", "\nk="], [dict(all=["keep"])], [0, 0], (0, 41), extra_hits=2, max_fences=0, sanitize=True)
 
 
+def test_merged_batch_is_sanitizer_clean(tmp_path):
+    """tests/cpp/san_merged_batch.cpp: the checks and the merge of terms and value patterns into ONE batch
+    (index4j_amd/csrc/fmx_host_batch.cpp, the file the library is linked from) as a stand-alone program under AddressSanitizer and
+    UndefinedBehaviorSanitizer, against a merge written out naively, every array exactly as large as the contract makes it"""
+    root = os.path.dirname(HERE)
+    csrc = os.path.join(root, "index4j_amd", "csrc")
+    exe = str(tmp_path / "san_merged_batch")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+           "-Wall", "-Wextra", "-Wno-unused-parameter", "-I" + csrc, os.path.join(root, "tests", "cpp", "san_merged_batch.cpp"),
+           os.path.join(csrc, "fmx_host_batch.cpp"), "-o", exe]
+    subprocess.check_call(cmd)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stdout[-3000:] + r.stderr[-6000:]
+    assert r.stdout.count(" ok: ") == 38 and "merged batch: 38 cases ok" in r.stdout, r.stdout[-3000:]
+
+
 def test_error_returns_without_a_device():
     """fails on a library without the feature (missing symbols)"""
     E_ARG, E_NO_DEVICE = ia._lib.E_ARG, ia._lib.E_NO_DEVICE

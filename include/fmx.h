@@ -465,6 +465,41 @@ int fmx_number_stats_where_class_batch(const fmx_index *idx, const uint16_t *alt
                                        uint64_t *sum_hi, int64_t *min, int64_t *max, int64_t *pct, int32_t *not_number, int32_t *overflow,
                                        int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *term_status);
 
+/* THE LINES THAT MATCH A QUERY WITH TERMS ON NUMBERS (latency_ms >= 500; size in 0 .. 67108863; status in 500 .. 599) — the host
+ * forms of the two packed stages + fmx_hits_in_number_range_dev (below: the stage) + fmx_query_lines_of_hits_dev.  They are
+ * fmx_match_query_batch's calls and its definitions hold unchanged: the n TERMS, query_off, term_kind (ALL / ANY / NONE; a query of
+ * NONE terms only has no lines), q, max_lines, line_off, *lines (the ONE allocation, freed with fmx_free_buffer), line_count,
+ * occurrences and status.  The one addition: num_lo and num_hi (n int64 each, host) and ONE frac_digits F in [0, 9].
+ * Term t is RANGED iff num_lo[t] >= 0 (a value is never negative: a negative num_lo[t] is a plain string term).  A hit of a ranged
+ * term has THE VALUE OF A HIT of fmx_number_stats_where_batch above, exactly (the window of 32 code units behind the term, F as
+ * there), and PASSES iff it parses and num_lo[t] <= value <= num_hi[t]; "not a number" and "overflow" never pass, whatever num_hi
+ * is (a run of 32 digits and a value above 2^63 - 1 included).  num_hi[t] = INT64_MAX is "no upper bound"; num_lo[t] > num_hi[t]
+ * is legal and keeps nothing.  The filter runs over the located hits between the fill and the line stage: a ranged term HOLDS on a
+ * line iff one of its PASSING hits lies there.  So the NONE term ("size ", 67108864, INT64_MAX) removes the lines whose size is at
+ * least 64 MiB, and lines whose "size " is not a number stay.
+ * occurrences[t] stays count() in the whole text.  kept[t], not_number[t], overflow[t] (each nullable, n ints): the hits of term t
+ * that pass, and those that did not parse, by reason — an unranged term: every hit, 0, 0 —, so
+ *     kept[t] + not_number[t] + overflow[t] <= occurrences[t],   the rest are numbers outside the range;
+ * with num_lo[t] = 0 and num_hi[t] = INT64_MAX the three are count, not_number and overflow of fmx_number_stats_where_batch for
+ * that pattern without edges and without a filter.  A window the packed extract ran literally hands its status to its term.  On
+ * an index built without extraction every ranged term gets FMX_ST_NOT_ENABLED and keeps no hit; unranged terms are unaffected.
+ * num_lo == NULL && num_hi == NULL: the answer is, array for array, fmx_match_query_batch's (kept = the occurrences), and an index
+ * without extraction still answers; one of them NULL alone is FMX_E_ARG.
+ * Device scratch: fmx_match_query_batch's, with fmx_hits_in_number_range_scratch_bytes (about 130 bytes per hit of the batch) in
+ * front and the line stage's 40 bytes per KEPT hit: ONE 8-byte read and wait brings the kept total down and sizes the line stage,
+ * one more the number of lines.  What comes down is the lines and the small per-term arrays — the hits and their text do not.
+ * Errors as fmx_match_query_batch, and FMX_E_ARG for frac_digits outside [0, 9]. */
+int fmx_match_query_number_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const int64_t *num_lo,
+                                 const int64_t *num_hi, int32_t frac_digits, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                 int32_t max_lines, int64_t *line_off, int32_t **lines, int32_t *line_count, int32_t *occurrences, int32_t *kept,
+                                 int32_t *not_number, int32_t *overflow, int32_t *status);
+/* ... with class patterns as terms, as fmx_match_query_class_batch; a position is one character of the pattern's length */
+int fmx_match_query_number_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                       int32_t n, int32_t max_ranges, const int64_t *num_lo, const int64_t *num_hi, int32_t frac_digits,
+                                       const int32_t *query_off, const uint8_t *term_kind, int32_t q, int32_t max_lines, int64_t *line_off,
+                                       int32_t **lines, int32_t *line_count, int32_t *occurrences, int32_t *kept, int32_t *not_number,
+                                       int32_t *overflow, int32_t *status);
+
 /* THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY (extract, FM:564-608, batched) — the host form of
  * fmx_extract_packed_offsets_dev + fmx_extract_packed_fill_dev (below: the layout, the statuses, how the work is cut).
  * host buffers, synchronous: text_off = n + 1 int64 (out), text_off[0] = 0; *chars = text_off[n] UTF-16 code units owned by the
@@ -817,6 +852,35 @@ int fmx_numbers_of_hits_dev(const fmx_index *idx, int32_t n, const int32_t *term
                             int32_t n_permille, int32_t *d_count, uint64_t *d_sum_lo, uint64_t *d_sum_hi, int64_t *d_min, int64_t *d_max,
                             int64_t *d_pct, int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status, void *d_ws, size_t ws_bytes,
                             void *stream);
+/* THE HITS WHOSE NUMBER LIES IN A RANGE over device pointers (ranged patterns, the value of a hit and when it passes:
+ * fmx_match_query_number_batch above).  Packed hits (d_hit_off, d_locs, n_hits) of n patterns exactly as fmx_hits_in_lines_dev takes
+ * them — d_hit_off[0] may be non-zero, slots behind d_hit_off[n] and beyond n_hits are no hits, the order is SA-row order — and the
+ * output is the packed format of the input, as fmx_hits_in_lines_dev leaves it: d_kept_off (n + 1 int64, d_kept_off[0] = 0),
+ * d_kept_locs (room for n_hits ints, not overlapping d_locs): the passing hits IN THE ORDER THEY HAD, every hit of an unranged
+ * pattern among them; entries from d_kept_off[n] on keep the caller's values.  term_len (n, the patterns' lengths), num_lo and
+ * num_hi (n int64 each) are HOST arrays: validated, and copied into d_ws before the call returns.  d_kept, d_not_number, d_overflow
+ * (each nullable, n ints): per pattern the hits that pass and those that did not parse, by reason (unranged: every hit, 0, 0).
+ * d_status (nullable, n ints the caller has initialised): a window the packed extract ran literally hands its status to its
+ * pattern.  On an index built without extraction nothing is launched over the image: every ranged pattern gets
+ * FMX_ST_NOT_ENABLED and keeps no hit, unranged patterns are copied through.  No line table is needed.
+ * A lane per slot stores the slot's pattern and its window (the hit tiles' loop, 16 KiB of LDS) — an EMPTY window for a slot of an
+ * unranged pattern and for a slot that is no hit, so the packed extract walks nothing for them and a call whose ranged terms are
+ * rare pays for those hits only; the packed extract fills the windows (redo launch included); a lane per slot parses its window,
+ * compares, and stores the flag and the word of the two reasons; two rocPRIM exclusive scans; fmx_hits_in_lines_dev's stable store;
+ * a lane per pattern reads the three counters off the scans.  Integers only, no atomics — the result does not depend on
+ * scheduling; lanes go to slots, never to patterns; the grids are fmx_hit_lines_geometry's and the extract honours `block` and
+ * `groups_per_cu`; asynchronous on `stream`, nothing is allocated, nothing is synchronised beyond the staged host copy of the small
+ * arrays.  d_ws: at least fmx_hits_in_number_range_scratch_bytes(n, n_hits) bytes (about 130 per slot: the window's 64, the ranges
+ * and offsets, flags and scans, the extract's scratch, rocPRIM's temporary storage; 0 for an empty call or n_hits beyond
+ * 2^31 - 1).  n == 0 or n_hits == 0: the n + 1 offsets and the counters are zeroed and nothing else is written.
+ * FMX_E_ARG for null or negative arguments, a negative term_len, frac_digits outside [0, 9], n_hits > 2^31 - 1, a workspace that is
+ * too small (the error names fmx_hits_in_number_range_scratch_bytes; nothing is launched, nothing is written), a SuffixArray /
+ * RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident. */
+size_t fmx_hits_in_number_range_scratch_bytes(int32_t n, int64_t n_hits);
+int fmx_hits_in_number_range_dev(const fmx_index *idx, int32_t n, const int32_t *term_len, const int64_t *num_lo, const int64_t *num_hi,
+                                 int32_t frac_digits, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int64_t *d_kept_off,
+                                 int32_t *d_kept_locs, int32_t *d_kept, int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status, void *d_ws,
+                                 size_t ws_bytes, void *stream);
 /* CLASS PATTERNS over device pointers (d_alt, d_pos_off, d_pat_off: the three packed arrays of fmx_count_class_batch, in device
  * memory and trusted as the literal device forms trust theirs); asynchronous on `stream`, nothing is allocated or synchronised.
  * THE SEARCH keeps, per pattern, a frontier of SA ranges: the last position gives {C[c], C[c + 1]} of each of its codes, every

@@ -261,6 +261,70 @@ public:
                 if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
         return matchQueryBatch({query}, maxLines).lines;
     }
+    // ... with terms on the NUMBER behind a pattern (fmx.h "THE LINES THAT MATCH A QUERY WITH TERMS ON NUMBERS": latency_ms >= 500).
+    // A NumberTerm with lo >= 0 is ranged: it holds on a line iff one of its hits there is followed by a number (numberStatsWhere's
+    // value, fracDigits as there) with lo <= value <= hi; kNumberMax is "no upper bound"; the default (lo = -1) is a plain string
+    // term.  matchQueryNumberBatch: Lines as matchQueryBatch, and per term kept (the hits that pass), notNumber and overflow (the
+    // hits that did not parse, by reason), in the order all, any, none of query 0, then query 1 ...
+    static constexpr int64_t kNumberMax = INT64_MAX;
+    struct NumberTerm {
+        std::u16string pattern;
+        int64_t lo = -1, hi = -1;
+    };
+    struct NumberQuery {
+        std::vector<NumberTerm> all, any, none;
+    };
+    struct NumberLines : Lines {
+        std::vector<int32_t> kept, notNumber, overflow;
+    };
+    NumberLines matchQueryNumberBatch(const std::vector<NumberQuery> &queries, int fracDigits = 0, int maxLines = 0) const {
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int64_t> lo, hi;
+        std::vector<int32_t> queryOff{0};
+        for (const NumberQuery &qu : queries) {
+            const std::vector<NumberTerm> *groups[3] = {&qu.all, &qu.any, &qu.none};
+            for (int k = 0; k < 3; ++k)
+                for (const NumberTerm &t : *groups[k]) {
+                    terms.push_back(t.pattern);
+                    kind.push_back((uint8_t)k);
+                    lo.push_back(t.lo);
+                    hi.push_back(t.hi);
+                }
+            queryOff.push_back((int32_t)terms.size());
+        }
+        std::vector<uint16_t> chars;
+        std::vector<int32_t> off;
+        pack(terms, chars, off);
+        const int32_t n = (int32_t)terms.size(), q = (int32_t)queries.size();
+        lo.push_back(0);  // (never an empty array)
+        hi.push_back(0);
+        NumberLines out;
+        out.offsets.assign((size_t)q + 1, 0);
+        out.lineCount.assign(queries.size(), 0);
+        for (std::vector<int32_t> *a : {&out.occurrences, &out.kept, &out.notNumber, &out.overflow}) a->assign(terms.size(), 0);
+        std::vector<int32_t> status(terms.size());
+        int32_t *buf = nullptr;
+        detail::check(fmx_match_query_number_batch(h_, chars.data(), off.data(), n, lo.data(), hi.data(), fracDigits, queryOff.data(), kind.data(), q,
+                                                   maxLines, out.offsets.data(), &buf, out.lineCount.data(), out.occurrences.data(),
+                                                   out.kept.data(), out.notNumber.data(), out.overflow.data(), status.data()),
+                      "fmx_match_query_number_batch");
+        try {
+            if (buf) out.lines.assign(buf, buf + out.offsets[(size_t)q]);
+        } catch (...) {
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+            throw;
+        }
+        fmx_free_buffer(reinterpret_cast<uint8_t *>(buf));
+        for (int s : status) detail::raise_for_status(s);
+        return out;
+    }
+    std::vector<int32_t> matchQueryNumber(const NumberQuery &query, int fracDigits = 0, int maxLines = 0) const {
+        for (const std::vector<NumberTerm> *g : {&query.all, &query.any, &query.none})
+            for (const NumberTerm &t : *g)
+                if (t.pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        return matchQueryNumberBatch({query}, fracDigits, maxLines).lines;
+    }
 
     // the lines that hold a SEQUENCE of terms in order, without overlap (fmx.h "THE LINES THAT HOLD A SEQUENCE OF TERMS IN ORDER":
     // grep 'A.*B').  matchSequenceBatch: lines[offsets[Q] .. offsets[Q + 1]) are those of sequence Q, ascending; lineCount per

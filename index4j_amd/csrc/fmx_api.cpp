@@ -4024,7 +4024,7 @@ int values_between_call(const fmx_index *idx, const ValuesBatch &batch, const ui
         return rc;
     const hipStream_t st = call.stream.s;
     const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, d_koff, d_kept, &call, between_block, idx,
-                           r.status ? r.status + n_terms : nullptr};
+                           r.status ? r.status + n_terms : nullptr, r.status};
     if ((rc = between(hits, arg))) return rc;
     std::vector<int64_t> kept_off((size_t)n + 1);
     HIP_TRY(hipMemcpyAsync(kept_off.data(), d_koff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -4052,7 +4052,7 @@ int hits_stage_call(const fmx_index *idx, const ValuesBatch &batch, ValuesBetwee
     if ((rc = merged_hits(call, batch, status || term_status, view, r, &d_locs))) return rc;
     const hipStream_t st = call.stream.s;
     const HitsBetween hits{&view, st, n_terms, n, r.hit_off, d_locs, r.mark_total, r.total, nullptr, nullptr, &call, between_block, idx,
-                           r.status ? r.status + n_terms : nullptr};
+                           r.status ? r.status + n_terms : nullptr, r.status};
     if ((rc = stage(hits, arg))) return rc;
     if (occurrences && n > 0) HIP_TRY(hipMemcpyAsync(occurrences, r.counts + n_terms, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     if (status && n > 0) HIP_TRY(hipMemcpyAsync(status, r.status + n_terms, (size_t)n * 4, hipMemcpyDeviceToHost, st));

@@ -8,7 +8,8 @@
 //                     the window, ONE lower bound in the line list of the pattern's query; flag 1 = kept.  Slots in front of
 //                     hit_off[0] and behind hit_off[n] get 0.
 //   rocPRIM           the exclusive scan of the flags: where each kept hit goes — the order they had
-//   k_hit_keep_store  a lane per slot stores a kept hit; a lane per pattern reads kept_off off the scan
+//   k_hit_keep_store  a lane per slot stores a kept hit; a lane per pattern reads kept_off off the scan (launch_hit_keep_store: also
+//                     the store of fmx_hit_range.hip, which makes its flags from the number behind a hit)
 // Integers only, no atomics: the result does not depend on the order the lanes run in.  Nothing here looks at the image, so this
 // file is compiled once.
 #include <hip/hip_runtime.h>
@@ -130,7 +131,13 @@ int launch_hits_in_lines(const int32_t *T, int32_t count, int n_cu, int32_t n, c
     if (hipError_t e = rocprim::exclusive_scan(tmp, tmp_bytes, flag, pos, (int32_t)0, (size_t)n_hits + 1, rocprim::plus<int32_t>(), st);
         e != hipSuccess)
         return (int)e;
-    hipLaunchKernelGGL(k_hit_keep_store, dim3((unsigned)flat), dim3(kFlatBlock), 0, st, flag, pos, hit_off, n, locs, n_hits, kept_off, kept_locs);
+    return launch_hit_keep_store(flat, flag, pos, hit_off, n, locs, n_hits, kept_off, kept_locs, stream);
+}
+
+int launch_hit_keep_store(int32_t flat_grid, const int32_t *flag, const int32_t *pos, const int64_t *hit_off, int32_t n, const int32_t *locs,
+                          int64_t n_hits, int64_t *kept_off, int32_t *kept_locs, void *stream) {
+    hipLaunchKernelGGL(k_hit_keep_store, dim3((unsigned)flat_grid), dim3(kFlatBlock), 0, static_cast<hipStream_t>(stream), flag, pos, hit_off, n,
+                       locs, n_hits, kept_off, kept_locs);
     return (int)hipGetLastError();
 }
 

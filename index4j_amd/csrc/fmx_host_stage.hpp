@@ -1,10 +1,11 @@
 // fmx_host_stage.hpp — the host-stage layer of the C ABI: what the feature files (fmx_class_api.cpp, fmx_where_api.cpp,
-// fmx_hist_api.cpp, fmx_stats_api.cpp) see of a handle and of the packed host sequence of fmx_api.cpp, and what they share among
+// fmx_hist_api.cpp, fmx_stats_api.cpp, fmx_range_api.cpp) see of a handle and of the packed host sequence of fmx_api.cpp, and what they share among
 // themselves.  Host code only: no .hip file includes it.
 //   fmx_api.cpp          the views of a handle, extract_windows, check_query_arrays, values_between_call, hits_stage_call
 //   fmx_host_batch.cpp   the checks of a call's HOST arrays and the merge of terms and value patterns into ONE batch: no HIP
 //                        runtime call, so that the CPU suite links it as plain C++ (tests/cpp/san_merged_batch.cpp)
-//   fmx_host_stage.cpp   the stages on the device: the lines of the queries, the filter over the value patterns' hits
+//   fmx_host_stage.cpp   the stages on the device: the number filter over the terms' hits, the lines of the queries, the filter
+//                        over the value patterns' hits
 // Every function that returns int returns an FMX_* code (fmx::api_fail has set the message).
 #pragma once
 
@@ -62,6 +63,7 @@ struct HitsBetween {
     int (*block)(void *call, size_t bytes, void **out);
     const ::fmx_index *idx;      // the handle of the call
     int32_t *status;             // the value patterns' statuses (device, n; nullptr: the call asks for none)
+    int32_t *term_status;        // the terms' statuses (device, n_terms; nullptr likewise)
 };
 struct ValuesBatch {
     const uint16_t *chars;
@@ -99,6 +101,21 @@ int merge_literal_batch(const uint16_t *pat, const int32_t *pat_off, int32_t n, 
 int merge_class_batch(const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
                       const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges,
                       MergedBatch *m, ValuesBatch *batch);
+// the number filter over the TERMS' hits (fmx_hit_range.hpp: term t is ranged iff num_lo[t] >= 0); the default is "none"
+struct NumberTerms {
+    const int64_t *num_lo = nullptr, *num_hi = nullptr;  // n_terms each (host)
+    const int32_t *term_len = nullptr;                   // n_terms (host), none negative
+    int32_t frac_digits = 0;                             // in [0, 9]
+    bool ranged = false;                                 // number_terms_ranged
+    // n_terms each (host, out, nullable): what the stage stores has arrived when the call has synchronised; a call whose terms have
+    // no hit stores nothing
+    int32_t *kept = nullptr, *not_number = nullptr, *overflow = nullptr;
+};
+inline bool number_terms_ranged(int32_t n_terms, const int64_t *num_lo) {
+    for (int32_t t = 0; t < n_terms && num_lo; ++t)
+        if (num_lo[t] >= 0) return true;
+    return false;
+}
 // the queries, which query each value pattern asks for and the window of lines
 struct HitsFilter {
     const int32_t *query_off;
@@ -107,6 +124,7 @@ struct HitsFilter {
     const int32_t *where_of;   // n entries, each -1 .. q - 1
     int32_t line_lo, line_hi;  // the window of lines (0 .. INT32_MAX: every line)
     bool filters;              // hits_filter_asked
+    NumberTerms number{};      // query_lines_stage: a ranged term holds on a line iff one of its PASSING hits lies there
 };
 // the call filters at all: a pattern asks for a query, or the window is not 0 .. INT32_MAX
 bool hits_filter_asked(int32_t n, const int32_t *where_of, int32_t line_lo = 0, int32_t line_hi = INT32_MAX);
@@ -127,8 +145,23 @@ void zero(T *a, size_t count) {
 // the refusal of queries whose sort key query | line | term is wider than 64 bits (count: the boundaries of the line table)
 int check_query_key_width(int32_t q, int32_t count, const int32_t *query_off);
 // the lines of the f.q > 0 queries from the terms' hits, no limit: *d_line_off (q + 1) and *d_lines on the device, from block();
-// d_line_count (device, q entries; nullable)
-int query_lines_stage(const HitsBetween &h, const HitsFilter &f, int64_t **d_line_off, int32_t **d_lines, int32_t *d_line_count);
+// d_line_count (device, q entries; nullable).  With f.number.ranged the terms' hits first go through number_range_run — the ONE
+// launcher of that filter — and ONE 8-byte read and wait brings the kept total down, which sizes the line stage.  max_lines: the
+// line stages' limit per query (0: none).
+int query_lines_stage(const HitsBetween &h, const HitsFilter &f, int64_t **d_line_off, int32_t **d_lines, int32_t *d_line_count,
+                      int32_t max_lines = 0);
+// packed hits -> the packed hits whose number lies in a range (fmx_hit_range.hip's launchers around the packed extract): n > 0,
+// n_hits in [1, 2^31 - 1], the host arrays judged (fm_range_args_bad).  An index built without extraction: no launch over the image,
+// every ranged pattern gets FMX_ST_NOT_ENABLED and keeps no hit, unranged patterns are copied through.  kept, not_number, overflow
+// and status are nullable device arrays of n ints.
+struct NumberRangeOut {
+    int64_t *kept_off;   // n + 1
+    int32_t *kept_locs;  // room for n_hits
+    int32_t *kept, *not_number, *overflow, *status;
+};
+int number_range_run(const ::fmx_index *idx, int n_cu, const TextView &text, int32_t n, const int32_t *term_len, const int64_t *num_lo,
+                     const int64_t *num_hi, int32_t frac_digits, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits,
+                     const NumberRangeOut &out, void *ws, size_t ws_bytes, void *stream);
 // the value patterns' hits that pass the filter, into (kept_off: n + 1, kept_locs: room for total - term_hits): the lines of the
 // queries where the call filters and has queries, then fmx_hits_in_lines_dev's launcher.  A call that does not filter runs it
 // without a line table (every hit is kept), so an index without one still answers.  h.n > 0 and a value pattern has a hit.

@@ -146,6 +146,31 @@ size_t hits_in_lines_scratch_bytes(int32_t n, int64_t n_hits);
 int launch_hits_in_lines(const int32_t *T, int32_t count, int n_cu, int32_t n, const int32_t *where_of, const int64_t *line_off,
                          const int32_t *lines, int32_t line_lo, int32_t line_hi, const int64_t *hit_off, const int32_t *locs, int64_t n_hits,
                          int64_t *kept_off, int32_t *kept_locs, void *ws, size_t ws_bytes, void *stream);
+// the stable store alone, for a stage that makes flags of its own (fmx_hit_range.hip): flag and pos = its exclusive scan, n_hits + 1
+// int32 each, the flags in front of hit_off[0] and behind hit_off[n] being 0; flat_grid: hit_lines_geometry's over n_hits
+int launch_hit_keep_store(int32_t flat_grid, const int32_t *flag, const int32_t *pos, const int64_t *hit_off, int32_t n, const int32_t *locs,
+                          int64_t n_hits, int64_t *kept_off, int32_t *kept_locs, void *stream);
+
+// fmx_hit_range.hip — packed hits -> the packed hits whose number lies in a range, in the order they had
+// (fmx_hits_in_number_range_dev; fmx_hit_range.hpp has the definition).  Compiled once.  term_len (n, none negative), num_lo and
+// num_hi (n int64 each; num_lo[i] < 0: pattern i is not ranged) are HOST arrays the caller has validated; they are copied into the
+// workspace before launch_range_windows returns.  The C-ABI layer runs three steps on one stream over one workspace, as for the
+// numbers stage:
+//   launch_range_windows   pattern and window [s, e) of every slot, into the regions range_windows names — an empty window for a
+//                          slot of an unranged pattern and for a slot that is no hit: the extract walks nothing for them;
+//   the packed extract     extract_windows (fmx_host_stage.hpp) over those n_hits ranges; skipped with extract == false;
+//   launch_range_keep      the codes (extract == false: a ranged pattern keeps nothing and gets the status not_enabled), the two
+//                          exclusive scans, launch_hit_keep_store, and a lane per pattern for kept, not_number and overflow (each
+//                          nullable); status (nullable): a window the extract ran literally hands its status to its pattern.
+// The grids are hit_lines_geometry's.  hipErrorInvalidValue before anything is launched or written: too small a workspace, n <= 0,
+// n_hits <= 0 or beyond 2^31 - 1, frac_digits outside [0, 9].
+size_t hits_in_number_range_scratch_bytes(int32_t n, int64_t n_hits);
+bool range_windows(void *ws, size_t ws_bytes, int32_t n, int64_t n_hits, ValuesWindows *out);
+int launch_range_windows(int32_t text_len, int n_cu, int32_t n, const int32_t *term_len, const int64_t *num_lo, const int64_t *num_hi,
+                         const int64_t *hit_off, const int32_t *locs, int64_t n_hits, void *ws, size_t ws_bytes, void *stream);
+int launch_range_keep(int n_cu, int32_t n, bool extract, int32_t not_enabled, int32_t frac_digits, const int64_t *hit_off, const int32_t *locs,
+                      int64_t n_hits, int64_t *kept_off, int32_t *kept_locs, int32_t *kept, int32_t *not_number, int32_t *overflow,
+                      int32_t *status, void *ws, size_t ws_bytes, void *stream);
 
 // fmx_line_hist.hip — matching lines and hits per bucket of lines (fmx_lines_histogram_dev, fmx_hits_histogram_dev;
 // fmx_line_hist.hpp has the definitions).  Compiled once.  edges (n_edges >= 2, edges[0] >= 0, never decreasing) is a HOST array; it

@@ -18,6 +18,8 @@ from . import _lib
 from ._lib import check, lib
 
 _EXC = {0: RuntimeError, 1: ValueError, 2: IndexError}
+NUMBER_MAX = 2 ** 63 - 1  # "no upper bound" of a ranged term (match_query_number_batch)
+all_of = all  # (match_query's and grep's keyword `all` shadows the builtin there)
 
 
 def as_chars(text):
@@ -487,6 +489,51 @@ class FmIndex:
             lib.fmx_free_buffer(buf)
         return (lines, line_off, status, line_count, occurrences) if want_counts else (lines, line_off, status)
 
+    # ---- query terms on the number behind a pattern (fmx.h "THE LINES THAT MATCH A QUERY WITH TERMS ON NUMBERS") ----
+    def _match_query_number_call(self, call, where, args, n, query_off, term_kind, num_lo, num_hi, frac_digits, max_lines, want_counts):
+        query_off = np.ascontiguousarray(query_off, dtype=np.int32)
+        term_kind = np.ascontiguousarray(term_kind, dtype=np.uint8)
+        q = len(query_off) - 1
+        if len(term_kind) != n:
+            raise ValueError("term_kind has %d entries for %d terms" % (len(term_kind), n))
+        lo = None if num_lo is None else np.ascontiguousarray(num_lo, dtype=np.int64)
+        hi = None if num_hi is None else np.ascontiguousarray(num_hi, dtype=np.int64)
+        for a in (lo, hi):
+            if a is not None and len(a) != n:
+                raise ValueError("num_lo / num_hi have %d entries for %d terms" % (len(a), n))
+        line_off = np.zeros(q + 1, dtype=np.int64)
+        line_count = np.zeros(q, dtype=np.int32)
+        occurrences, kept, not_number, overflow, status = (np.zeros(n, dtype=np.int32) for _ in range(5))
+        buf = C.c_void_p()
+        check(call(self._h, *args, None if lo is None else lo.ctypes.data, None if hi is None else hi.ctypes.data, int(frac_digits),
+                   query_off.ctypes.data, term_kind.ctypes.data, q, int(max_lines), line_off.ctypes.data, C.byref(buf), line_count.ctypes.data,
+                   occurrences.ctypes.data, kept.ctypes.data, not_number.ctypes.data, overflow.ctypes.data, status.ctypes.data), where)
+        total = int(line_off[q])
+        try:  # the library's buffer is copied into an array of NumPy's own and handed back
+            lines = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_int32)), shape=(total,)).copy() if total else np.zeros(0, np.int32)
+        finally:
+            lib.fmx_free_buffer(buf)
+        return (lines, line_off, status, line_count, occurrences, kept, not_number, overflow) if want_counts else (lines, line_off, status)
+
+    def match_query_number_batch(self, chars, offsets, query_off, term_kind, num_lo, num_hi, frac_digits=0, max_lines=0, want_counts=False):
+        """match_query_batch with terms on the NUMBER behind a pattern (fmx_match_query_number_batch): term t is ranged iff
+        num_lo[t] >= 0, and then holds on a line iff one of its hits there is followed by a number (number_stats' value, frac_digits
+        as there) with num_lo[t] <= value <= num_hi[t]; 2^63 - 1 is "no upper bound", a negative num_lo[t] a plain string term.
+        num_lo = num_hi = None: match_query_batch's answer.  Returns (lines, line_off, status[, line_count, occurrences, kept,
+        not_number, overflow]): per TERM the hits in the whole text, those that pass, and those that did not parse, by reason."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        return self._match_query_number_call(lib.fmx_match_query_number_batch, "fmx_match_query_number_batch", (chars.ctypes.data, offsets.ctypes.data, len(offsets) - 1),
+                                             len(offsets) - 1, query_off, term_kind, num_lo, num_hi, frac_digits, max_lines, want_counts)
+
+    def match_query_number_class_batch(self, alt, pos_off, pat_off, query_off, term_kind, num_lo, num_hi, frac_digits=0, max_lines=0,
+                                       want_counts=False, max_ranges=CLASS_RANGES_DEFAULT):
+        """match_query_number_batch with class patterns as terms (fmx_match_query_number_class_batch); same returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        return self._match_query_number_call(lib.fmx_match_query_number_class_batch, "fmx_match_query_number_class_batch",
+                                             (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, int(max_ranges)), n, query_off,
+                                             term_kind, num_lo, num_hi, frac_digits, max_lines, want_counts)
+
     # ---- the lines that hold a sequence of terms in order (fmx.h "THE LINES THAT HOLD A SEQUENCE OF TERMS IN ORDER") ----
     def _sequence_call(self, call, where, args, n, query_off, max_lines, want_counts, want_spans):
         query_off = np.ascontiguousarray(query_off, dtype=np.int32)
@@ -911,18 +958,37 @@ class FmIndex:
         raise_for_status(status[0])
         return lines
 
-    def match_query(self, all=(), any=(), none=(), max_lines=0, ignore_case=False):  # noqa: A002 (the words of the query)
+    def match_query(self, all=(), any=(), none=(), max_lines=0, ignore_case=False, frac_digits=0):  # noqa: A002 (the words of the query)
         """the ids of the lines that hold every pattern of `all`, at least one of `any` (if given) and none of `none`, each once,
         ascending; at most max_lines of them for max_lines > 0.  Without `all` and `any` there are no lines (`none` filters).
-        ignore_case: every term in any case (class patterns: match_query_class_batch)."""
-        terms, kinds = [], []
-        for kind, group in enumerate((all, any, none)):  # (a lone str is one term)
-            for p in ([group] if isinstance(group, str) else group):
-                terms.append(as_chars(p))
+        ignore_case: every term in any case (class patterns: match_query_class_batch).  A term may be a tuple (pattern, lo, hi): it
+        holds on a line iff a hit of `pattern` there is followed by a number in [lo, hi] (None: open; number_stats' value with
+        frac_digits) — match_query(all=["addStoredBlock", ("size ", None, 67108863)]); match_query_number_batch runs then."""
+        terms, kinds, lo, hi = [], [], [], []
+        for kind, group in enumerate((all, any, none)):  # (a lone str is one term, and so is a lone tuple (pattern, lo, hi))
+            lone = isinstance(group, str) or (isinstance(group, tuple) and len(group) == 3 and
+                                              all_of(b is None or isinstance(b, (int, np.integer)) for b in group[1:]))
+            for p in ([group] if lone else group):
+                ranged = isinstance(p, tuple)
+                if ranged and len(p) != 3:
+                    raise ValueError("a ranged term is (pattern, lo, hi)")
+                terms.append(as_chars(p[0] if ranged else p))
                 kinds.append(kind)
+                lo.append(-1 if not ranged else 0 if p[1] is None else int(p[1]))
+                hi.append(-1 if not ranged else NUMBER_MAX if p[2] is None else int(p[2]))
+                if ranged and not (0 <= lo[-1] <= NUMBER_MAX and 0 <= hi[-1] <= NUMBER_MAX):
+                    raise ValueError("the bounds of a ranged term lie in [0, 2^63 - 1]")
         if min((len(t) for t in terms), default=1) == 0:
             raise IndexError("ArrayIndexOutOfBoundsException")
-        if ignore_case:
+        if max(lo, default=-1) >= 0:  # (some term is ranged)
+            if ignore_case:
+                packed = pack_class_patterns([_ignore_case(t) for t in terms])
+                lines, line_off, status = self.match_query_number_class_batch(*packed, [0, len(terms)], np.array(kinds, np.uint8), lo, hi,
+                                                                              frac_digits, max_lines)
+            else:
+                lines, line_off, status = self.match_query_number_batch(*pack_patterns(terms), [0, len(terms)], np.array(kinds, np.uint8), lo, hi,
+                                                                        frac_digits, max_lines)
+        elif ignore_case:
             packed = pack_class_patterns([_ignore_case(t) for t in terms])
             lines, line_off, status = self.match_query_class_batch(*packed, [0, len(terms)], np.array(kinds, np.uint8), max_lines)
         else:
@@ -931,6 +997,22 @@ class FmIndex:
         for st in status:
             raise_for_status(st)
         return lines
+
+    def number_range_count(self, pattern, lo=None, hi=None, frac_digits=0, ignore_case=False):
+        """(kept, not_number, overflow, occurrences) of `pattern`: its hits whose number (number_stats' value with frac_digits) lies in
+        [lo, hi] (None: open), those that are followed by no number or by one above 2^63 - 1, and count()"""
+        p = as_chars(pattern)
+        if len(p) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        lo, hi = [0 if lo is None else int(lo)], [NUMBER_MAX if hi is None else int(hi)]
+        if not (0 <= lo[0] <= NUMBER_MAX and 0 <= hi[0] <= NUMBER_MAX):
+            raise ValueError("the bounds lie in [0, 2^63 - 1]")
+        if ignore_case:
+            out = self.match_query_number_class_batch(*pack_class_patterns([_ignore_case(p)]), [0, 1], [0], lo, hi, frac_digits, 1, True)
+        else:
+            out = self.match_query_number_batch(*pack_patterns([p]), [0, 1], [0], lo, hi, frac_digits, 1, True)
+        raise_for_status(out[2][0])
+        return int(out[5][0]), int(out[6][0]), int(out[7][0]), int(out[4][0])
 
     def match_sequence(self, terms, max_lines=0, ignore_case=False, want_spans=False):
         """the ids of the lines that hold the terms in this order, without overlap (grep 'A.*B.*C'), each once, ascending; at most
@@ -1083,10 +1165,11 @@ class FmIndex:
             raise_for_status(st)
         return [chars[a:b].tobytes().decode("utf-16-le", "surrogatepass") for a, b in zip(text_off[:-1], text_off[1:])]
 
-    def grep(self, pattern=None, all=(), any=(), none=(), max_lines=0, ignore_case=False, sequence=None):  # noqa: A002 (the words of the query)
+    def grep(self, pattern=None, all=(), any=(), none=(), max_lines=0, ignore_case=False, sequence=None, frac_digits=0):  # noqa: A002 (the words of the query)
         """[(line id, line)] of the lines that hold `pattern` — or, without one, that match the query of all / any / none
-        (match_query), or that hold the terms of `sequence` in order (match_sequence; not together with the others: ValueError)
-        — ascending, at most max_lines of them for max_lines > 0: match_lines / match_query / match_sequence, then line_text_batch"""
+        (match_query; a term may be (pattern, lo, hi), frac_digits as there), or that hold the terms of `sequence` in order
+        (match_sequence; not together with the others: ValueError) — ascending, at most max_lines of them for max_lines > 0:
+        match_lines / match_query / match_sequence, then line_text_batch"""
         if sequence is not None:
             if pattern is not None or all or any or none:
                 raise ValueError("a sequence, or a pattern, or a query: one of them")
@@ -1096,7 +1179,7 @@ class FmIndex:
                 raise ValueError("a pattern or a query, not both")
             ids = self.match_lines(pattern, max_lines, ignore_case=ignore_case)
         else:
-            ids = self.match_query(all, any, none, max_lines, ignore_case=ignore_case)
+            ids = self.match_query(all, any, none, max_lines, ignore_case=ignore_case, frac_digits=frac_digits)
         return list(zip(ids.tolist(), self.line_text(ids)))
 
     def extract(self, start, stop, destination, offset=0):  # FM:564-608

@@ -465,6 +465,67 @@ int fmx_number_stats_where_class_batch(const fmx_index *idx, const uint16_t *alt
                                        uint64_t *sum_hi, int64_t *min, int64_t *max, int64_t *pct, int32_t *not_number, int32_t *overflow,
                                        int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *term_status);
 
+/* STATISTICS BY KEY: THE NUMBER BEHIND A PATTERN, GROUPED BY THE VALUE OF A FIELD OF THE SAME LINE (stats count, sum(bytes=),
+ * p95(latency_ms=) by status=) — the host form of the three stages fmx_first_hits_of_lines_dev, fmx_values_of_hits_groups_dev and
+ * fmx_numbers_by_key_dev (below).  A call has m KEY PATTERNS (key_pat, key_off) and n NUMBER PATTERNS (pat, pat_off); by_of[i] in
+ * [0, m) names the key pattern number pattern i is grouped by, several may share one.  The terms, query_off, term_kind, q and the
+ * window of lines [line_lo, line_hi) (0 .. INT32_MAX: every line) are fmx_field_values_where_batch's and its keep rule holds for
+ * the key patterns' hits (key_where_of, m ints, each -1 .. q - 1) and for the number patterns' hits (where_of, n ints) alike.
+ * THE KEY OF A LINE for key pattern k: among the KEPT hits of k whose line is L (a hit belongs to the line of its first character)
+ * the one with the smallest text position; the key is fmx_field_values_batch's VALUE of that hit under stop / n_stop / max_len (its
+ * window, cut at the first code unit of the stop set; the empty string is a key; without '\n' in the stop set the window may run
+ * into the next line).  A line with no kept hit of k has no key.
+ * THE GROUPS of key pattern k are the distinct keys of its lines in fmx_field_values_batch's order, val_off[k] .. val_off[k + 1] of
+ * (*lines)[g] = the number of lines that have that key (count of "stats ... by"), (*text_off)[g] .. (*text_off)[g + 1] of *chars
+ * its code units; val_off (m + 1 int64, out), val_off[m] = G.  A group may have lines > 0 and no number hit.
+ * THE ROWS are packed: row_off (n + 1 int64, out), row_off[i + 1] - row_off[i] = the groups of key by_of[i]; row (i, g) at
+ * row_off[i] + g is over the kept hits of number pattern i whose line has key g and that parse (the value of a hit:
+ * fmx_number_stats_where_batch): (*count), (*sum_lo), (*sum_hi), (*min), (*max), (*pct)[row * P + j] as there.  Per number pattern:
+ * no_key[i] = the kept hits on a line without a key — decided before parsing, such a hit is counted here and nowhere else;
+ * not_number[i], overflow[i] = the kept hits on a line with a key that did not parse.  For every i
+ *     sum over g of count[row_off[i] + g] + no_key[i] + not_number[i] + overflow[i] = kept[i].
+ * occurrences, kept, status (n ints) are the number patterns', key_occurrences, key_kept, key_status (m ints) the key patterns',
+ * term_status the terms'; each nullable.  *lines, *text_off, *chars, *count, *sum_lo, *sum_hi, *min, *max and *pct point into ONE
+ * allocation owned by the library until fmx_free_buffer((uint8_t *)*lines); all are NULL when there is no group (and on every
+ * failure).  When the key patterns have no kept hit nothing beyond the filter runs on the device, there are no groups and no rows
+ * and no_key[i] = kept[i]; when the number patterns have none, the groups are reported with zero rows.  On an index built without
+ * extraction there are no groups, no rows, every counter is zero and every status is FMX_ST_NOT_ENABLED; occurrences and kept are
+ * still filled.  The line table is always required (keys are per line).
+ * Two waits beyond the filter's own: the kept offsets (they size the stages) and the m + 1 group offsets (they size the rows), and
+ * one for the size of the groups' text.  Scratch: about 30 bytes per kept key hit for stage a, fmx_values_of_hits_groups_scratch_bytes
+ * per first hit, fmx_numbers_by_key_scratch_bytes per kept slot.
+ * n == 0: FMX_OK, nothing is searched, val_off and row_off are zeroed, term_status is zeroed.  m == 0 with n > 0: FMX_E_ARG.
+ * FMX_E_ARG as fmx_field_values_where_batch (max_len outside [1, 64], more than 64 stop units, the query arrays, a where_of or
+ * key_where_of outside -1 .. q - 1, a window that is not 0 <= line_lo <= line_hi, kept hits * max_len above 2^35) and as
+ * fmx_number_stats_where_batch (frac_digits, n_permille, a permille), for a by_of outside [0, m), more than 2^27 rows or rows *
+ * max(P, 1) above 2^27, an index without a line table (the fmx_line_table_build message), a SuffixArray / RrrVector / stand-alone
+ * wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident; FMX_E_NOMEM leaves nothing behind. */
+int fmx_number_stats_by_batch(const fmx_index *idx, const uint16_t *key_pat, const int32_t *key_off, int32_t m, const uint16_t *pat,
+                              const int32_t *pat_off, int32_t n, const int32_t *by_of, const uint16_t *term_pat, const int32_t *term_off,
+                              int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q, const int32_t *key_where_of,
+                              const int32_t *where_of, int32_t line_lo, int32_t line_hi, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                              int32_t frac_digits, const int32_t *permille, int32_t n_permille, int64_t *val_off, int32_t **lines,
+                              int64_t **text_off, uint16_t **chars, int64_t *row_off, int32_t **count, uint64_t **sum_lo, uint64_t **sum_hi,
+                              int64_t **min, int64_t **max, int64_t **pct, int32_t *no_key, int32_t *not_number, int32_t *overflow,
+                              int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *key_occurrences, int32_t *key_kept,
+                              int32_t *key_status, int32_t *term_status);
+/* ... with class patterns as key patterns (key_alt, key_pos_off, key_n_pos, key_off), as number patterns and as terms, each batch as
+ * fmx_field_values_where_class_batch takes its own; a position is one character of a pattern's length, so the windows behind a key
+ * and behind a number start behind the last position.  The values and numbers behind ALL spellings of a pattern make one answer.
+ * key_pos_off and key_off are required even with m == 0.  FMX_E_ARG also as fmx_field_values_where_class_batch judges a class
+ * batch (max_ranges outside [1, FMX_CLASS_RANGES_MAX], offsets that decrease, pattern offsets behind the positions) */
+int fmx_number_stats_by_class_batch(const fmx_index *idx, const uint16_t *key_alt, const int32_t *key_pos_off, int32_t key_n_pos,
+                                    const int32_t *key_off, int32_t m, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos,
+                                    const int32_t *pat_off, int32_t n, const int32_t *by_of, const uint16_t *term_alt, const int32_t *term_pos_off,
+                                    int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges, const int32_t *query_off,
+                                    const uint8_t *term_kind, int32_t q, const int32_t *key_where_of, const int32_t *where_of, int32_t line_lo,
+                                    int32_t line_hi, const uint16_t *stop, int32_t n_stop, int32_t max_len, int32_t frac_digits,
+                                    const int32_t *permille, int32_t n_permille, int64_t *val_off, int32_t **lines, int64_t **text_off,
+                                    uint16_t **chars, int64_t *row_off, int32_t **count, uint64_t **sum_lo, uint64_t **sum_hi, int64_t **min,
+                                    int64_t **max, int64_t **pct, int32_t *no_key, int32_t *not_number, int32_t *overflow, int32_t *occurrences,
+                                    int32_t *kept, int32_t *status, int32_t *key_occurrences, int32_t *key_kept, int32_t *key_status,
+                                    int32_t *term_status);
+
 /* THE LINES THAT MATCH A QUERY WITH TERMS ON NUMBERS (latency_ms >= 500; size in 0 .. 67108863; status in 500 .. 599) — the host
  * forms of the two packed stages + fmx_hits_in_number_range_dev (below: the stage) + fmx_query_lines_of_hits_dev.  They are
  * fmx_match_query_batch's calls and its definitions hold unchanged: the n TERMS, query_off, term_kind (ALL / ANY / NONE; a query of
@@ -852,6 +913,61 @@ int fmx_numbers_of_hits_dev(const fmx_index *idx, int32_t n, const int32_t *term
                             int32_t n_permille, int32_t *d_count, uint64_t *d_sum_lo, uint64_t *d_sum_hi, int64_t *d_min, int64_t *d_max,
                             int64_t *d_pct, int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status, void *d_ws, size_t ws_bytes,
                             void *stream);
+/* STATISTICS BY KEY over device pointers (the key of a line, the groups, the rows and the invariant: fmx_number_stats_by_batch
+ * above), three stages on one stream; the caller reads stage b's m + 1 group offsets between b and c, as it reads G between
+ * fmx_values_of_hits_dev and fmx_values_fill_dev.  Integers only, no atomics — the results do not depend on scheduling; lanes go to
+ * hits, keys or rows, never to patterns; the grids are fmx_hit_lines_geometry's and the extract honours `block` and
+ * `groups_per_cu`; asynchronous on `stream`, nothing is allocated, nothing is synchronised beyond the staged host copy of the small
+ * arrays.  Every stage refuses with FMX_E_ARG, before anything is launched or written: null or negative arguments, n_hits > 2^31 -
+ * 1, a workspace smaller than its _scratch_bytes function says (which is 0 for an empty call or a shape the call refuses), a
+ * SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident.
+ *
+ * STAGE a, fmx_first_hits_of_lines_dev: THE FIRST HIT OF EVERY LINE.  Packed hits (d_hit_off, d_locs, n_hits) of m patterns as
+ * fmx_hits_in_lines_dev takes them — d_hit_off[0] may be non-zero, slots in front of it, behind d_hit_off[m] and beyond n_hits are
+ * no hits, any order; positions in [0, textLength] — go to d_first_off (m + 1 int64, d_first_off[0] = 0), d_first_lines and
+ * d_first_locs (room for the hits of the m patterns; entries behind d_first_off[m] keep the caller's values): per pattern its
+ * distinct lines ascending, each with the smallest position of a hit on it.  A lane per slot makes the key pattern | position; ONE
+ * rocPRIM radix sort over the bits in use; a lane per sorted slot finds its line (fences staged in LDS); a lane per sorted slot
+ * compares pattern and line with its predecessor's; an exclusive scan; a head stores its line and position.  About 30 bytes of
+ * workspace per slot.  m == 0: nothing is written; n_hits == 0: d_first_off is zeroed.  FMX_E_ARG also for an index without a
+ * line table.
+ *
+ * STAGE b, fmx_values_of_hits_groups_dev: fmx_values_of_hits_dev — its arguments, outputs, limits and refusals, d_hit_off[0] = 0 —
+ * with one more output, d_group_of_hit (n_hits ints): the index of each hit's group within its pattern (d_val_off[p] + it = the
+ * group), -1 for a slot that is no hit.  The grouping is exact for hits in any order, so it runs over stage a's hits, which stand
+ * in line order: d_count[g] is then the number of LINES that have key g.  Its workspace is its own
+ * (fmx_values_of_hits_groups_scratch_bytes: fmx_values_of_hits_scratch_bytes and four bytes per hit); fmx_values_fill_dev takes it
+ * unchanged.  On an index without extraction there are no groups, every d_group_of_hit is -1 and every status FMX_ST_NOT_ENABLED.
+ * fmx_values_of_hits_dev and fmx_values_of_hits_scratch_bytes answer what they always did.
+ *
+ * STAGE c, fmx_numbers_by_key_dev: THE ROWS.  Packed hits of n number patterns as fmx_numbers_of_hits_dev takes them.  term_len (n),
+ * by_of (n, each in [0, m)), val_off (m + 1: stage b's d_val_off, read by the caller) and permille are HOST arrays: validated, and
+ * copied into d_ws before the call returns.  d_first_off, d_first_lines: stage a's; d_group_of_first: stage b's d_group_of_hit over
+ * them.  d_row_off (n + 1 int64) gets the rows' offsets, R = d_row_off[n] = the sum over i of the groups of by_of[i]; d_count,
+ * d_sum_lo, d_sum_hi, d_min, d_max get R entries, d_pct R * P, d_no_key, d_not_number and d_overflow n; each nullable except
+ * d_row_off and (with R > 0) d_count; entries behind them keep the caller's values.  d_status as in fmx_numbers_of_hits_dev.  A
+ * lane per slot makes the window, finds its line and takes ONE lower bound in the first lines of its key pattern: the code of the
+ * slot is the group of the found first hit, B = the largest group count of the call for NO KEY, B + 1 not a number, B + 2 overflow;
+ * then the packed extract, the parse, the two stable sorts and the two running sums of fmx_numbers_of_hits_dev; a lane per PACKED
+ * row finds its pattern in the row offsets and takes the two lower bounds; a lane per pattern stores the three counters.
+ * n == 0: nothing is written; n_hits == 0 or an index without extraction: d_row_off is stored, the rows and the counters are
+ * zeroed (without extraction every status is FMX_ST_NOT_ENABLED).  FMX_E_ARG also for frac_digits outside [0, 9], n_permille
+ * outside [0, 16], a permille outside [0, 1000], a negative term_len, m == 0 with n > 0, a by_of outside [0, m), a val_off that
+ * starts below 0 or decreases, R above 2^27, R * max(P, 1) above 2^27, an index without a line table. */
+size_t fmx_first_hits_of_lines_scratch_bytes(int32_t m, int64_t n_hits);
+int fmx_first_hits_of_lines_dev(const fmx_index *idx, int32_t m, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits,
+                                int64_t *d_first_off, int32_t *d_first_lines, int32_t *d_first_locs, void *d_ws, size_t ws_bytes, void *stream);
+size_t fmx_values_of_hits_groups_scratch_bytes(int32_t n, int64_t n_hits, int32_t max_len);
+int fmx_values_of_hits_groups_dev(const fmx_index *idx, int32_t n, const int32_t *term_len, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                                  const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int64_t *d_val_off, int32_t *d_count,
+                                  int64_t *d_text_off, int32_t *d_group_of_hit, int32_t *d_status, void *d_ws, size_t ws_bytes, void *stream);
+size_t fmx_numbers_by_key_scratch_bytes(int32_t n, int64_t n_hits, int32_t n_permille);
+int fmx_numbers_by_key_dev(const fmx_index *idx, int32_t n, const int32_t *term_len, const int32_t *by_of, int32_t m, const int64_t *val_off,
+                           const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, const int64_t *d_first_off,
+                           const int32_t *d_first_lines, const int32_t *d_group_of_first, int32_t frac_digits, const int32_t *permille,
+                           int32_t n_permille, int64_t *d_row_off, int32_t *d_count, uint64_t *d_sum_lo, uint64_t *d_sum_hi, int64_t *d_min,
+                           int64_t *d_max, int64_t *d_pct, int32_t *d_no_key, int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status,
+                           void *d_ws, size_t ws_bytes, void *stream);
 /* THE HITS WHOSE NUMBER LIES IN A RANGE over device pointers (ranged patterns, the value of a hit and when it passes:
  * fmx_match_query_number_batch above).  Packed hits (d_hit_off, d_locs, n_hits) of n patterns exactly as fmx_hits_in_lines_dev takes
  * them — d_hit_off[0] may be non-zero, slots behind d_hit_off[n] and beyond n_hits are no hits, the order is SA-row order — and the

@@ -718,6 +718,96 @@ public:
         return s;
     }
 
+    // statistics of the number behind a pattern, GROUPED BY THE VALUE OF A FIELD of the same line (fmx.h "STATISTICS BY KEY"; stats
+    // count, sum(bytes=), p95(latency_ms=) by status=): byOf[i] names the key pattern number pattern i is grouped by; the key of a
+    // line is fieldValues' value (stop, maxLen) of the key pattern's first kept hit on it.  The groups of key pattern k are
+    // valOff[k] .. valOff[k + 1]: values[g], lines[g] = the lines that have that key; the rows are packed, row (i, g) at rowOff[i] + g:
+    // count, the exact sum = sumHi * 2^64 + sumLo, min, max, pct[row * P + j]; noKey / notNumber / overflow per number pattern.  The
+    // same query filters the key patterns' and the number patterns' hits (keyWhereOf, whereOf: -1 = none); needs buildLineTable().
+    // Statuses are not thrown by the batch form; numberStatsBy answers one number pattern by one key pattern and throws them.
+    struct NumberStatsBy {
+        int32_t permilles = 0;
+        std::vector<int64_t> valOff, rowOff;
+        std::vector<std::u16string> values;
+        std::vector<int32_t> lines, count;
+        std::vector<uint64_t> sumLo, sumHi;
+        std::vector<int64_t> min, max, pct;
+        std::vector<int32_t> noKey, notNumber, overflow, occurrences, kept, status, keyOccurrences, keyKept, keyStatus, termStatus;
+        double mean(size_t row) const {  // (a convenience of the host: the sum as a double)
+            return count[row] ? ((double)sumHi[row] * 18446744073709551616.0 + (double)sumLo[row]) / count[row] : 0.0;
+        }
+    };
+    NumberStatsBy numberStatsByBatch(const std::vector<std::u16string> &patterns, const std::vector<std::u16string> &keys,
+                                     const std::vector<int32_t> &byOf, const std::u16string &stop, int32_t maxLen,
+                                     const std::vector<Query> &queries, const std::vector<int32_t> &keyWhereOf, const std::vector<int32_t> &whereOf,
+                                     const std::vector<int32_t> &permille = {500, 950}, int32_t fracDigits = 0, int32_t lineLo = 0,
+                                     int32_t lineHi = INT32_MAX) const {
+        if (whereOf.size() != patterns.size() || byOf.size() != patterns.size()) throw std::invalid_argument("whereOf and byOf have one entry per pattern");
+        if (keyWhereOf.size() != keys.size()) throw std::invalid_argument("keyWhereOf has one entry per key pattern");
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        flattenQueries(queries, terms, kind, queryOff);
+        std::vector<uint16_t> chars, keyChars, termChars;
+        std::vector<int32_t> off, keyOff, termOff;
+        pack(patterns, chars, off);
+        pack(keys, keyChars, keyOff);
+        pack(terms, termChars, termOff);
+        NumberStatsBy out;
+        const size_t n = patterns.size(), m = keys.size(), P = permille.size();
+        out.permilles = (int32_t)P;
+        out.valOff.assign(m + 1, 0);
+        out.rowOff.assign(n + 1, 0);
+        for (std::vector<int32_t> *v : {&out.noKey, &out.notNumber, &out.overflow, &out.occurrences, &out.kept, &out.status}) v->assign(n + 1, 0);
+        for (std::vector<int32_t> *v : {&out.keyOccurrences, &out.keyKept, &out.keyStatus}) v->assign(m + 1, 0);
+        out.termStatus.assign(terms.size(), 0);
+        int32_t *lines = nullptr, *count = nullptr;
+        int64_t *textOff = nullptr, *vmin = nullptr, *vmax = nullptr, *pct = nullptr;
+        uint64_t *sumLo = nullptr, *sumHi = nullptr;
+        uint16_t *text = nullptr;
+        detail::check(fmx_number_stats_by_batch(h_, keyChars.data(), keyOff.data(), (int32_t)m, chars.data(), off.data(), (int32_t)n, byOf.data(),
+                                                termChars.data(), termOff.data(), (int32_t)terms.size(), queryOff.data(), kind.data(),
+                                                (int32_t)queries.size(), keyWhereOf.data(), whereOf.data(), lineLo, lineHi,
+                                                reinterpret_cast<const uint16_t *>(stop.data()), (int32_t)stop.size(), maxLen, fracDigits,
+                                                permille.data(), (int32_t)P, out.valOff.data(), &lines, &textOff, &text, out.rowOff.data(), &count,
+                                                &sumLo, &sumHi, &vmin, &vmax, &pct, out.noKey.data(), out.notNumber.data(), out.overflow.data(),
+                                                out.occurrences.data(), out.kept.data(), out.status.data(), out.keyOccurrences.data(),
+                                                out.keyKept.data(), out.keyStatus.data(), out.termStatus.data()),
+                      "fmx_number_stats_by_batch");
+        const size_t G = (size_t)out.valOff[m], R = (size_t)out.rowOff[n];
+        if (lines) {  // the ONE allocation: copied, then handed back
+            out.lines.assign(lines, lines + G);
+            for (size_t g = 0; g < G; ++g)
+                out.values.emplace_back(reinterpret_cast<const char16_t *>(text) + textOff[g], (size_t)(textOff[g + 1] - textOff[g]));
+            out.count.assign(count, count + R);
+            out.sumLo.assign(sumLo, sumLo + R);
+            out.sumHi.assign(sumHi, sumHi + R);
+            out.min.assign(vmin, vmin + R);
+            out.max.assign(vmax, vmax + R);
+            out.pct.assign(pct, pct + R * P);
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(lines));
+        }
+        for (std::vector<int32_t> *v : {&out.noKey, &out.notNumber, &out.overflow, &out.occurrences, &out.kept, &out.status, &out.keyOccurrences,
+                                        &out.keyKept, &out.keyStatus})
+            v->pop_back();
+        return out;
+    }
+    NumberStatsBy numberStatsBy(const std::u16string &pattern, const std::u16string &by, const std::u16string &stop = u" \t\r\n", int32_t maxLen = 32,
+                                const Query *where = nullptr, const std::vector<int32_t> &permille = {500, 950}, int32_t fracDigits = 0) const {
+        if (pattern.empty() || by.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        if (where)
+            for (const std::vector<std::u16string> *g : {&where->all, &where->any, &where->none})
+                for (const std::u16string &t : *g)
+                    if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const int32_t w = where ? 0 : -1;
+        const NumberStatsBy s = numberStatsByBatch({pattern}, {by}, {0}, stop, maxLen, where ? std::vector<Query>{*where} : std::vector<Query>{}, {w}, {w},
+                                                   permille, fracDigits);
+        detail::raise_for_status(s.status[0]);
+        detail::raise_for_status(s.keyStatus[0]);
+        for (int st : s.termStatus) detail::raise_for_status(st);
+        return s;
+    }
+
     // the text of ranges and of lines in ONE packed array (fmx.h "THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY"): range / line
     // i is chars[offsets[i] .. offsets[i + 1]) — what extract(start, stop, destination, 0) leaves in destination; memory follows
     // the sum of the lengths.  status[i] is the range's own (not thrown: one range out of the text does not hide the others);

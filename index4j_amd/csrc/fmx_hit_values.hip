@@ -22,6 +22,10 @@
 //   k_val_counts      a lane per group: the difference of the weight scan over its slots
 //   k_val_offsets     a lane per pattern: val_off[p] = the group id at the first sorted slot whose pattern is not below p
 //   k_val_fill        a lane per group: the representative's code units into the caller's array
+// and, only in launch_values_groups_of_hits (fmx_values_of_hits_groups_dev: the keys of "stats ... by", fmx_hit_by.hpp):
+//   k_val_run_groups  a lane per sorted slot: the group of its run, off the scan of the heads
+//   k_val_hit_groups  a lane per hit: its run off the scan of the run flags, that run's group, counted from its pattern's first
+// The grouping is exact for hits in any order — runs only shorten the sort — so these hits need not stand in SA-row order.
 // No atomics, integer arithmetic only: the result does not depend on the order the lanes run in.  Nothing here looks at the
 // image, so this file is compiled once, like fmx_sequence_lines.hip.
 #include <hip/hip_runtime.h>
@@ -251,6 +255,26 @@ __global__ __launch_bounds__(kFlatBlock) void k_val_fill(const uint16_t *const *
     }
 }
 
+// THE GROUP OF EVERY HIT (launch_values_groups_of_hits): sorted slot j holds run perm[j], and its group is the number of heads up to
+// and including it, less one — hscan is exclusive.  perm is a permutation of the slots, so every run is stored by one lane.
+__global__ __launch_bounds__(kFlatBlock) void k_val_run_groups(const uint32_t *__restrict__ skeys, const uint32_t *__restrict__ perm, int32_t n,
+                                                               const int32_t *__restrict__ head, const int32_t *__restrict__ hscan,
+                                                               int64_t n_hits, int32_t *__restrict__ run_group) {
+    for (int64_t j = (int64_t)blockIdx.x * kFlatBlock + threadIdx.x; j < n_hits; j += (int64_t)gridDim.x * kFlatBlock)
+        if (skeys[j] < (uint32_t)n) run_group[perm[j]] = hscan[j] + head[j] - 1;
+}
+
+// a lane per hit: its run is the number of run flags up to and including it, less one (scan is exclusive over n_hits + 1, so that
+// number is scan[i + 1]); its group counts from its pattern's first group.  A slot that is no hit gets -1.
+__global__ __launch_bounds__(kFlatBlock) void k_val_hit_groups(const int32_t *__restrict__ pat, int32_t n, const int32_t *__restrict__ scan,
+                                                               const int32_t *__restrict__ run_group, const int64_t *__restrict__ val_off,
+                                                               int64_t n_hits, int32_t *__restrict__ group_of_hit) {
+    for (int64_t i = (int64_t)blockIdx.x * kFlatBlock + threadIdx.x; i < n_hits; i += (int64_t)gridDim.x * kFlatBlock) {
+        const int32_t p = pat[i];
+        group_of_hit[i] = p < n ? (int32_t)(run_group[scan[i + 1] - 1] - val_off[p]) : -1;
+    }
+}
+
 __global__ __launch_bounds__(kFlatBlock) void k_val_status_all(int32_t *__restrict__ status, int32_t n, int32_t value) {
     for (int64_t p = (int64_t)blockIdx.x * kFlatBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kFlatBlock) status[p] = value;
 }
@@ -365,11 +389,17 @@ int launch_values_ranges(int32_t text_len, int n_cu, int32_t n, const int32_t *t
     return (int)hipGetLastError();
 }
 
-int launch_values_groups(int n_cu, int32_t n, int32_t n_stop, int32_t max_len, int64_t n_hits, const int64_t *hit_off,
-                         int64_t *val_off, int32_t *count, int64_t *text_off, int32_t *status, void *ws, size_t ws_bytes, void *stream) {
+namespace {
+
+// the workspace of the twin that also stores the group of every hit: val_ws, and behind it run_group (a group per run)
+size_t groups_of_hits_ws_total(const ValWs &w, int64_t n_hits) { return w.total + pad256(((size_t)n_hits + 1) * 4); }
+
+// group_of_hit == nullptr: launch_values_groups as it always was (nothing behind w.total is touched)
+int values_groups_impl(int n_cu, int32_t n, int32_t n_stop, int32_t max_len, int64_t n_hits, const int64_t *hit_off, int64_t *val_off,
+                       int32_t *count, int64_t *text_off, int32_t *status, int32_t *group_of_hit, void *ws, size_t ws_bytes, void *stream) {
     if (!shape_ok(n, n_hits, max_len) || n_stop < 0 || n_stop > kValuesMaxStop) return (int)hipErrorInvalidValue;
     const ValWs w = val_ws(n, n_hits, max_len);
-    if (!ws || ws_bytes < w.total) return (int)hipErrorInvalidValue;
+    if (!ws || ws_bytes < (group_of_hit ? groups_of_hits_ws_total(w, n_hits) : w.total)) return (int)hipErrorInvalidValue;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const int32_t *pat = region<int32_t>(ws, w.pat), *win_status = region<int32_t>(ws, w.win_status);
     const int64_t *win_off = region<int64_t>(ws, w.win_off);
@@ -425,8 +455,33 @@ int launch_values_groups(int n_cu, int32_t n, int32_t n_stop, int32_t max_len, i
     hipLaunchKernelGGL(k_val_counts, fg, fb, 0, st, hscan, wscan, group_start, n_hits, count);
     FMX_VAL_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_val_offsets, dim3((unsigned)pat_grid), fb, 0, st, skeys, hscan, n, n_hits, val_off);
+    if (group_of_hit) {
+        FMX_VAL_CHECK(hipGetLastError());
+        int32_t *run_group = region<int32_t>(ws, w.total);
+        hipLaunchKernelGGL(k_val_run_groups, fg, fb, 0, st, skeys, perm_a, n, head, hscan, n_hits, run_group);
+        FMX_VAL_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_val_hit_groups, fg, fb, 0, st, pat, n, scan, run_group, val_off, n_hits, group_of_hit);
+    }
 #undef FMX_VAL_CHECK
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+int launch_values_groups(int n_cu, int32_t n, int32_t n_stop, int32_t max_len, int64_t n_hits, const int64_t *hit_off,
+                         int64_t *val_off, int32_t *count, int64_t *text_off, int32_t *status, void *ws, size_t ws_bytes, void *stream) {
+    return values_groups_impl(n_cu, n, n_stop, max_len, n_hits, hit_off, val_off, count, text_off, status, nullptr, ws, ws_bytes, stream);
+}
+
+size_t values_groups_of_hits_scratch_bytes(int32_t n, int64_t n_hits, int32_t max_len) {
+    return shape_ok(n, n_hits, max_len) ? groups_of_hits_ws_total(val_ws(n, n_hits, max_len), n_hits) : 0;
+}
+
+int launch_values_groups_of_hits(int n_cu, int32_t n, int32_t n_stop, int32_t max_len, int64_t n_hits, const int64_t *hit_off, int64_t *val_off,
+                                 int32_t *count, int64_t *text_off, int32_t *status, int32_t *group_of_hit, void *ws, size_t ws_bytes,
+                                 void *stream) {
+    if (!group_of_hit) return (int)hipErrorInvalidValue;
+    return values_groups_impl(n_cu, n, n_stop, max_len, n_hits, hit_off, val_off, count, text_off, status, group_of_hit, ws, ws_bytes, stream);
 }
 
 int launch_values_fill(int n_cu, int64_t groups, const int64_t *text_off, uint16_t *chars, const void *ws, void *stream) {

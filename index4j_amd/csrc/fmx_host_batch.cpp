@@ -88,6 +88,13 @@ int check_where_of(int32_t n, const int32_t *where_of, int32_t q) {
     return FMX_OK;
 }
 
+int check_by_of(int32_t n, const int32_t *by_of, int32_t m) {
+    if (n > 0 && m <= 0) return api_fail(FMX_E_ARG, "number patterns without a key pattern (m == 0 with n > 0)");
+    for (int32_t i = 0; i < n; ++i)
+        if (by_of[i] < 0 || by_of[i] >= m) return api_fail(FMX_E_ARG, "by_of[" + std::to_string(i) + "] is outside 0 .. m - 1");
+    return FMX_OK;
+}
+
 int check_edges_array(const int32_t *edges, int32_t n_edges) {
     switch (fm_hist_edges_bad(edges, n_edges)) {
         case 0: return FMX_OK;

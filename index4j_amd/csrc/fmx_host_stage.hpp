@@ -1,5 +1,5 @@
 // fmx_host_stage.hpp — the host-stage layer of the C ABI: what the feature files (fmx_class_api.cpp, fmx_where_api.cpp,
-// fmx_hist_api.cpp, fmx_stats_api.cpp, fmx_range_api.cpp) see of a handle and of the packed host sequence of fmx_api.cpp, and what they share among
+// fmx_hist_api.cpp, fmx_stats_api.cpp, fmx_range_api.cpp, fmx_by_api.cpp) see of a handle and of the packed host sequence of fmx_api.cpp, and what they share among
 // themselves.  Host code only: no .hip file includes it.
 //   fmx_api.cpp          the views of a handle, extract_windows, check_query_arrays, values_between_call, hits_stage_call
 //   fmx_host_batch.cpp   the checks of a call's HOST arrays and the merge of terms and value patterns into ONE batch: no HIP
@@ -129,6 +129,8 @@ struct HitsFilter {
 // the call filters at all: a pattern asks for a query, or the window is not 0 .. INT32_MAX
 bool hits_filter_asked(int32_t n, const int32_t *where_of, int32_t line_lo = 0, int32_t line_hi = INT32_MAX);
 int check_where_of(int32_t n, const int32_t *where_of, int32_t q);
+// by_of (n entries, each 0 .. m - 1): the key pattern each number pattern is grouped by (fmx_number_stats_by_batch); n > 0 needs m > 0
+int check_by_of(int32_t n, const int32_t *by_of, int32_t m);
 // edges by fmx_line_hist.hpp's rules (n_edges >= 2, edges[0] >= 0, never decreasing)
 int check_edges_array(const int32_t *edges, int32_t n_edges);
 

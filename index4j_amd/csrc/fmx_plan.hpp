@@ -206,4 +206,37 @@ int launch_numbers_rows(int n_cu, int32_t n, const int64_t *hit_off, int64_t n_h
                         int32_t *count, uint64_t *sum_lo, uint64_t *sum_hi, int64_t *min, int64_t *max, int64_t *pct, int32_t *not_number,
                         int32_t *overflow, int32_t *status, void *ws, size_t ws_bytes, void *stream);
 
+
+// "STATS ... BY KEY" (fmx_hit_by.hpp has the definition): the three stages of fmx_first_hits_of_lines_dev,
+// fmx_values_of_hits_groups_dev and fmx_numbers_by_key_dev.  Each compiled once; the grids are hit_lines_geometry's; the launchers
+// return a hipError_t as int, `stream` is a hipStream_t, nothing is synchronised or allocated.  hipErrorInvalidValue before anything
+// is launched or written: too small a workspace, a shape outside the stage's scratch-size function (which is 0 then).
+// fmx_hit_first.hip — packed hits of m patterns -> first_off (m + 1), first_lines and first_locs (first_off[m] entries each, nothing
+// behind them): per pattern its distinct lines ascending, each with the smallest position of a hit on it.  T: the line table (required).
+size_t first_hits_scratch_bytes(int32_t m, int64_t n_hits);
+int launch_first_hits(const int32_t *T, int32_t count, int32_t text_len, int n_cu, int32_t m, const int64_t *hit_off, const int32_t *locs,
+                      int64_t n_hits, int64_t *first_off, int32_t *first_lines, int32_t *first_locs, void *ws, size_t ws_bytes, void *stream);
+// fmx_hit_values.hip — launch_values_groups with one more output: group_of_hit (n_hits ints) = the index of each hit's group within
+// its pattern, -1 for a slot that is no hit.  Its workspace is larger than launch_values_groups' (a group per run behind it); the
+// ranges and the fill are launch_values_ranges / launch_values_fill over the same workspace, values_windows over its front part.
+size_t values_groups_of_hits_scratch_bytes(int32_t n, int64_t n_hits, int32_t max_len);
+int launch_values_groups_of_hits(int n_cu, int32_t n, int32_t n_stop, int32_t max_len, int64_t n_hits, const int64_t *hit_off, int64_t *val_off,
+                                 int32_t *count, int64_t *text_off, int32_t *status, int32_t *group_of_hit, void *ws, size_t ws_bytes,
+                                 void *stream);
+// fmx_hit_numbers.hip — the numbers stage with the code of a hit = the group of its line's key.  term_len, by_of (n, each in [0, m)),
+// val_off (m + 1: the key patterns' group offsets, stage b's answer read by the caller) and permille are HOST arrays, judged again
+// (fm_by_rows_bad) and copied into the workspace before launch_numbers_by_key_ranges returns; row_off_out (device, n + 1; nullable)
+// gets the rows' offsets.  Three steps on one stream over one workspace, as launch_numbers_ranges / extract_windows /
+// launch_numbers_rows; count is required when there are rows, every other output nullable.
+size_t numbers_by_key_scratch_bytes(int32_t n, int64_t n_hits, int32_t n_permille);
+bool numbers_by_key_windows(void *ws, size_t ws_bytes, int32_t n, int64_t n_hits, int32_t n_permille, ValuesWindows *out);
+int launch_numbers_by_key_ranges(const int32_t *T, int32_t count, int32_t text_len, int n_cu, int32_t n, const int32_t *term_len,
+                                 const int32_t *by_of, int32_t m, const int64_t *val_off, const int64_t *hit_off, const int32_t *locs,
+                                 int64_t n_hits, const int64_t *first_off, const int32_t *first_lines, const int32_t *group_of_first,
+                                 const int32_t *permille, int32_t n_permille, int64_t *row_off_out, void *ws, size_t ws_bytes, void *stream);
+int launch_numbers_by_key_rows(int n_cu, int32_t n, const int32_t *by_of, int32_t m, const int64_t *val_off, const int64_t *hit_off,
+                               int64_t n_hits, int32_t frac_digits, int32_t n_permille, int32_t *count, uint64_t *sum_lo, uint64_t *sum_hi,
+                               int64_t *min, int64_t *max, int64_t *pct, int32_t *no_key, int32_t *not_number, int32_t *overflow,
+                               int32_t *status, void *ws, size_t ws_bytes, void *stream);
+
 }  // namespace fmx

@@ -178,6 +178,33 @@ class NumberStats:
         return np.array([s / c if c else float("nan") for s, c in zip(self.sum, self.count.tolist())], dtype=np.float64)
 
 
+class NumberStatsBy:
+    """number pattern i of a number_stats_by_batch answer, by its key pattern by_of[i]: groups = [dict(value, lines, count, sum, min, max,
+    pct, mean)] — sum an exact Python int, mean a float (nan for a group without numbers) — in the order of the values, or with
+    top=k the k groups with the most lines, ties by value; the per-pattern counters as ints"""
+
+    def __init__(self, out, top=None, i=0):
+        k = int(out["by_of"][i])  # the key pattern number pattern i is grouped by
+        k_lo, r_lo = int(out["val_off"][k]), int(out["row_off"][i])
+        text_off, chars = out["text_off"], out["chars"]
+        self.groups = []
+        for g in range(int(out["row_off"][i + 1]) - r_lo):
+            r, v = r_lo + g, k_lo + g
+            c, total = int(out["count"][r]), (int(out["sum_hi"][r]) << 64) | int(out["sum_lo"][r])
+            self.groups.append(dict(value=chars[text_off[v]:text_off[v + 1]].tobytes().decode("utf-16-le", "surrogatepass"), lines=int(out["lines"][v]),
+                                    count=c, sum=total, min=int(out["min"][r]), max=int(out["max"][r]), pct=out["pct"][r].tolist(),
+                                    mean=total / c if c else float("nan")))
+        if top is not None:  # (a stable sort: equal line counts keep the order of the values)
+            self.groups = sorted(self.groups, key=lambda grp: -grp["lines"])[:max(int(top), 0)]
+        self.no_key, self.not_number, self.overflow = int(out["no_key"][i]), int(out["not_number"][i]), int(out["overflow"][i])
+        self.occurrences, self.kept = int(out["occurrences"][i]), int(out["kept"][i])
+        self.key_occurrences, self.key_kept = int(out["key_occurrences"][k]), int(out["key_kept"][k])
+
+    def by_value(self):
+        """{value: group}"""
+        return {grp["value"]: grp for grp in self.groups}
+
+
 class FmIndex:
     """fm/FmIndex.java query surface.  `device=None` keeps the index on the host (build / save /
     load only); any query then fails loudly."""
@@ -801,6 +828,88 @@ class FmIndex:
                                         term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms, int(max_ranges)), n, n_terms,
                                        query_off, term_kind, where_of, edges, permille, frac_digits)
 
+    # ---- ... grouped by the value of a field of the same line (fmx.h "STATISTICS BY KEY") ----
+    def number_stats_by_batch(self, key_chars, key_offsets, chars, offsets, by_of, term_chars, term_offsets, query_off, term_kind, key_where_of,
+                              where_of, stop, max_len, lines=None, permille=(500, 950), frac_digits=0):
+        """statistics of the number behind every hit of the n number patterns (chars, offsets), grouped by the value behind the key
+        pattern by_of[i] of (key_chars, key_offsets) on the same line (fmx_number_stats_by_batch; stats count, sum(bytes=),
+        p95(latency_ms=) by status=).  The key of a line is field_values' value (stop, max_len) of the key pattern's first kept hit
+        on it; terms, query_off, term_kind and lines are field_values_where_batch's, key_where_of / where_of its where_of for the
+        key and the number patterns.  Needs build_line_table().  Returns a dict of arrays: val_off (m + 1), lines (G, the lines
+        that have each key), text_off (G + 1), chars — the groups as field_values_batch returns them; row_off (n + 1), count,
+        sum_lo, sum_hi, min, max (R), pct (R, P) — row row_off[i] + g is number pattern i in group g of key by_of[i]; no_key,
+        not_number, overflow, occurrences, kept, status (n); key_occurrences, key_kept, key_status (m); term_status."""
+        key_chars = np.ascontiguousarray(key_chars, dtype=np.uint16)
+        key_offsets = np.ascontiguousarray(key_offsets, dtype=np.int32)
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        term_chars = np.ascontiguousarray(term_chars, dtype=np.uint16)
+        term_offsets = np.ascontiguousarray(term_offsets, dtype=np.int32)
+        by_of = np.ascontiguousarray(by_of, dtype=np.int32)
+        m, n, n_terms = len(key_offsets) - 1, len(offsets) - 1, len(term_offsets) - 1
+        head = (key_chars.ctypes.data, key_offsets.ctypes.data, m, chars.ctypes.data, offsets.ctypes.data, n, by_of.ctypes.data, term_chars.ctypes.data,
+                term_offsets.ctypes.data, n_terms)
+        return self._number_stats_by_call(lib.fmx_number_stats_by_batch, "fmx_number_stats_by_batch", head, m, n, n_terms, by_of, query_off, term_kind,
+                                          key_where_of, where_of, stop, max_len, lines, permille, frac_digits)
+
+    def number_stats_by_class_batch(self, key_alt, key_pos_off, key_pat_off, alt, pos_off, pat_off, by_of, term_alt, term_pos_off, term_pat_off, query_off,
+                                    term_kind, key_where_of, where_of, stop, max_len, lines=None, permille=(500, 950), frac_digits=0,
+                                    max_ranges=CLASS_RANGES_DEFAULT):
+        """number_stats_by_batch with class patterns as key patterns, as number patterns and as terms (fmx_number_stats_by_class_batch; a
+        pattern's length is its number of positions): the keys and numbers behind ALL spellings of a pattern make one answer; same
+        returns"""
+        key_alt, key_pos_off, key_pat_off, key_n_pos, m = self._class_arrays(key_alt, key_pos_off, key_pat_off)
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        term_alt, term_pos_off, term_pat_off, term_n_pos, n_terms = self._class_arrays(term_alt, term_pos_off, term_pat_off)
+        by_of = np.ascontiguousarray(by_of, dtype=np.int32)
+        head = (key_alt.ctypes.data, key_pos_off.ctypes.data, key_n_pos, key_pat_off.ctypes.data, m, alt.ctypes.data, pos_off.ctypes.data, n_pos,
+                pat_off.ctypes.data, n, by_of.ctypes.data, term_alt.ctypes.data, term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms,
+                int(max_ranges))
+        return self._number_stats_by_call(lib.fmx_number_stats_by_class_batch, "fmx_number_stats_by_class_batch", head, m, n, n_terms, by_of, query_off,
+                                          term_kind, key_where_of, where_of, stop, max_len, lines, permille, frac_digits)
+
+    def _number_stats_by_call(self, call, name, head, m, n, n_terms, by_of, query_off, term_kind, key_where_of, where_of, stop, max_len, lines, permille,
+                              frac_digits):
+        if len(by_of) != n:
+            raise ValueError("by_of has %d entries for %d patterns" % (len(by_of), n))
+        query_off, term_kind, where_of, q, lo, hi = self._where_arrays(n, n_terms, query_off, term_kind, where_of, lines)
+        key_where_of = np.ascontiguousarray(key_where_of, dtype=np.int32)
+        if len(key_where_of) != m:
+            raise ValueError("key_where_of has %d entries for %d key patterns" % (len(key_where_of), m))
+        stop = as_chars(stop)
+        permille = np.ascontiguousarray(permille, dtype=np.int32).reshape(-1)
+        P = len(permille)
+        val_off, row_off = np.zeros(m + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        no_key, not_number, overflow, occurrences, kept, status = (np.zeros(n, dtype=np.int32) for _ in range(6))
+        key_occurrences, key_kept, key_status = (np.zeros(m, dtype=np.int32) for _ in range(3))
+        term_status = np.zeros(n_terms, dtype=np.int32)
+        ptr = [C.c_void_p() for _ in range(9)]  # lines (the allocation), text_off, chars, count, sum_lo, sum_hi, min, max, pct
+        check(call(self._h, *head, query_off.ctypes.data, term_kind.ctypes.data, q, key_where_of.ctypes.data, where_of.ctypes.data, lo, hi,
+                   stop.ctypes.data, len(stop), int(max_len), int(frac_digits), permille.ctypes.data, P, val_off.ctypes.data, C.byref(ptr[0]),
+                   C.byref(ptr[1]), C.byref(ptr[2]), row_off.ctypes.data, *(C.byref(x) for x in ptr[3:]), no_key.ctypes.data, not_number.ctypes.data,
+                   overflow.ctypes.data, occurrences.ctypes.data, kept.ctypes.data, status.ctypes.data, key_occurrences.ctypes.data,
+                   key_kept.ctypes.data, key_status.ctypes.data, term_status.ctypes.data), name)
+        G, R = int(val_off[m]), int(row_off[n])
+
+        def take(at, ctype, dtype, count):  # (the library's buffer is copied into arrays of NumPy's own)
+            if not at or count == 0:
+                return np.zeros(count, dtype)
+            return np.ctypeslib.as_array(C.cast(at, C.POINTER(ctype)), shape=(count,)).copy()
+
+        try:
+            group_lines = take(ptr[0], C.c_int32, np.int32, G)
+            text_off = take(ptr[1], C.c_int64, np.int64, G + 1) if ptr[0] else np.zeros(1, np.int64)
+            text = take(ptr[2], C.c_uint16, np.uint16, int(text_off[G]))
+            count = take(ptr[3], C.c_int32, np.int32, R)
+            sum_lo, sum_hi = take(ptr[4], C.c_uint64, np.uint64, R), take(ptr[5], C.c_uint64, np.uint64, R)
+            vmin, vmax = take(ptr[6], C.c_int64, np.int64, R), take(ptr[7], C.c_int64, np.int64, R)
+            pct = take(ptr[8], C.c_int64, np.int64, R * P).reshape(R, P)
+        finally:
+            lib.fmx_free_buffer(ptr[0])
+        return dict(by_of=by_of.copy(), val_off=val_off, lines=group_lines, text_off=text_off, chars=text, row_off=row_off, count=count, sum_lo=sum_lo, sum_hi=sum_hi,
+                    min=vmin, max=vmax, pct=pct, no_key=no_key, not_number=not_number, overflow=overflow, occurrences=occurrences, kept=kept,
+                    status=status, key_occurrences=key_occurrences, key_kept=key_kept, key_status=key_status, term_status=term_status)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -1157,6 +1266,38 @@ class FmIndex:
         for st in [out["status"][0]] + out["term_status"].tolist():
             raise_for_status(st)
         return NumberStats(out, 0)
+
+    def number_stats_by(self, pattern, by, stop=" \t\r\n", max_len=32, where=None, lines=None, permille=(500, 950), frac_digits=0, top=None,
+                        ignore_case=False):
+        """statistics of the number behind `pattern` grouped by the value behind `by` on the same line: stats count, sum(bytes=),
+        p95(latency_ms=) by status=.  The key of a line is field_values' value (stop, max_len) of the first hit of `by` on it;
+        where=dict(all=, any=, none=) and lines=(lo, hi) filter the hits of both patterns as in field_values.  Returns a
+        NumberStatsBy: groups = [dict(value, lines, count, sum (a Python int, exact), min, max, pct, mean)] in field_values' order —
+        with top=k the k groups with the most lines, ties by value, sorted on the host — and no_key, not_number, overflow,
+        occurrences, kept, key_occurrences, key_kept as ints.  ignore_case: both patterns and the filter's terms in any case, one
+        answer for all spellings (the values keep the text's case).  Needs build_line_table().  Only the groups and rows come down."""
+        p, k = as_chars(pattern), as_chars(by)
+        terms, kinds = [], []
+        for kind, word in enumerate(("all", "any", "none")):
+            group = (where or {}).get(word, ())
+            for t in ([group] if isinstance(group, str) else group):  # (a lone str is one term)
+                terms.append(as_chars(t))
+                kinds.append(kind)
+        if where is not None and set(where) - {"all", "any", "none"}:
+            raise ValueError("where takes all=, any= and none=")
+        if min((len(t) for t in terms + [p, k]), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        query_off, where_of = ([0, len(terms)], [0]) if where is not None else ([0], [-1])
+        if ignore_case:
+            out = self.number_stats_by_class_batch(*pack_class_patterns([_ignore_case(k)]), *pack_class_patterns([_ignore_case(p)]), [0],
+                                                   *pack_class_patterns([_ignore_case(t) for t in terms]), query_off, np.array(kinds, np.uint8),
+                                                   where_of, where_of, stop, max_len, lines, permille, frac_digits)
+        else:
+            out = self.number_stats_by_batch(*pack_patterns([k]), *pack_patterns([p]), [0], *pack_patterns(terms), query_off, np.array(kinds, np.uint8),
+                                             where_of, where_of, stop, max_len, lines, permille, frac_digits)
+        for st in [out["status"][0], out["key_status"][0]] + out["term_status"].tolist():
+            raise_for_status(st)
+        return NumberStatsBy(out, top)
 
     def line_text(self, lines):
         """the lines with these ids as a list of str (the boundary excluded); raises for an id that is no line"""

@@ -526,6 +526,54 @@ int fmx_number_stats_by_class_batch(const fmx_index *idx, const uint16_t *key_al
                                     int32_t *kept, int32_t *status, int32_t *key_occurrences, int32_t *key_kept, int32_t *key_status,
                                     int32_t *term_status);
 
+/* TOP VALUES PER BUCKET: THE TOP VALUES OF A FIELD PER BUCKET OF LINES, the stacked timeline (count by status over time where line
+ * has user=svc3: the ten most frequent values, each with its counts per bucket, plus "other") — the host forms of
+ * fmx_values_of_hits_groups_dev, fmx_values_top_histogram_dev and fmx_values_gather_rows_dev (below: the stages).  The value
+ * patterns, terms, query_off, term_kind, q, where_of, stop, n_stop and max_len are fmx_field_values_where_batch's, and so are a hit's
+ * value and the order of values; edges and n_edges are fmx_number_stats_where_batch's: edges == NULL with n_edges == 0 means B = 1,
+ * every line (no line table is needed unless a pattern asks for a query), otherwise the edge rules above.  top lies in [1, 65536].
+ * THE HITS OF THE CALL: with edges the filter's window of lines is [edges[0], edges[B]), so every kept hit has a bucket; kept[i] is
+ * the number of those hits, occurrences[i] stays the count in the whole text.  The values stage runs over the kept hits only.
+ * THE GROUPS of pattern i are fmx_field_values_where_batch's values and counts for that window, n_values[i] = G_i of them (n ints,
+ * out, nullable).
+ * THE ROWS of pattern i are its R_i = min(top, G_i) groups with the largest counts, in descending order of count; equal counts stay
+ * in value order (the smaller group index first).  row_off (n + 1 int64, out, row_off[0] = 0) packs them, R = row_off[n].  Per row
+ * r: (*row_count)[r] = the kept hits that have the value; (*row_group)[r] = the value's index among the pattern's distinct values in
+ * value order; (*text_off)[r] .. (*text_off)[r + 1] of *chars its code units (R + 1 int64); (*hist)[r * B + b] = the hits of that
+ * value in bucket b.  other (the caller's n * B ints): other[i * B + b] = the kept hits of pattern i in bucket b whose value is no
+ * row.  For every row the sum over b of hist[r * B + b] is row_count[r]; for every i and b the rows' hist[., b] and other[i * B + b]
+ * add up to hist[i * B + b] of fmx_hit_histogram_where_batch for the same call (with edges == NULL: to kept[i]); with top >= G_i
+ * the rows of i, sorted back by row_group, are fmx_field_values_where_batch's values and counts and other is zero.
+ * *row_count, *row_group, *text_off, *chars and *hist point into ONE allocation owned by the library until
+ * fmx_free_buffer((uint8_t *)*row_count); all are NULL when R = 0 (and on every failure).  On an index built without extraction
+ * every status is FMX_ST_NOT_ENABLED, there are no rows and other is zero; occurrences and kept are still filled.
+ * FMX_ST_TOO_MANY_RANGES (class form) as in fmx_field_values_where_class_batch.
+ * Only top * B counters and the text of top values per pattern come down, whatever G_i is.  Three waits beyond the filter's own: the
+ * kept offsets (they size the stages), ONE read of the n + 1 group offsets with the size of the groups' text behind them, and the 8
+ * bytes of the rows' packed text length.  Scratch: fmx_values_of_hits_groups_scratch_bytes and
+ * fmx_values_top_histogram_scratch_bytes per kept hit, four bytes per code unit of the groups' text.
+ * n == 0: FMX_OK, nothing is searched, row_off[0] = 0, term_status is zeroed.
+ * FMX_E_ARG as fmx_field_values_where_batch (max_len outside [1, 64], more than 64 stop units, the query arrays, a where_of outside
+ * -1 .. q - 1, kept hits * max_len above 2^35) and as fmx_number_stats_where_batch judges edges (an index without a line table:
+ * only when edges are given or a pattern asks for a query), for top outside [1, 65536] and for (int64) n * (top + 1) * B above
+ * 2^27; FMX_E_NO_DEVICE for a handle that is not resident; FMX_E_NOMEM leaves nothing behind.  A refused call stores nothing. */
+int fmx_field_values_histogram_where_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *term_pat,
+                                           const int32_t *term_off, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                           const int32_t *where_of, const int32_t *edges, int32_t n_edges, int32_t top, const uint16_t *stop,
+                                           int32_t n_stop, int32_t max_len, int32_t *n_values, int64_t *row_off, int32_t **row_count,
+                                           int32_t **row_group, int64_t **text_off, uint16_t **chars, int32_t **hist, int32_t *other,
+                                           int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *term_status);
+/* ... with class patterns as value patterns and as terms, as fmx_field_values_where_class_batch; a position is one character of the
+ * pattern's length.  The values behind ALL spellings of a pattern make one answer. */
+int fmx_field_values_histogram_where_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos,
+                                                 const int32_t *pat_off, int32_t n, const uint16_t *term_alt, const int32_t *term_pos_off,
+                                                 int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges,
+                                                 const int32_t *query_off, const uint8_t *term_kind, int32_t q, const int32_t *where_of,
+                                                 const int32_t *edges, int32_t n_edges, int32_t top, const uint16_t *stop, int32_t n_stop,
+                                                 int32_t max_len, int32_t *n_values, int64_t *row_off, int32_t **row_count, int32_t **row_group,
+                                                 int64_t **text_off, uint16_t **chars, int32_t **hist, int32_t *other, int32_t *occurrences,
+                                                 int32_t *kept, int32_t *status, int32_t *term_status);
+
 /* THE LINES THAT MATCH A QUERY WITH TERMS ON NUMBERS (latency_ms >= 500; size in 0 .. 67108863; status in 500 .. 599) — the host
  * forms of the two packed stages + fmx_hits_in_number_range_dev (below: the stage) + fmx_query_lines_of_hits_dev.  They are
  * fmx_match_query_batch's calls and its definitions hold unchanged: the n TERMS, query_off, term_kind (ALL / ANY / NONE; a query of
@@ -968,6 +1016,52 @@ int fmx_numbers_by_key_dev(const fmx_index *idx, int32_t n, const int32_t *term_
                            int32_t n_permille, int64_t *d_row_off, int32_t *d_count, uint64_t *d_sum_lo, uint64_t *d_sum_hi, int64_t *d_min,
                            int64_t *d_max, int64_t *d_pct, int32_t *d_no_key, int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status,
                            void *d_ws, size_t ws_bytes, void *stream);
+/* TOP VALUES PER BUCKET over device pointers (the rows, `other` and the invariants: fmx_field_values_histogram_where_batch above),
+ * two stages on one stream behind fmx_values_of_hits_groups_dev; the caller reads that stage's n + 1 group offsets in front of
+ * them.  Integers only, no atomics, no hashes — the results do not depend on scheduling; lanes go to groups, slots, counters or code
+ * units, never to patterns; the grids are fmx_hit_lines_geometry's; asynchronous on `stream`, nothing is allocated, nothing is
+ * synchronised beyond the staged host copy of the small arrays.  Both refuse with FMX_E_ARG, before anything is launched or
+ * written: null or negative arguments, n_hits > 2^31 - 1, top outside [1, 65536], a val_off that does not start at 0, decreases or
+ * holds more than 2^31 - 1 groups, a workspace smaller than the _scratch_bytes function says (which is 0 for an empty call or a shape
+ * the call refuses), a SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident.
+ * Nothing is tuned in this version: the block sizes and grids are the hits histogram's.
+ *
+ * fmx_values_top_histogram_dev: THE RANKS, THE ROWS AND THE COUNTERS.  val_off (n + 1: fmx_values_of_hits_groups_dev's d_val_off,
+ * read by the caller) and edges (as fmx_numbers_of_hits_dev takes them: NULL with n_edges == 0 is B = 1, every line, no line table
+ * needed) are HOST arrays: validated, and copied into d_ws before the call returns.  Packed hits (d_hit_off, d_locs, n_hits) as
+ * fmx_hits_histogram_dev takes them — d_hit_off[0] may be non-zero, slots in front of it, behind d_hit_off[n] and beyond n_hits are
+ * no hits; d_count (G = val_off[n] ints) and d_group_of_hit (n_hits ints, indexed by slot) are fmx_values_of_hits_groups_dev's over
+ * those hits; a slot whose group is outside its pattern's groups counts as "other".  d_row_off (n + 1 int64), d_row_group and
+ * d_row_count (R = the sum of min(top, G_i)), d_hist (R * B) and d_other (n * B) get the answer; entries behind them keep the
+ * caller's values.  A hit whose line lies in no bucket is in d_row_count (the group's count) and in no counter.
+ *   1. rank: a lane per group makes the key (pattern << 31) | (INT32_MAX - count), 31 + fm_bits(n) bits; ONE stable rocPRIM radix
+ *      sort carries the group's index; a lane per sorted group stores rank_of_group = min(sorted index - val_off[pattern], top) and,
+ *      below top, the row's group and count;
+ *   2. keys: a lane per slot finds its pattern (tiles of 1,024 slots, a slice of d_hit_off in LDS), its line (4,096 fences in LDS),
+ *      its bucket (up to 4,096 edges in LDS, more are searched in HBM) and makes the key pattern | rank in [0, top] | bucket in
+ *      [0, B]: fm_bits(n) + fm_bits(top) + fm_bits(B) bits, at most 31 + 17 + 28 — a key wider than 64 bits is refused (the limit
+ *      on n * (top + 1) * B keeps every accepted call below); 48 KiB of LDS per workgroup of 1,024 lanes;
+ *   3. sort: ONE rocPRIM radix sort over the bits in use;
+ *   4. counters: a lane per counter, (row, bucket) or (pattern, other, bucket), takes two lower bounds inside its pattern's slots.
+ * Workspace: 16 bytes per slot, 28 per group, and rocPRIM's.  n == 0: nothing is written; n_hits == 0: d_row_off and d_other are
+ * zeroed.  FMX_E_ARG also for (int64) n * (top + 1) * B above 2^27, bad edges, an index without a line table when edges are given.
+ *
+ * fmx_values_gather_rows_dev: THE TEXT OF THE ROWS.  After fmx_values_fill_dev has filled the text of ALL groups (d_text_off: G + 1,
+ * d_chars), the R selected groups' text goes to d_row_text_off (R + 1 int64) and d_row_chars, packed in row order: a lane per row
+ * finds its group (val_off[pattern] + d_row_group[r]) and its length, an exclusive scan, a lane per code unit copies one unit.
+ * val_off and top as above (HOST; copied into d_ws); max_units: a bound of the packed length that sizes the grid and d_row_chars'
+ * room (the units of all groups, d_text_off[G], will do); nothing is stored behind d_row_text_off[R] units.  No wait: the caller
+ * that needs the packed length reads the 8 bytes of d_row_text_off[R] — ONE wait — or sizes its buffer by the bound.  R == 0:
+ * d_row_text_off[0] is zeroed. */
+size_t fmx_values_top_histogram_scratch_bytes(int32_t n, int64_t n_groups, int64_t n_hits, int32_t n_edges);
+int fmx_values_top_histogram_dev(const fmx_index *idx, int32_t n, const int64_t *val_off, int32_t top, const int32_t *edges, int32_t n_edges,
+                                 const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, const int32_t *d_count,
+                                 const int32_t *d_group_of_hit, int64_t *d_row_off, int32_t *d_row_group, int32_t *d_row_count, int32_t *d_hist,
+                                 int32_t *d_other, void *d_ws, size_t ws_bytes, void *stream);
+size_t fmx_values_gather_rows_scratch_bytes(int32_t n, int64_t n_rows);
+int fmx_values_gather_rows_dev(const fmx_index *idx, int32_t n, const int64_t *val_off, int32_t top, int64_t max_units, const int32_t *d_row_group,
+                               const int64_t *d_text_off, const uint16_t *d_chars, int64_t *d_row_text_off, uint16_t *d_row_chars, void *d_ws,
+                               size_t ws_bytes, void *stream);
 /* THE HITS WHOSE NUMBER LIES IN A RANGE over device pointers (ranged patterns, the value of a hit and when it passes:
  * fmx_match_query_number_batch above).  Packed hits (d_hit_off, d_locs, n_hits) of n patterns exactly as fmx_hits_in_lines_dev takes
  * them — d_hit_off[0] may be non-zero, slots behind d_hit_off[n] and beyond n_hits are no hits, the order is SA-row order — and the

@@ -808,6 +808,78 @@ public:
         return s;
     }
 
+    // the top values of a field per bucket of lines, the stacked timeline (fmx.h "TOP VALUES PER BUCKET"; count by status over time
+    // where line has ...): fieldValuesWhereBatch's patterns, queries, whereOf, stop and maxLen, hitHistogramWhereBatch's edges — none
+    // at all: one bucket, every line, the device-side top-k of fieldValues (no line table needed unless a pattern asks for a query);
+    // with edges only the hits inside edges[0] .. edges[B] count.  The rows of pattern i are rowOff[i] .. rowOff[i + 1]: its min(top,
+    // nValues[i]) values with the largest counts, descending, equal counts in value order; values[r], rowCount[r], rowGroup[r] (the
+    // value's index among the pattern's distinct values), counts[r * B + b]; other[i * B + b] = the kept hits of no row.  Only the
+    // rows come down.  Statuses are not thrown by the batch form; fieldValuesHistogram answers one pattern and throws them.
+    struct FieldValuesHistogram {
+        int32_t buckets = 1;
+        std::vector<int64_t> rowOff;
+        std::vector<std::u16string> values;
+        std::vector<int32_t> rowCount, rowGroup, counts, other, nValues, occurrences, kept, status, termStatus;
+        std::vector<int32_t> row(size_t r) const { return {counts.begin() + r * (size_t)buckets, counts.begin() + (r + 1) * (size_t)buckets}; }
+        std::vector<int32_t> otherOf(size_t i) const { return {other.begin() + i * (size_t)buckets, other.begin() + (i + 1) * (size_t)buckets}; }
+    };
+    FieldValuesHistogram fieldValuesHistogramBatch(const std::vector<std::u16string> &patterns, const std::vector<Query> &queries,
+                                                   const std::vector<int32_t> &whereOf, const std::vector<int32_t> &edges = {}, int32_t top = 10,
+                                                   const std::u16string &stop = u" ", int32_t maxLen = 64) const {
+        if (whereOf.size() != patterns.size()) throw std::invalid_argument("whereOf has one entry per pattern");
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        flattenQueries(queries, terms, kind, queryOff);
+        std::vector<uint16_t> chars, termChars;
+        std::vector<int32_t> off, termOff;
+        pack(patterns, chars, off);
+        pack(terms, termChars, termOff);
+        FieldValuesHistogram out;
+        const size_t n = patterns.size();
+        out.buckets = edges.empty() ? 1 : edges.size() > 1 ? (int32_t)edges.size() - 1 : 0;
+        out.rowOff.assign(n + 1, 0);
+        out.other.assign(n * (size_t)out.buckets + 1, 0);
+        for (std::vector<int32_t> *v : {&out.nValues, &out.occurrences, &out.kept, &out.status}) v->assign(n + 1, 0);
+        out.termStatus.assign(terms.size(), 0);
+        int32_t *rowCount = nullptr, *rowGroup = nullptr, *hist = nullptr;
+        int64_t *textOff = nullptr;
+        uint16_t *text = nullptr;
+        detail::check(fmx_field_values_histogram_where_batch(h_, chars.data(), off.data(), (int32_t)n, termChars.data(), termOff.data(),
+                                                             (int32_t)terms.size(), queryOff.data(), kind.data(), (int32_t)queries.size(),
+                                                             whereOf.data(), edges.empty() ? nullptr : edges.data(), (int32_t)edges.size(), top,
+                                                             reinterpret_cast<const uint16_t *>(stop.data()), (int32_t)stop.size(), maxLen,
+                                                             out.nValues.data(), out.rowOff.data(), &rowCount, &rowGroup, &textOff, &text, &hist,
+                                                             out.other.data(), out.occurrences.data(), out.kept.data(), out.status.data(),
+                                                             out.termStatus.data()),
+                      "fmx_field_values_histogram_where_batch");
+        const size_t R = (size_t)out.rowOff[n];
+        if (rowCount) {  // the ONE allocation: copied, then handed back
+            out.rowCount.assign(rowCount, rowCount + R);
+            out.rowGroup.assign(rowGroup, rowGroup + R);
+            out.counts.assign(hist, hist + R * (size_t)out.buckets);
+            for (size_t r = 0; r < R; ++r)
+                out.values.emplace_back(reinterpret_cast<const char16_t *>(text) + textOff[r], (size_t)(textOff[r + 1] - textOff[r]));
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(rowCount));
+        }
+        out.other.pop_back();
+        for (std::vector<int32_t> *v : {&out.nValues, &out.occurrences, &out.kept, &out.status}) v->pop_back();
+        return out;
+    }
+    FieldValuesHistogram fieldValuesHistogram(const std::u16string &pattern, const std::vector<int32_t> &edges = {}, int32_t top = 10,
+                                              const Query *where = nullptr, const std::u16string &stop = u" ", int32_t maxLen = 64) const {
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        if (where)
+            for (const std::vector<std::u16string> *g : {&where->all, &where->any, &where->none})
+                for (const std::u16string &t : *g)
+                    if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const FieldValuesHistogram h = fieldValuesHistogramBatch({pattern}, where ? std::vector<Query>{*where} : std::vector<Query>{}, {where ? 0 : -1},
+                                                                 edges, top, stop, maxLen);
+        detail::raise_for_status(h.status[0]);
+        for (int st : h.termStatus) detail::raise_for_status(st);
+        return h;
+    }
+
     // the text of ranges and of lines in ONE packed array (fmx.h "THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY"): range / line
     // i is chars[offsets[i] .. offsets[i + 1]) — what extract(start, stop, destination, 0) leaves in destination; memory follows
     // the sum of the lengths.  status[i] is the range's own (not thrown: one range out of the text does not hide the others);

@@ -239,4 +239,29 @@ int launch_numbers_by_key_rows(int n_cu, int32_t n, const int32_t *by_of, int32_
                                int64_t *min, int64_t *max, int64_t *pct, int32_t *no_key, int32_t *not_number, int32_t *overflow,
                                int32_t *status, void *ws, size_t ws_bytes, void *stream);
 
+// fmx_value_hist.hip — THE TOP VALUES OF A FIELD PER BUCKET OF LINES (fmx_values_top_histogram_dev, fmx_values_gather_rows_dev;
+// fmx_value_hist.hpp has the definition).  Compiled once; the grids are hit_lines_geometry's; the launchers return a hipError_t as
+// int, `stream` is a hipStream_t, nothing is synchronised or allocated.  val_off (n + 1: the values stage's group offsets, read by the
+// caller, val_off[0] = 0) and edges (n_edges >= 2 by fmx_line_hist.hpp's rules, or none at all: n_edges == 0, B = 1, T not needed)
+// are HOST arrays; they are judged again (fm_vh_shape_bad) and copied into the workspace before the launcher returns.
+// hipErrorInvalidValue before anything is launched or written: too small a workspace, a shape outside the scratch-size function's
+// (which is 0 then), top outside [1, 65536], n * (top + 1) * B beyond 2^27.  n <= 0 or n_hits <= 0: nothing is done.
+// launch_values_top_histogram: group_count (G = val_off[n] ints) and group_of_hit (n_hits ints) are launch_values_groups_of_hits'
+// over the same packed hits; row_off_out (n + 1), row_group and row_count (R each), hist (R * B), other (n * B): nothing behind them.
+size_t values_top_histogram_scratch_bytes(int32_t n, int64_t n_groups, int64_t n_hits, int32_t n_edges);
+int launch_values_top_histogram(const int32_t *T, int32_t count, int n_cu, int32_t n, const int64_t *val_off, int32_t top, const int32_t *edges,
+                                int32_t n_edges, const int64_t *hit_off, const int32_t *locs, int64_t n_hits, const int32_t *group_count,
+                                const int32_t *group_of_hit, int64_t *row_off_out, int32_t *row_group, int32_t *row_count, int32_t *hist,
+                                int32_t *other, void *ws, size_t ws_bytes, void *stream);
+// launch_values_gather_rows: the text of the R rows (row r of pattern p: group val_off[p] + row_group[r]) out of the text of ALL
+// groups (text_off: G + 1, chars: launch_values_fill's) into row_text_off (R + 1) and row_chars; max_units: a bound of the packed
+// length that sizes the grid (the units of all groups will do); nothing is stored behind row_text_off[R] units.
+// launch_values_groups_units: *out (device) = text_off[val_off[n]], the code units of all groups' text (val_off, text_off: the values
+// stage's, on the device), so that ONE read brings the group offsets and that size down
+int launch_values_groups_units(const int64_t *val_off, int32_t n, const int64_t *text_off, int64_t *out, void *stream);
+size_t values_gather_rows_scratch_bytes(int32_t n, int64_t n_rows);
+int launch_values_gather_rows(int n_cu, int32_t n, const int64_t *val_off, int32_t top, int64_t max_units, const int32_t *row_group,
+                              const int64_t *text_off, const uint16_t *chars, int64_t *row_text_off, uint16_t *row_chars, void *ws,
+                              size_t ws_bytes, void *stream);
+
 }  // namespace fmx

@@ -205,6 +205,24 @@ class NumberStatsBy:
         return {grp["value"]: grp for grp in self.groups}
 
 
+class FieldValuesHistogram:
+    """pattern i of a field_values_histogram_where_batch answer: rows = [dict(value, count, group, hist)] — the top values in descending
+    order of count, ties in value order; group the value's index among the pattern's distinct values, hist its B counters as a list —
+    other (B ints: the kept hits whose value is no row), and n_values, kept, occurrences as ints"""
+
+    def __init__(self, out, i=0):
+        text_off, chars = out["text_off"], out["chars"]
+        self.rows = [dict(value=chars[text_off[r]:text_off[r + 1]].tobytes().decode("utf-16-le", "surrogatepass"), count=int(out["row_count"][r]),
+                          group=int(out["row_group"][r]), hist=out["hist"][r].tolist())
+                     for r in range(int(out["row_off"][i]), int(out["row_off"][i + 1]))]
+        self.other = out["other"][i].tolist()
+        self.n_values, self.kept, self.occurrences = int(out["n_values"][i]), int(out["kept"][i]), int(out["occurrences"][i])
+
+    def by_value(self):
+        """{value: row}"""
+        return {row["value"]: row for row in self.rows}
+
+
 class FmIndex:
     """fm/FmIndex.java query surface.  `device=None` keeps the index on the host (build / save /
     load only); any query then fails loudly."""
@@ -910,6 +928,70 @@ class FmIndex:
                     min=vmin, max=vmax, pct=pct, no_key=no_key, not_number=not_number, overflow=overflow, occurrences=occurrences, kept=kept,
                     status=status, key_occurrences=key_occurrences, key_kept=key_kept, key_status=key_status, term_status=term_status)
 
+    # ---- the top values of a field per bucket of lines, the stacked timeline (fmx.h "TOP VALUES PER BUCKET") ----
+    def _field_values_histogram_call(self, call, name, head, n, n_terms, query_off, term_kind, where_of, edges, top, stop, max_len):
+        query_off, term_kind, where_of, q, _, _ = self._where_arrays(n, n_terms, query_off, term_kind, where_of, None)
+        if edges is None:
+            edges_ptr, n_edges, B = None, 0, 1
+        else:
+            edges, B = self._edges(edges)
+            edges_ptr, n_edges = edges.ctypes.data, len(edges)
+        stop = as_chars(stop)
+        n_values, occurrences, kept, status = (np.zeros(n, dtype=np.int32) for _ in range(4))
+        row_off = np.zeros(n + 1, dtype=np.int64)
+        other = np.zeros((n, B), dtype=np.int32)
+        term_status = np.zeros(n_terms, dtype=np.int32)
+        ptr = [C.c_void_p() for _ in range(5)]  # row_count (the allocation), row_group, text_off, chars, hist
+        check(call(self._h, *head, query_off.ctypes.data, term_kind.ctypes.data, q, where_of.ctypes.data, edges_ptr, n_edges, int(top),
+                   stop.ctypes.data, len(stop), int(max_len), n_values.ctypes.data, row_off.ctypes.data, *(C.byref(x) for x in ptr),
+                   other.ctypes.data, occurrences.ctypes.data, kept.ctypes.data, status.ctypes.data, term_status.ctypes.data), name)
+        R = int(row_off[n])
+
+        def take(at, ctype, dtype, count):  # (the library's buffer is copied into arrays of NumPy's own)
+            if not at or count == 0:
+                return np.zeros(count, dtype)
+            return np.ctypeslib.as_array(C.cast(at, C.POINTER(ctype)), shape=(count,)).copy()
+
+        try:
+            row_count, row_group = take(ptr[0], C.c_int32, np.int32, R), take(ptr[1], C.c_int32, np.int32, R)
+            text_off = take(ptr[2], C.c_int64, np.int64, R + 1) if ptr[0] else np.zeros(1, np.int64)
+            text = take(ptr[3], C.c_uint16, np.uint16, int(text_off[R]))
+            hist = take(ptr[4], C.c_int32, np.int32, R * B).reshape(R, B)
+        finally:
+            lib.fmx_free_buffer(ptr[0])
+        return dict(n_values=n_values, row_off=row_off, row_count=row_count, row_group=row_group, text_off=text_off, chars=text, hist=hist,
+                    other=other, occurrences=occurrences, kept=kept, status=status, term_status=term_status)
+
+    def field_values_histogram_where_batch(self, chars, offsets, term_chars, term_offsets, query_off, term_kind, where_of, edges=None, top=10,
+                                           stop=" ", max_len=64):
+        """the top values that follow every pattern, each with its hits per bucket of lines, and the rest as "other"
+        (fmx_field_values_histogram_where_batch; count by status over time where line has ...): field_values_where_batch's patterns,
+        terms, query_off, term_kind, where_of, stop and max_len, hit_histogram_where_batch's edges (None: one bucket, every line —
+        the device-side top-k of field_values).  With edges only the hits inside edges[0] .. edges[B] count.  Returns a dict of
+        arrays: n_values (n: the distinct values), row_off (n + 1) — the rows of pattern i are row_off[i] .. row_off[i + 1], its
+        min(top, n_values[i]) values with the largest counts, descending, ties in value order —, row_count, row_group (R: the
+        value's index among the pattern's values), text_off (R + 1), chars, hist (R, B), other (n, B), occurrences, kept, status (n),
+        term_status.  Only the rows come down, however many values a pattern has."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        term_chars = np.ascontiguousarray(term_chars, dtype=np.uint16)
+        term_offsets = np.ascontiguousarray(term_offsets, dtype=np.int32)
+        n, n_terms = len(offsets) - 1, len(term_offsets) - 1
+        head = (chars.ctypes.data, offsets.ctypes.data, n, term_chars.ctypes.data, term_offsets.ctypes.data, n_terms)
+        return self._field_values_histogram_call(lib.fmx_field_values_histogram_where_batch, "fmx_field_values_histogram_where_batch", head, n,
+                                                 n_terms, query_off, term_kind, where_of, edges, top, stop, max_len)
+
+    def field_values_histogram_where_class_batch(self, alt, pos_off, pat_off, term_alt, term_pos_off, term_pat_off, query_off, term_kind, where_of,
+                                                 edges=None, top=10, stop=" ", max_len=64, max_ranges=CLASS_RANGES_DEFAULT):
+        """field_values_histogram_where_batch with class patterns as value patterns and as terms
+        (fmx_field_values_histogram_where_class_batch): the values behind ALL spellings of a pattern make one answer; same returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        term_alt, term_pos_off, term_pat_off, term_n_pos, n_terms = self._class_arrays(term_alt, term_pos_off, term_pat_off)
+        head = (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, term_alt.ctypes.data, term_pos_off.ctypes.data, term_n_pos,
+                term_pat_off.ctypes.data, n_terms, int(max_ranges))
+        return self._field_values_histogram_call(lib.fmx_field_values_histogram_where_class_batch, "fmx_field_values_histogram_where_class_batch",
+                                                 head, n, n_terms, query_off, term_kind, where_of, edges, top, stop, max_len)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -1298,6 +1380,35 @@ class FmIndex:
         for st in [out["status"][0], out["key_status"][0]] + out["term_status"].tolist():
             raise_for_status(st)
         return NumberStatsBy(out, top)
+
+    def field_values_histogram(self, pattern, edges=None, top=10, where=None, stop=" ", max_len=64, ignore_case=False):
+        """the `top` most frequent values that follow `pattern`, each with its occurrences per bucket of lines, and the rest as
+        "other": count by status over time where line has user=svc3, the stacked timeline.  edges as in hit_histogram (None: one
+        bucket, every line — the top-k of field_values, ranked on the device); where=dict(all=, any=, none=) as in field_values.
+        Returns a FieldValuesHistogram: rows = [dict(value, count, group, hist)] in descending order of count, ties in value order,
+        other (B ints), n_values, kept, occurrences.  Only the rows come down, however many distinct values there are."""
+        p = as_chars(pattern)
+        terms, kinds = [], []
+        for kind, word in enumerate(("all", "any", "none")):
+            group = (where or {}).get(word, ())
+            for t in ([group] if isinstance(group, str) else group):  # (a lone str is one term)
+                terms.append(as_chars(t))
+                kinds.append(kind)
+        if where is not None and set(where) - {"all", "any", "none"}:
+            raise ValueError("where takes all=, any= and none=")
+        if min((len(t) for t in terms + [p]), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        query_off, where_of = ([0, len(terms)], [0]) if where is not None else ([0], [-1])
+        if ignore_case:
+            out = self.field_values_histogram_where_class_batch(*pack_class_patterns([_ignore_case(p)]),
+                                                                *pack_class_patterns([_ignore_case(t) for t in terms]), query_off,
+                                                                np.array(kinds, np.uint8), where_of, edges, top, stop, max_len)
+        else:
+            out = self.field_values_histogram_where_batch(*pack_patterns([p]), *pack_patterns(terms), query_off, np.array(kinds, np.uint8), where_of,
+                                                          edges, top, stop, max_len)
+        for st in [out["status"][0]] + out["term_status"].tolist():
+            raise_for_status(st)
+        return FieldValuesHistogram(out, 0)
 
     def line_text(self, lines):
         """the lines with these ids as a list of str (the boundary excluded); raises for an id that is no line"""

@@ -465,6 +465,50 @@ int fmx_number_stats_where_class_batch(const fmx_index *idx, const uint16_t *alt
                                        uint64_t *sum_hi, int64_t *min, int64_t *max, int64_t *pct, int32_t *not_number, int32_t *overflow,
                                        int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *term_status);
 
+/* THE LINES RANKED BY THE NUMBER BEHIND A PATTERN (... | sort -k latency -nr | head -10: "show me the ten slowest requests") — the
+ * host forms of fmx_top_lines_of_hits_dev (below: the stage).  For number pattern i of the n value patterns:
+ * THE KEPT HITS are exactly fmx_number_stats_where_batch's without edges (its value patterns, terms, query_off, term_kind, q and
+ * where_of), further cut by the window of lines line_lo <= L < line_hi of fmx_field_values_where_batch (0 .. INT32_MAX: every
+ * line).  A hit belongs to the line of its first character.
+ * THE VALUE OF A HIT is fmx_number_stats_where_batch's, bit for bit (the window of 32 code units behind the pattern, ONE
+ * frac_digits in [0, 9] per call).  Only the hits that parse take part; the others are counted per pattern as not_number[i] and
+ * overflow[i].
+ * THE ORDER: descending[i] (one byte per pattern): 1 is largest first, 0 smallest first.
+ * THE CANDIDATE OF A LINE is the kept parsing hit on it that ranks best in that order; among hits of equal value the smallest
+ * text position wins.  A line without a parsing kept hit has no candidate.
+ * THE RANKING: the candidates of pattern i ordered by value in the order asked, equal values by ascending line id — a total order,
+ * a line has one candidate.  lines[i] = the candidates, numbers[i] = the parsing kept hits, so
+ *     numbers[i] + not_number[i] + overflow[i] = kept[i].
+ * THE ROWS: first >= 0 and top >= 1 hold for the whole call; the rows of pattern i are the ranks first .. first + top - 1:
+ * rows[i] = min(top, max(0, lines[i] - first)).  Row (i, j) lives at i * top + j: row_line (int32), row_value (int64), row_loc
+ * (int32: the candidate's position); the entries at j >= rows[i] are stored as 0.  Every output is nullable except rows.
+ * occurrences, kept, status and term_status as in fmx_number_stats_where_batch.  On an index built without extraction every
+ * status is FMX_ST_NOT_ENABLED, all rows and counters are zero, occurrences and kept are still filled.  A window the packed
+ * extract ran literally hands its status to its pattern.  The terms are plain strings: a ranged term (fmx_match_query_number_batch)
+ * is not taken yet.
+ * The packed stages up to the filter run as for the number statistics (skipped when nothing filters), then
+ * fmx_top_lines_of_hits_dev over the kept hits; when no value pattern has a hit nothing is launched for the stage.  Only the
+ * n x top rows and the small per-pattern and per-term arrays come down, never the hits.
+ * FMX_E_ARG as fmx_number_stats_where_batch and fmx_field_values_where_batch judge their arguments, for frac_digits outside [0, 9],
+ * first < 0, top < 1, (int64) n * top above 2^27, and ALWAYS for an index without a line table (the answer is lines);
+ * FMX_E_NO_DEVICE for a handle that is not resident; FMX_E_NOMEM leaves nothing behind.  n == 0: FMX_OK, nothing is searched and
+ * term_status is zeroed. */
+int fmx_top_lines_where_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *term_pat,
+                              const int32_t *term_off, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                              const int32_t *where_of, int32_t line_lo, int32_t line_hi, const uint8_t *descending, int32_t frac_digits,
+                              int32_t first, int32_t top, int32_t *rows, int32_t *row_line, int64_t *row_value, int32_t *row_loc, int32_t *lines,
+                              int32_t *numbers, int32_t *not_number, int32_t *overflow, int32_t *occurrences, int32_t *kept, int32_t *status,
+                              int32_t *term_status);
+/* ... with class patterns as value patterns and as terms, as fmx_number_stats_where_class_batch; a position is one character of
+ * the pattern's length */
+int fmx_top_lines_where_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off,
+                                    int32_t n, const uint16_t *term_alt, const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off,
+                                    int32_t n_terms, int32_t max_ranges, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                    const int32_t *where_of, int32_t line_lo, int32_t line_hi, const uint8_t *descending, int32_t frac_digits,
+                                    int32_t first, int32_t top, int32_t *rows, int32_t *row_line, int64_t *row_value, int32_t *row_loc,
+                                    int32_t *lines, int32_t *numbers, int32_t *not_number, int32_t *overflow, int32_t *occurrences, int32_t *kept,
+                                    int32_t *status, int32_t *term_status);
+
 /* STATISTICS BY KEY: THE NUMBER BEHIND A PATTERN, GROUPED BY THE VALUE OF A FIELD OF THE SAME LINE (stats count, sum(bytes=),
  * p95(latency_ms=) by status=) — the host form of the three stages fmx_first_hits_of_lines_dev, fmx_values_of_hits_groups_dev and
  * fmx_numbers_by_key_dev (below).  A call has m KEY PATTERNS (key_pat, key_off) and n NUMBER PATTERNS (pat, pat_off); by_of[i] in
@@ -961,6 +1005,38 @@ int fmx_numbers_of_hits_dev(const fmx_index *idx, int32_t n, const int32_t *term
                             int32_t n_permille, int32_t *d_count, uint64_t *d_sum_lo, uint64_t *d_sum_hi, int64_t *d_min, int64_t *d_max,
                             int64_t *d_pct, int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status, void *d_ws, size_t ws_bytes,
                             void *stream);
+/* THE LINES RANKED BY THE NUMBER BEHIND A PATTERN over device pointers (the value of a hit, the candidate of a line, the ranking
+ * and the rows: fmx_top_lines_where_batch above).  Packed hits (d_hit_off, d_locs, n_hits) of n patterns exactly as
+ * fmx_numbers_of_hits_dev takes them — d_hit_off has n + 1 entries, d_hit_off[0] may be non-zero, slots in front of it, behind
+ * d_hit_off[n] and beyond n_hits are no hits, the order is SA-row order; every hit given is a kept hit (the window of lines is the
+ * filter stage's).  term_len (n, the patterns' lengths) and descending (n bytes) are HOST arrays: validated, and copied into d_ws
+ * before the call returns.  d_rows, d_lines, d_numbers, d_not_number and d_overflow get n entries, d_row_line, d_row_value and
+ * d_row_loc n * top; each is nullable except d_rows; entries behind them keep the caller's values.  d_status (nullable, n ints the
+ * caller has initialised): a window the packed extract ran literally hands its status to its pattern; on an index without
+ * extraction every status is FMX_ST_NOT_ENABLED and every row and counter zero.
+ * A lane per slot makes the window and the key pattern | position (the slice of d_hit_off staged in LDS); the packed extract fills
+ * all windows (redo launch included); a lane per slot parses its window into the ordered value u = descending ? INT64_MAX - value :
+ * value — a slot that does not parse gets the pattern n, its reason goes into one word of two halves whose exclusive scan gives
+ * not_number and overflow of every pattern; ONE rocPRIM radix sort by pattern | position over the bits in use (lines never decrease
+ * within a pattern); a lane per sorted slot finds its line (the fences staged in LDS); rocPRIM's reduce_by_key over the runs of
+ * equal (pattern, line) keeps the minimum of (u, position) — a lane's work does not grow with the hits of one line; the candidates
+ * lie in (pattern, line) order, so one stable sort by u (63 bits) and one stable sort over the pattern's bits rank them, stability
+ * being the tie rule; a lane per pattern reads its segment, lines, rows, numbers and the two reasons; a lane per row (i, j) reads
+ * rank first + j.  Integers only, no atomics of its own — the result does not depend on scheduling; lanes go to slots, keys or
+ * rows, never to patterns or lines; the grids are fmx_hit_lines_geometry's and the extract honours `block` and `groups_per_cu`;
+ * asynchronous on `stream`, nothing is allocated, nothing is synchronised beyond the staged host copy of the small arrays.
+ * d_ws: at least fmx_top_lines_of_hits_scratch_bytes(n, n_hits, top) bytes (about 250 per slot: the window's 64, four 8-byte sort
+ * arrays, the reasons and their scan, the runs' and candidates' keys and pairs, the ranking's index and pattern arrays, the ranges
+ * and offsets, the extract's scratch, rocPRIM's temporary storage); 0 for an empty call or a shape the call refuses.  n == 0:
+ * nothing is written; n_hits == 0: the per-pattern counters and the rows are zeroed and nothing else is written.
+ * FMX_E_ARG for null or negative arguments, n_hits > 2^31 - 1, frac_digits outside [0, 9], first < 0, top < 1, (int64) n * top
+ * above 2^27, a negative term_len, an index without a line table, a workspace that is too small (nothing is launched, nothing is
+ * written), a SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident. */
+size_t fmx_top_lines_of_hits_scratch_bytes(int32_t n, int64_t n_hits, int32_t top);
+int fmx_top_lines_of_hits_dev(const fmx_index *idx, int32_t n, const int32_t *term_len, const uint8_t *descending, const int64_t *d_hit_off,
+                              const int32_t *d_locs, int64_t n_hits, int32_t frac_digits, int32_t first, int32_t top, int32_t *d_rows,
+                              int32_t *d_row_line, int64_t *d_row_value, int32_t *d_row_loc, int32_t *d_lines, int32_t *d_numbers,
+                              int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status, void *d_ws, size_t ws_bytes, void *stream);
 /* STATISTICS BY KEY over device pointers (the key of a line, the groups, the rows and the invariant: fmx_number_stats_by_batch
  * above), three stages on one stream; the caller reads stage b's m + 1 group offsets between b and c, as it reads G between
  * fmx_values_of_hits_dev and fmx_values_fill_dev.  Integers only, no atomics — the results do not depend on scheduling; lanes go to

@@ -718,6 +718,70 @@ public:
         return s;
     }
 
+    // the lines ranked by the number behind a pattern (fmx.h "THE LINES RANKED BY THE NUMBER BEHIND A PATTERN"; ... | sort -k latency
+    // -nr | head -10): numberStatsWhereBatch's patterns, queries, whereOf and fracDigits, and a window of lines.  descending[i] != 0:
+    // largest first.  A line counts with its best parsing hit (equal values: the smallest position); the candidates are ranked by
+    // value, equal values by line id; the ranks first .. first + top - 1 of pattern i are the rows i * top + j, j < rows[i]: line,
+    // value, loc (zero behind rows[i]).  lines = the lines that have a candidate, numbers = the kept hits that parse.  Needs
+    // buildLineTable().  Statuses are not thrown by the batch form; topLinesByNumber answers one pattern and throws them.
+    struct TopLines {
+        int32_t top = 0;
+        std::vector<int32_t> rows, line, loc;
+        std::vector<int64_t> value;
+        std::vector<int32_t> lines, numbers, notNumber, overflow, occurrences, kept, status, termStatus;
+    };
+    TopLines topLinesByNumberBatch(const std::vector<std::u16string> &patterns, const std::vector<Query> &queries,
+                                   const std::vector<int32_t> &whereOf, const std::vector<uint8_t> &descending, int32_t top = 10,
+                                   int32_t first = 0, int32_t fracDigits = 0, int32_t lineLo = 0, int32_t lineHi = INT32_MAX) const {
+        if (whereOf.size() != patterns.size() || descending.size() != patterns.size())
+            throw std::invalid_argument("whereOf and descending have one entry per pattern");
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        flattenQueries(queries, terms, kind, queryOff);
+        std::vector<uint16_t> chars, termChars;
+        std::vector<int32_t> off, termOff;
+        pack(patterns, chars, off);
+        pack(terms, termChars, termOff);
+        TopLines out;
+        out.top = top;
+        const size_t n = patterns.size(), cells = n * (size_t)(top > 0 ? top : 0);
+        out.line.assign(cells + 1, 0);
+        out.loc.assign(cells + 1, 0);
+        out.value.assign(cells + 1, 0);
+        for (std::vector<int32_t> *v : {&out.rows, &out.lines, &out.numbers, &out.notNumber, &out.overflow, &out.occurrences, &out.kept, &out.status})
+            v->assign(n + 1, 0);
+        out.termStatus.assign(terms.size(), 0);
+        detail::check(fmx_top_lines_where_batch(h_, chars.data(), off.data(), (int32_t)n, termChars.data(), termOff.data(), (int32_t)terms.size(),
+                                                queryOff.data(), kind.data(), (int32_t)queries.size(), whereOf.data(), lineLo, lineHi,
+                                                descending.data(), fracDigits, first, top, out.rows.data(), out.line.data(), out.value.data(),
+                                                out.loc.data(), out.lines.data(), out.numbers.data(), out.notNumber.data(), out.overflow.data(),
+                                                out.occurrences.data(), out.kept.data(), out.status.data(), out.termStatus.data()),
+                      "fmx_top_lines_where_batch");
+        for (std::vector<int32_t> *v : {&out.rows, &out.line, &out.loc, &out.lines, &out.numbers, &out.notNumber, &out.overflow, &out.occurrences,
+                                        &out.kept, &out.status})
+            v->pop_back();
+        out.value.pop_back();
+        return out;
+    }
+    // one pattern; the rows behind rows[0] are cut off
+    TopLines topLinesByNumber(const std::u16string &pattern, int32_t top = 10, bool largest = true, int32_t first = 0, const Query *where = nullptr,
+                              int32_t fracDigits = 0, int32_t lineLo = 0, int32_t lineHi = INT32_MAX) const {
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        if (where)
+            for (const std::vector<std::u16string> *g : {&where->all, &where->any, &where->none})
+                for (const std::u16string &t : *g)
+                    if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        TopLines s = topLinesByNumberBatch({pattern}, where ? std::vector<Query>{*where} : std::vector<Query>{}, {where ? 0 : -1},
+                                           {(uint8_t)(largest ? 1 : 0)}, top, first, fracDigits, lineLo, lineHi);
+        detail::raise_for_status(s.status[0]);
+        for (int st : s.termStatus) detail::raise_for_status(st);
+        s.line.resize((size_t)s.rows[0]);
+        s.loc.resize((size_t)s.rows[0]);
+        s.value.resize((size_t)s.rows[0]);
+        return s;
+    }
+
     // statistics of the number behind a pattern, GROUPED BY THE VALUE OF A FIELD of the same line (fmx.h "STATISTICS BY KEY"; stats
     // count, sum(bytes=), p95(latency_ms=) by status=): byOf[i] names the key pattern number pattern i is grouped by; the key of a
     // line is fieldValues' value (stop, maxLen) of the key pattern's first kept hit on it.  The groups of key pattern k are

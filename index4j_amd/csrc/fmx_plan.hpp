@@ -264,4 +264,27 @@ int launch_values_gather_rows(int n_cu, int32_t n, const int64_t *val_off, int32
                               const int64_t *text_off, const uint16_t *chars, int64_t *row_text_off, uint16_t *row_chars, void *ws,
                               size_t ws_bytes, void *stream);
 
+// fmx_hit_top.hip — packed hits of a batch of patterns -> the lines ranked by the number behind each hit (fmx_top_lines_of_hits_dev;
+// fmx_hit_top.hpp has the definition).  Compiled once; the grids are hit_lines_geometry's; the launchers return a hipError_t as int,
+// `stream` is a hipStream_t, nothing is synchronised or allocated.  term_len (n, none negative) and descending (n bytes) are HOST
+// arrays; they are copied into the workspace before launch_top_lines_windows returns.  The C-ABI layer runs three steps on one
+// stream over one workspace, as for the numbers stage:
+//   launch_top_lines_windows  window [s, e) and key pattern | position of every slot, into the regions top_lines_windows names;
+//   the packed extract        extract_windows (fmx_host_stage.hpp) over those n_hits ranges;
+//   launch_top_lines_rows     the parse, the sort by position, the lines, the reduction per (pattern, line), the two ranking sorts,
+//                             the per-pattern counters (rows is required, every other output nullable) and the rows of n x top;
+//                             status (nullable): a window the extract ran literally hands its status to its pattern.  T: the line
+//                             table (required).
+// hipErrorInvalidValue before anything is launched or written: too small a workspace, a shape outside
+// top_lines_of_hits_scratch_bytes' (which is 0 then: n <= 0, n_hits <= 0 or beyond 2^31 - 1, top < 1, n * top beyond 2^27).
+bool top_lines_shape_ok(int32_t n, int64_t n_hits, int32_t top);
+size_t top_lines_of_hits_scratch_bytes(int32_t n, int64_t n_hits, int32_t top);
+bool top_lines_windows(void *ws, size_t ws_bytes, int32_t n, int64_t n_hits, int32_t top, ValuesWindows *out);
+int launch_top_lines_windows(int32_t text_len, int n_cu, int32_t n, const int32_t *term_len, const uint8_t *descending, const int64_t *hit_off,
+                             const int32_t *locs, int64_t n_hits, int32_t top, void *ws, size_t ws_bytes, void *stream);
+int launch_top_lines_rows(const int32_t *T, int32_t count, int32_t text_len, int n_cu, int32_t n, const int64_t *hit_off, int64_t n_hits,
+                          int32_t frac_digits, int32_t first, int32_t top, int32_t *rows, int32_t *row_line, int64_t *row_value, int32_t *row_loc,
+                          int32_t *lines, int32_t *numbers, int32_t *not_number, int32_t *overflow, int32_t *status, void *ws, size_t ws_bytes,
+                          void *stream);
+
 }  // namespace fmx

@@ -178,6 +178,23 @@ class NumberStats:
         return np.array([s / c if c else float("nan") for s, c in zip(self.sum, self.count.tolist())], dtype=np.float64)
 
 
+class TopLines:
+    """pattern i of a top_lines_where_batch answer: line, value, loc — the rows[i] ranked rows as numpy arrays (int32, int64, int32) —
+    and lines (the lines that have a candidate), numbers, not_number, overflow, kept, occurrences as ints; text: the rows' lines
+    as a list of str where the call asked for it, else None"""
+
+    def __init__(self, out, i=0, text=None):
+        r = int(out["rows"][i])
+        self.line, self.value, self.loc = out["row_line"][i, :r].copy(), out["row_value"][i, :r].copy(), out["row_loc"][i, :r].copy()
+        self.lines, self.numbers = int(out["lines"][i]), int(out["numbers"][i])
+        self.not_number, self.overflow = int(out["not_number"][i]), int(out["overflow"][i])
+        self.occurrences, self.kept = int(out["occurrences"][i]), int(out["kept"][i])
+        self.text = text
+
+    def __len__(self):
+        return len(self.line)
+
+
 class NumberStatsBy:
     """number pattern i of a number_stats_by_batch answer, by its key pattern by_of[i]: groups = [dict(value, lines, count, sum, min, max,
     pct, mean)] — sum an exact Python int, mean a float (nan for a group without numbers) — in the order of the values, or with
@@ -846,6 +863,53 @@ class FmIndex:
                                         term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms, int(max_ranges)), n, n_terms,
                                        query_off, term_kind, where_of, edges, permille, frac_digits)
 
+    # ---- the lines ranked by the number behind a pattern (fmx.h "THE LINES RANKED BY THE NUMBER BEHIND A PATTERN") ----
+    def _top_lines_call(self, call, where, args, n, n_terms, query_off, term_kind, where_of, descending, top, first, lines, frac_digits):
+        query_off, term_kind, where_of, q, lo, hi = self._where_arrays(n, n_terms, query_off, term_kind, where_of, lines)
+        descending = np.ascontiguousarray(descending, dtype=np.uint8).reshape(-1)
+        if len(descending) != n:
+            raise ValueError("descending has %d entries for %d patterns" % (len(descending), n))
+        top = int(top)
+        cells = max(top, 0)
+        rows, n_lines, numbers, not_number, overflow, occurrences, kept, status = (np.zeros(n, dtype=np.int32) for _ in range(8))
+        row_line, row_loc = np.zeros((n, cells), dtype=np.int32), np.zeros((n, cells), dtype=np.int32)
+        row_value = np.zeros((n, cells), dtype=np.int64)
+        term_status = np.zeros(n_terms, dtype=np.int32)
+        check(call(self._h, *args, query_off.ctypes.data, term_kind.ctypes.data, q, where_of.ctypes.data, lo, hi, descending.ctypes.data,
+                   int(frac_digits), int(first), top, rows.ctypes.data, row_line.ctypes.data, row_value.ctypes.data, row_loc.ctypes.data,
+                   n_lines.ctypes.data, numbers.ctypes.data, not_number.ctypes.data, overflow.ctypes.data, occurrences.ctypes.data,
+                   kept.ctypes.data, status.ctypes.data, term_status.ctypes.data), where)
+        return dict(rows=rows, row_line=row_line, row_value=row_value, row_loc=row_loc, lines=n_lines, numbers=numbers, not_number=not_number,
+                    overflow=overflow, occurrences=occurrences, kept=kept, status=status, term_status=term_status)
+
+    def top_lines_where_batch(self, chars, offsets, term_chars, term_offsets, query_off, term_kind, where_of, descending, top=10, first=0,
+                              lines=None, frac_digits=0):
+        """the lines ranked by the number behind every pattern, only within the lines of a query and a window of lines
+        (fmx_top_lines_where_batch; ... | sort -k latency -nr | head -10): number_stats_where_batch's patterns, terms, query_off,
+        term_kind, where_of and frac_digits, field_values_where_batch's lines=(lo, hi).  descending[i] = 1: largest first, 0: smallest
+        first.  The candidate of a line is its best parsing hit (equal values: the smallest position); the candidates are ranked by
+        value, equal values by line id, and the ranks first .. first + top - 1 come down.  Returns a dict of arrays: rows (n);
+        row_line, row_loc (n, top) int32 and row_value (n, top) int64, zero behind rows[i]; lines, numbers, not_number, overflow,
+        occurrences, kept, status (n); term_status.  Needs build_line_table()."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        term_chars = np.ascontiguousarray(term_chars, dtype=np.uint16)
+        term_offsets = np.ascontiguousarray(term_offsets, dtype=np.int32)
+        n, n_terms = len(offsets) - 1, len(term_offsets) - 1
+        return self._top_lines_call(lib.fmx_top_lines_where_batch, "fmx_top_lines_where_batch",
+                                    (chars.ctypes.data, offsets.ctypes.data, n, term_chars.ctypes.data, term_offsets.ctypes.data, n_terms), n,
+                                    n_terms, query_off, term_kind, where_of, descending, top, first, lines, frac_digits)
+
+    def top_lines_where_class_batch(self, alt, pos_off, pat_off, term_alt, term_pos_off, term_pat_off, query_off, term_kind, where_of, descending,
+                                    top=10, first=0, lines=None, frac_digits=0, max_ranges=CLASS_RANGES_DEFAULT):
+        """top_lines_where_batch with class patterns as value patterns and as terms (fmx_top_lines_where_class_batch); same returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        term_alt, term_pos_off, term_pat_off, term_n_pos, n_terms = self._class_arrays(term_alt, term_pos_off, term_pat_off)
+        return self._top_lines_call(lib.fmx_top_lines_where_class_batch, "fmx_top_lines_where_class_batch",
+                                    (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, term_alt.ctypes.data,
+                                     term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms, int(max_ranges)), n, n_terms,
+                                    query_off, term_kind, where_of, descending, top, first, lines, frac_digits)
+
     # ---- ... grouped by the value of a field of the same line (fmx.h "STATISTICS BY KEY") ----
     def number_stats_by_batch(self, key_chars, key_offsets, chars, offsets, by_of, term_chars, term_offsets, query_off, term_kind, key_where_of,
                               where_of, stop, max_len, lines=None, permille=(500, 950), frac_digits=0):
@@ -1348,6 +1412,40 @@ class FmIndex:
         for st in [out["status"][0]] + out["term_status"].tolist():
             raise_for_status(st)
         return NumberStats(out, 0)
+
+    def top_lines_by_number(self, pattern, top=10, largest=True, first=0, where=None, lines=None, frac_digits=0, ignore_case=False, text=False):
+        """the `top` lines ranked by the number behind `pattern`, from rank `first` on: ... | sort -k latency -nr | head -10 — the ten
+        slowest requests, the largest blocks, with largest=False the smallest.  A line counts with its best number (two ids on one
+        line: the larger, or with largest=False the smaller; equal numbers: the first); equal numbers of two lines rank by line id.
+        where=dict(all=, any=, none=) and lines=(lo, hi) keep only the hits in the lines that match, as in field_values; frac_digits
+        as in number_stats.  Returns a TopLines: line, value, loc (arrays, best first) and lines, numbers, not_number, overflow,
+        kept, occurrences as ints; with text=True also text, the rows' lines as str (line_text_batch).  Needs build_line_table().
+        Only the rows come down."""
+        p = as_chars(pattern)
+        terms, kinds = [], []
+        for kind, word in enumerate(("all", "any", "none")):
+            group = (where or {}).get(word, ())
+            for t in ([group] if isinstance(group, str) else group):  # (a lone str is one term)
+                terms.append(as_chars(t))
+                kinds.append(kind)
+        if where is not None and set(where) - {"all", "any", "none"}:
+            raise ValueError("where takes all=, any= and none=")
+        if min((len(t) for t in terms + [p]), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        query_off, where_of = ([0, len(terms)], [0]) if where is not None else ([0], [-1])
+        if ignore_case:
+            out = self.top_lines_where_class_batch(*pack_class_patterns([_ignore_case(p)]), *pack_class_patterns([_ignore_case(t) for t in terms]),
+                                                   query_off, np.array(kinds, np.uint8), where_of, [1 if largest else 0], top, first, lines,
+                                                   frac_digits)
+        else:
+            out = self.top_lines_where_batch(*pack_patterns([p]), *pack_patterns(terms), query_off, np.array(kinds, np.uint8), where_of,
+                                             [1 if largest else 0], top, first, lines, frac_digits)
+        for st in [out["status"][0]] + out["term_status"].tolist():
+            raise_for_status(st)
+        res = TopLines(out, 0)
+        if text:
+            res.text = self.line_text(res.line)
+        return res
 
     def number_stats_by(self, pattern, by, stop=" \t\r\n", max_len=32, where=None, lines=None, permille=(500, 950), frac_digits=0, top=None,
                         ignore_case=False):

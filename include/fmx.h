@@ -570,6 +570,66 @@ int fmx_number_stats_by_class_batch(const fmx_index *idx, const uint16_t *key_al
                                     int32_t *kept, int32_t *status, int32_t *key_occurrences, int32_t *key_kept, int32_t *key_status,
                                     int32_t *term_status);
 
+/* STATISTICS BY KEY PER BUCKET: THE NUMBER BEHIND A PATTERN, BY THE VALUE OF A FIELD OF THE SAME LINE, PER BUCKET OF LINES (timechart
+ * p95(latency_ms=) by status=: the top few values, each with its statistics per bucket, plus "other") — the host form of stages a
+ * and b of STATISTICS BY KEY and fmx_numbers_by_key_buckets_dev (below).  The arguments are fmx_number_stats_by_batch's, word for
+ * word — the m key patterns, the n number patterns with by_of, the terms, query_off, term_kind, q, key_where_of, where_of, stop /
+ * n_stop / max_len, frac_digits, permille / n_permille — except that edges / n_edges (fmx_number_stats_where_batch's: edges == NULL
+ * with n_edges == 0 means B = 1, every line) stand in the place of line_lo / line_hi, and top in [1, 65536] is added.
+ * THE HITS OF THE CALL: with edges the filter's window of lines is [edges[0], edges[B]) for key hits and number hits alike, so
+ * every kept hit has a bucket.  The line table is always required (keys are per line).
+ * THE GROUPS of key pattern k are fmx_number_stats_by_batch's for that window: the distinct keys of its lines in
+ * fmx_field_values_batch's order, each with its lines; n_groups[k] = G_k (m ints, out, nullable).  The groups do not come down.
+ * THE KEY ROWS of k are its R_k = min(top, G_k) groups with the most lines, in descending order; equal lines stay in value order
+ * (the smaller group index first).  key_row_off (m + 1 int64, out, key_row_off[0] = 0) packs them.  Per key row r:
+ * (*key_row_lines)[r]; (*key_row_group)[r] = the group's index among the pattern's groups; (*text_off)[r] .. (*text_off)[r + 1] of
+ * *chars its code units (key_row_off[m] + 1 int64).
+ * THE CELLS of number pattern i with k = by_of[i] number (R_k + 1) * B, packed at cell_off[i] (n + 1 int64, out): cell (i, r, b) at
+ * cell_off[i] + r * B + b.  Rows r < R_k are over the kept hits of i that parse and whose line has the key of key row r of k; row
+ * r = R_k is "other": the key of the line is a group that is no key row.  Each cell holds (*count), (*sum_lo), (*sum_hi), (*min),
+ * (*max) and (*pct)[cell * P + j] exactly as fmx_number_stats_where_batch defines them; an empty cell is all zeros.
+ * Per number pattern no_key[i], not_number[i] and overflow[i] are fmx_number_stats_by_batch's (no_key is decided before parsing);
+ * occurrences, kept, status, key_occurrences, key_kept, key_status and term_status as there.  For every i
+ *     sum over the cells of i of count + no_key[i] + not_number[i] + overflow[i] = kept[i];
+ * with top >= G_k and no edges the rows of i, put back in key_row_group order, are fmx_number_stats_by_batch's rows and "other" is
+ * zero; with edges, a row's cells summed over b are that call's row for lines = [edges[0], edges[B]); for every (i, b) the cells'
+ * counts over all rows plus the hits of bucket b among no_key, not_number and overflow are fmx_hit_histogram_where_batch's counter.
+ * *key_row_lines, *key_row_group, *text_off, *chars, *count, *sum_lo, *sum_hi, *min, *max and *pct point into ONE allocation owned
+ * by the library until fmx_free_buffer((uint8_t *)*key_row_lines).  When no key pattern has a kept hit nothing beyond the filter
+ * runs, all of them are NULL, key_row_off and cell_off are zeroed and no_key[i] = kept[i]; when the number patterns have no kept
+ * hit the key rows are reported and every cell is zero.  n == 0, m == 0 with n > 0, an index without extraction, a handle that is
+ * not resident and the wrong kind of handle: as fmx_number_stats_by_batch.
+ * Only (top + 1) * B cells per number pattern and the text of top keys per key pattern come down, whatever G_k is.  The waits are
+ * fmx_number_stats_by_batch's (the kept offsets; the m + 1 group offsets with the size of the groups' text behind them) and the 8
+ * bytes of the key rows' packed text length.
+ * FMX_E_ARG, judged from the arguments alone and before any device work: everything fmx_number_stats_by_batch refuses, edges as
+ * fmx_number_stats_where_batch judges them, top outside [1, 65536], (int64) n * (top + 1) * B above 2^27 or that times max(P, 1)
+ * above 2^27.  A refused call stores nothing. */
+int fmx_number_stats_by_histogram_batch(const fmx_index *idx, const uint16_t *key_pat, const int32_t *key_off, int32_t m, const uint16_t *pat,
+                                        const int32_t *pat_off, int32_t n, const int32_t *by_of, const uint16_t *term_pat, const int32_t *term_off,
+                                        int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q, const int32_t *key_where_of,
+                                        const int32_t *where_of, const int32_t *edges, int32_t n_edges, int32_t top, const uint16_t *stop,
+                                        int32_t n_stop, int32_t max_len, int32_t frac_digits, const int32_t *permille, int32_t n_permille,
+                                        int32_t *n_groups, int64_t *key_row_off, int32_t **key_row_lines, int32_t **key_row_group, int64_t **text_off,
+                                        uint16_t **chars, int64_t *cell_off, int32_t **count, uint64_t **sum_lo, uint64_t **sum_hi, int64_t **min,
+                                        int64_t **max, int64_t **pct, int32_t *no_key, int32_t *not_number, int32_t *overflow, int32_t *occurrences,
+                                        int32_t *kept, int32_t *status, int32_t *key_occurrences, int32_t *key_kept, int32_t *key_status,
+                                        int32_t *term_status);
+/* ... with class patterns as key patterns, as number patterns and as terms, each batch as fmx_number_stats_by_class_batch takes its
+ * own.  The values and numbers behind ALL spellings of a pattern make one answer. */
+int fmx_number_stats_by_histogram_class_batch(const fmx_index *idx, const uint16_t *key_alt, const int32_t *key_pos_off, int32_t key_n_pos,
+                                              const int32_t *key_off, int32_t m, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos,
+                                              const int32_t *pat_off, int32_t n, const int32_t *by_of, const uint16_t *term_alt,
+                                              const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms,
+                                              int32_t max_ranges, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
+                                              const int32_t *key_where_of, const int32_t *where_of, const int32_t *edges, int32_t n_edges, int32_t top,
+                                              const uint16_t *stop, int32_t n_stop, int32_t max_len, int32_t frac_digits, const int32_t *permille,
+                                              int32_t n_permille, int32_t *n_groups, int64_t *key_row_off, int32_t **key_row_lines,
+                                              int32_t **key_row_group, int64_t **text_off, uint16_t **chars, int64_t *cell_off, int32_t **count,
+                                              uint64_t **sum_lo, uint64_t **sum_hi, int64_t **min, int64_t **max, int64_t **pct, int32_t *no_key,
+                                              int32_t *not_number, int32_t *overflow, int32_t *occurrences, int32_t *kept, int32_t *status,
+                                              int32_t *key_occurrences, int32_t *key_kept, int32_t *key_status, int32_t *term_status);
+
 /* TOP VALUES PER BUCKET: THE TOP VALUES OF A FIELD PER BUCKET OF LINES, the stacked timeline (count by status over time where line
  * has user=svc3: the ten most frequent values, each with its counts per bucket, plus "other") — the host forms of
  * fmx_values_of_hits_groups_dev, fmx_values_top_histogram_dev and fmx_values_gather_rows_dev (below: the stages).  The value
@@ -1092,6 +1152,49 @@ int fmx_numbers_by_key_dev(const fmx_index *idx, int32_t n, const int32_t *term_
                            int32_t n_permille, int64_t *d_row_off, int32_t *d_count, uint64_t *d_sum_lo, uint64_t *d_sum_hi, int64_t *d_min,
                            int64_t *d_max, int64_t *d_pct, int32_t *d_no_key, int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status,
                            void *d_ws, size_t ws_bytes, void *stream);
+/* STATISTICS BY KEY PER BUCKET over device pointers (the key rows, the cells and the invariants:
+ * fmx_number_stats_by_histogram_batch above): ONE stage on one stream behind stages a and b of STATISTICS BY KEY; the caller reads
+ * stage b's m + 1 group offsets in front of it.  Integers only, no atomics, no hashes — the results do not depend on scheduling;
+ * lanes go to groups, slots, cells or code units, never to patterns; the grids are fmx_hit_lines_geometry's and the extract honours
+ * `block` and `groups_per_cu`; asynchronous on `stream`, nothing is allocated, nothing is synchronised beyond the staged host copy
+ * of the small arrays (term_len, by_of, val_off, edges, permille: HOST arrays, validated, copied into d_ws before the call returns).
+ * Packed hits (d_hit_off, d_locs, n_hits) of n number patterns as fmx_numbers_by_key_dev takes them; d_first_off, d_first_lines:
+ * stage a's; d_group_of_first and d_group_lines (G = val_off[m] ints): stage b's d_group_of_hit and d_count over them.
+ * d_key_row_off (m + 1 int64), d_key_row_group and d_key_row_lines (R = the sum of min(top, G_k)), d_cell_off (n + 1 int64),
+ * d_count, d_sum_lo, d_sum_hi, d_min, d_max (d_cell_off[n] entries, = the sum over i of (R_by_of[i] + 1) * B), d_pct (that times P),
+ * d_no_key, d_not_number and d_overflow (n) get the answer; the cells' arrays are nullable except d_count; entries behind them keep
+ * the caller's values.  d_status as in fmx_numbers_of_hits_dev.
+ *   1. rank: a lane per group makes the key (key pattern << 31) | (INT32_MAX - lines), 31 + fm_bits(m) bits; ONE stable rocPRIM
+ *      radix sort carries the group's index; a lane per sorted group stores rank_of_group = min(sorted index - val_off[k], top) and,
+ *      below top, the key row's group and lines.  Stability is the tie rule.
+ *   2. codes: a lane per slot makes its window, finds its pattern (tiles of 1,024 slots, a slice of d_hit_off in LDS), its line
+ *      (4,096 fences in LDS), its bucket (up to 4,096 edges in LDS, more are searched in HBM; none: bucket 0) and takes ONE lower
+ *      bound in the first lines of its key pattern; the code is min(rank_of_group, R_k) * B + bucket, and with C = (min(top, max_k
+ *      G_k) + 1) * B the codes C = no key, C + 1 = not a number, C + 2 = overflow; 48 KiB of LDS per workgroup of 1,024 lanes.  A
+ *      hit whose line lies in no bucket has no cell and is counted with no_key: hand in hits of the edges' span only (the host form's
+ *      filter does).
+ *   3. the packed extract, the parse, the two stable sorts (value over 63 bits, then pattern | code) and the two running sums of
+ *      fmx_numbers_of_hits_dev, as they are.
+ *   4. cells: a lane per PACKED cell finds its pattern in the cell offsets and takes the two lower bounds, then reads count, min,
+ *      max, the 128-bit sum and the percentiles; a lane per number pattern stores the three counters.
+ * The text of the key rows is fmx_values_fill_dev and fmx_values_gather_rows_dev as they are, over (m, val_off, top, d_key_row_group).
+ * Workspace: fmx_numbers_by_key_scratch_bytes' per slot, 28 bytes per group, and rocPRIM's.  n == 0: nothing is written;
+ * n_hits == 0 or an index without extraction: the key rows and both offset arrays are stored, the cells and the counters are zeroed
+ * (without extraction every status is FMX_ST_NOT_ENABLED; the workspace is then sized for n_hits = 0).  FMX_E_ARG, before
+ * anything is launched or written: null or negative arguments, n_hits > 2^31 - 1, frac_digits outside [0, 9], n_permille outside
+ * [0, 16], a permille outside [0, 1000], a negative term_len, bad edges, top outside [1, 65536], (int64) n * (top + 1) * B above
+ * 2^27 or that times max(P, 1) above 2^27, m == 0 with n > 0, a by_of outside [0, m), a val_off that does not start at 0, decreases
+ * or holds more than 2^31 - 1 groups, a workspace smaller than fmx_numbers_by_key_buckets_scratch_bytes says (which is 0 for a
+ * shape the call refuses), an index without a line table, a SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE
+ * for a handle that is not resident. */
+size_t fmx_numbers_by_key_buckets_scratch_bytes(int32_t n, int32_t m, int64_t n_groups, int64_t n_hits, int32_t n_edges, int32_t n_permille);
+int fmx_numbers_by_key_buckets_dev(const fmx_index *idx, int32_t n, const int32_t *term_len, const int32_t *by_of, int32_t m, const int64_t *val_off,
+                                   int32_t top, const int32_t *edges, int32_t n_edges, const int64_t *d_hit_off, const int32_t *d_locs,
+                                   int64_t n_hits, const int64_t *d_first_off, const int32_t *d_first_lines, const int32_t *d_group_of_first,
+                                   const int32_t *d_group_lines, int32_t frac_digits, const int32_t *permille, int32_t n_permille,
+                                   int64_t *d_key_row_off, int32_t *d_key_row_group, int32_t *d_key_row_lines, int64_t *d_cell_off, int32_t *d_count,
+                                   uint64_t *d_sum_lo, uint64_t *d_sum_hi, int64_t *d_min, int64_t *d_max, int64_t *d_pct, int32_t *d_no_key,
+                                   int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status, void *d_ws, size_t ws_bytes, void *stream);
 /* TOP VALUES PER BUCKET over device pointers (the rows, `other` and the invariants: fmx_field_values_histogram_where_batch above),
  * two stages on one stream behind fmx_values_of_hits_groups_dev; the caller reads that stage's n + 1 group offsets in front of
  * them.  Integers only, no atomics, no hashes — the results do not depend on scheduling; lanes go to groups, slots, counters or code

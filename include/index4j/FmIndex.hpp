@@ -872,6 +872,103 @@ public:
         return s;
     }
 
+    // ... per bucket of lines (fmx.h "STATISTICS BY KEY PER BUCKET"; timechart p95(latency_ms=) by status=): numberStatsByBatch's
+    // patterns, keys, byOf, stop, maxLen, queries, keyWhereOf and whereOf, hitHistogramWhereBatch's edges — none at all: one bucket,
+    // every line, the device-side top-k of numberStatsBy; with edges only the hits inside edges[0] .. edges[B] count — and top.  The
+    // key rows of key pattern k are keyRowOff[k] .. keyRowOff[k + 1]: its min(top, nGroups[k]) groups with the most lines, descending,
+    // equal lines in value order; values[r], keyRowLines[r], keyRowGroup[r] (the key's index among the pattern's groups).  Number
+    // pattern i has (rows of byOf[i] + 1) * B cells at cellOff[i]: cell(i, r, b), the last row being every other key; count, the
+    // exact sum = sumHi * 2^64 + sumLo, min, max, pct[cell * P + j]; noKey / notNumber / overflow per number pattern.  Only the key
+    // rows and the cells come down.  Needs buildLineTable().  Statuses are not thrown by the batch form; numberStatsByHistogram
+    // answers one number pattern by one key pattern and throws them.
+    struct NumberStatsByHistogram {
+        int32_t buckets = 1, permilles = 0;
+        std::vector<int64_t> keyRowOff, cellOff;
+        std::vector<std::u16string> values;
+        std::vector<int32_t> keyRowLines, keyRowGroup, nGroups, count;
+        std::vector<uint64_t> sumLo, sumHi;
+        std::vector<int64_t> min, max, pct;
+        std::vector<int32_t> noKey, notNumber, overflow, occurrences, kept, status, keyOccurrences, keyKept, keyStatus, termStatus;
+        size_t cell(size_t i, size_t r, size_t b) const { return (size_t)cellOff[i] + r * (size_t)buckets + b; }
+    };
+    NumberStatsByHistogram numberStatsByHistogramBatch(const std::vector<std::u16string> &patterns, const std::vector<std::u16string> &keys,
+                                                       const std::vector<int32_t> &byOf, const std::u16string &stop, int32_t maxLen,
+                                                       const std::vector<Query> &queries, const std::vector<int32_t> &keyWhereOf,
+                                                       const std::vector<int32_t> &whereOf, const std::vector<int32_t> &edges = {}, int32_t top = 10,
+                                                       const std::vector<int32_t> &permille = {500, 950}, int32_t fracDigits = 0) const {
+        if (whereOf.size() != patterns.size() || byOf.size() != patterns.size()) throw std::invalid_argument("whereOf and byOf have one entry per pattern");
+        if (keyWhereOf.size() != keys.size()) throw std::invalid_argument("keyWhereOf has one entry per key pattern");
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        flattenQueries(queries, terms, kind, queryOff);
+        std::vector<uint16_t> chars, keyChars, termChars;
+        std::vector<int32_t> off, keyOff, termOff;
+        pack(patterns, chars, off);
+        pack(keys, keyChars, keyOff);
+        pack(terms, termChars, termOff);
+        NumberStatsByHistogram out;
+        const size_t n = patterns.size(), m = keys.size(), P = permille.size();
+        out.buckets = edges.empty() ? 1 : edges.size() > 1 ? (int32_t)edges.size() - 1 : 0;
+        out.permilles = (int32_t)P;
+        out.keyRowOff.assign(m + 1, 0);
+        out.cellOff.assign(n + 1, 0);
+        for (std::vector<int32_t> *v : {&out.noKey, &out.notNumber, &out.overflow, &out.occurrences, &out.kept, &out.status}) v->assign(n + 1, 0);
+        for (std::vector<int32_t> *v : {&out.nGroups, &out.keyOccurrences, &out.keyKept, &out.keyStatus}) v->assign(m + 1, 0);
+        out.termStatus.assign(terms.size(), 0);
+        int32_t *rowLines = nullptr, *rowGroup = nullptr, *count = nullptr;
+        int64_t *textOff = nullptr, *vmin = nullptr, *vmax = nullptr, *pct = nullptr;
+        uint64_t *sumLo = nullptr, *sumHi = nullptr;
+        uint16_t *text = nullptr;
+        detail::check(fmx_number_stats_by_histogram_batch(h_, keyChars.data(), keyOff.data(), (int32_t)m, chars.data(), off.data(), (int32_t)n,
+                                                          byOf.data(), termChars.data(), termOff.data(), (int32_t)terms.size(), queryOff.data(),
+                                                          kind.data(), (int32_t)queries.size(), keyWhereOf.data(), whereOf.data(),
+                                                          edges.empty() ? nullptr : edges.data(), (int32_t)edges.size(), top,
+                                                          reinterpret_cast<const uint16_t *>(stop.data()), (int32_t)stop.size(), maxLen, fracDigits,
+                                                          permille.data(), (int32_t)P, out.nGroups.data(), out.keyRowOff.data(), &rowLines, &rowGroup,
+                                                          &textOff, &text, out.cellOff.data(), &count, &sumLo, &sumHi, &vmin, &vmax, &pct,
+                                                          out.noKey.data(), out.notNumber.data(), out.overflow.data(), out.occurrences.data(),
+                                                          out.kept.data(), out.status.data(), out.keyOccurrences.data(), out.keyKept.data(),
+                                                          out.keyStatus.data(), out.termStatus.data()),
+                      "fmx_number_stats_by_histogram_batch");
+        const size_t R = (size_t)out.keyRowOff[m], cells = (size_t)out.cellOff[n];
+        if (rowLines) {  // the ONE allocation: copied, then handed back
+            out.keyRowLines.assign(rowLines, rowLines + R);
+            out.keyRowGroup.assign(rowGroup, rowGroup + R);
+            for (size_t r = 0; r < R; ++r)
+                out.values.emplace_back(reinterpret_cast<const char16_t *>(text) + textOff[r], (size_t)(textOff[r + 1] - textOff[r]));
+            out.count.assign(count, count + cells);
+            out.sumLo.assign(sumLo, sumLo + cells);
+            out.sumHi.assign(sumHi, sumHi + cells);
+            out.min.assign(vmin, vmin + cells);
+            out.max.assign(vmax, vmax + cells);
+            out.pct.assign(pct, pct + cells * P);
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(rowLines));
+        }
+        for (std::vector<int32_t> *v : {&out.noKey, &out.notNumber, &out.overflow, &out.occurrences, &out.kept, &out.status, &out.nGroups,
+                                        &out.keyOccurrences, &out.keyKept, &out.keyStatus})
+            v->pop_back();
+        return out;
+    }
+    NumberStatsByHistogram numberStatsByHistogram(const std::u16string &pattern, const std::u16string &by, const std::vector<int32_t> &edges = {},
+                                                  int32_t top = 10, const std::u16string &stop = u" \t\r\n", int32_t maxLen = 32,
+                                                  const Query *where = nullptr, const std::vector<int32_t> &permille = {500, 950},
+                                                  int32_t fracDigits = 0) const {
+        if (pattern.empty() || by.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        if (where)
+            for (const std::vector<std::u16string> *g : {&where->all, &where->any, &where->none})
+                for (const std::u16string &t : *g)
+                    if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const int32_t w = where ? 0 : -1;
+        const NumberStatsByHistogram s = numberStatsByHistogramBatch({pattern}, {by}, {0}, stop, maxLen,
+                                                                     where ? std::vector<Query>{*where} : std::vector<Query>{}, {w}, {w}, edges, top,
+                                                                     permille, fracDigits);
+        detail::raise_for_status(s.status[0]);
+        detail::raise_for_status(s.keyStatus[0]);
+        for (int st : s.termStatus) detail::raise_for_status(st);
+        return s;
+    }
+
     // the top values of a field per bucket of lines, the stacked timeline (fmx.h "TOP VALUES PER BUCKET"; count by status over time
     // where line has ...): fieldValuesWhereBatch's patterns, queries, whereOf, stop and maxLen, hitHistogramWhereBatch's edges — none
     // at all: one bucket, every line, the device-side top-k of fieldValues (no line table needed unless a pattern asks for a query);

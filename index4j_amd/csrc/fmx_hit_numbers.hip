@@ -391,6 +391,46 @@ int launch_numbers_rows(int n_cu, int32_t n, const int64_t *hit_off, int64_t n_h
     return 0;
 }
 
+// ---- the parse, the two sorts and the two running sums alone, over the arrays of a stage that makes the codes and reads the cells
+// itself (fmx_by_hist.hip): key_a / val_a leave sorted by (key, value), val_b and key_b hold the running sums of the values' halves --
+size_t numbers_sorted_tmp_bytes(int64_t n_hits) {
+    size_t sort = 0, scan = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, sort, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const uint64_t *)nullptr, (uint64_t *)nullptr,
+                                    (size_t)n_hits, 0u, 64u);
+    (void)rocprim::inclusive_scan(nullptr, scan, rocprim::make_transform_iterator((const uint64_t *)nullptr, LowHalf()), (uint64_t *)nullptr,
+                                  (size_t)n_hits, rocprim::plus<uint64_t>());
+    return pad256(std::max(sort, scan));
+}
+
+int launch_numbers_sorted(int n_cu, int32_t n, int64_t n_hits, int32_t B, int32_t frac_digits, const int64_t *win_off, const uint16_t *win,
+                          const int32_t *win_status, uint64_t *key_a, uint64_t *key_b, uint64_t *val_a, uint64_t *val_b, bool sums, int32_t *status,
+                          void *tmp, size_t tmp_bytes, void *stream) {
+    if (n <= 0 || n_hits <= 0 || n_hits > 0x7fffffff || B < 1 || frac_digits < 0 || frac_digits > kNumFracMax || !win_off || !win || !win_status ||
+        !key_a || !key_b || !val_a || !val_b || !tmp || tmp_bytes < numbers_sorted_tmp_bytes(n_hits))
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const int32_t code_bits = fm_num_code_bits(B);
+    const size_t H = (size_t)n_hits;
+    int32_t unused = 1, flat = 1;
+    hit_lines_geometry(n_hits, n_cu, &unused, &flat);
+#define FMX_NUM_CHECK(call) \
+    if (hipError_t e_ = (call); e_ != hipSuccess) return (int)e_
+    hipLaunchKernelGGL(k_num_parse, dim3((unsigned)flat), dim3(kFlatBlock), 0, st, win_off, win, win_status, n_hits, n, B, code_bits, frac_digits,
+                       key_a, val_a, status);
+    FMX_NUM_CHECK(hipGetLastError());
+    // the order (key, value): stable passes, the least significant first
+    FMX_NUM_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, val_a, val_b, key_a, key_b, H, 0u, 63u, st));
+    FMX_NUM_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, key_b, key_a, val_b, val_a, H, 0u, (unsigned)fm_num_key_width(n, B), st));
+    if (sums) {
+        FMX_NUM_CHECK(rocprim::inclusive_scan(tmp, tmp_bytes, rocprim::make_transform_iterator((const uint64_t *)val_a, LowHalf()), val_b, H,
+                                              rocprim::plus<uint64_t>(), st));
+        FMX_NUM_CHECK(rocprim::inclusive_scan(tmp, tmp_bytes, rocprim::make_transform_iterator((const uint64_t *)val_a, HighHalf()), key_b, H,
+                                              rocprim::plus<uint64_t>(), st));
+    }
+#undef FMX_NUM_CHECK
+    return 0;
+}
+
 // ---- grouped by the value of a field: num_ws without edges, and behind it the tables by_of (n ints) and row_off (n + 1 int64) -----
 namespace {
 struct ByWs {

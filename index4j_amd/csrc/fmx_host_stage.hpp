@@ -1,5 +1,5 @@
 // fmx_host_stage.hpp — the host-stage layer of the C ABI: what the feature files (fmx_class_api.cpp, fmx_where_api.cpp,
-// fmx_hist_api.cpp, fmx_stats_api.cpp, fmx_range_api.cpp, fmx_by_api.cpp, fmx_value_hist_api.cpp, fmx_top_api.cpp) see of a handle and of the packed host sequence of fmx_api.cpp, and what they share among
+// fmx_hist_api.cpp, fmx_stats_api.cpp, fmx_range_api.cpp, fmx_by_api.cpp, fmx_value_hist_api.cpp, fmx_top_api.cpp, fmx_by_hist_api.cpp) see of a handle and of the packed host sequence of fmx_api.cpp, and what they share among
 // themselves.  Host code only: no .hip file includes it.
 //   fmx_api.cpp          the views of a handle, extract_windows, check_query_arrays, values_between_call, hits_stage_call
 //   fmx_host_batch.cpp   the checks of a call's HOST arrays and the merge of terms and value patterns into ONE batch: no HIP

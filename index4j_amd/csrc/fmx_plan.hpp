@@ -264,6 +264,41 @@ int launch_values_gather_rows(int n_cu, int32_t n, const int64_t *val_off, int32
                               const int64_t *text_off, const uint16_t *chars, int64_t *row_text_off, uint16_t *row_chars, void *ws,
                               size_t ws_bytes, void *stream);
 
+// fmx_by_hist.hip — "STATS ... BY KEY" PER BUCKET OF LINES (fmx_numbers_by_key_buckets_dev; fmx_by_hist.hpp has the definition).
+// Compiled once; the grids are hit_lines_geometry's; the launchers return a hipError_t as int, `stream` is a hipStream_t, nothing is
+// synchronised or allocated.  term_len, by_of (n, each in [0, m)), val_off (m + 1: the key patterns' group offsets, stage b's answer
+// read by the caller, val_off[0] = 0), edges (n_edges >= 2 by fmx_line_hist.hpp's rules, or none at all: n_edges == 0, B = 1) and
+// permille are HOST arrays, judged again (fm_bh_shape_bad) and copied into the workspace before launch_by_hist_codes returns.  Three
+// steps on one stream over one workspace, as launch_numbers_by_key_ranges / extract_windows / launch_numbers_by_key_rows:
+//   launch_by_hist_codes   the rank of every group by its lines (group_lines: stage b's counts, G ints), the key rows
+//                          (key_row_off_out: m + 1, key_row_group and key_row_lines: R = the sum of min(top, G_k); cell_off_out:
+//                          n + 1; the two offset arrays nullable), then window [s, e) and key pattern | code of every slot, into the
+//                          regions numbers_by_key_buckets_windows names; n_hits == 0: the key rows alone;
+//   the packed extract     extract_windows (fmx_host_stage.hpp) over those n_hits ranges;
+//   launch_by_hist_cells   launch_numbers_sorted, the cells (count is required, every other output nullable) and the per-pattern
+//                          counters; status (nullable) as in launch_numbers_rows.  n_hits > 0.
+// hipErrorInvalidValue before anything is launched or written: too small a workspace, a shape outside the scratch-size function's
+// (which is 0 then), top outside [1, 65536], n * (top + 1) * B beyond 2^27 (or that times max(n_permille, 1)).
+// launch_numbers_sorted (fmx_hit_numbers.hip): that file's k_num_parse over the windows' text and the keys pattern | code in key_a
+// (codes in [0, B]; code_bits = fm_num_code_bits(B)), its two stable sorts (key_a / val_a leave sorted by (key, value)) and, with
+// `sums`, its two running sums of the values' halves (low in val_b, high in key_b); tmp: numbers_sorted_tmp_bytes(n_hits).
+size_t numbers_sorted_tmp_bytes(int64_t n_hits);
+int launch_numbers_sorted(int n_cu, int32_t n, int64_t n_hits, int32_t B, int32_t frac_digits, const int64_t *win_off, const uint16_t *win,
+                          const int32_t *win_status, uint64_t *key_a, uint64_t *key_b, uint64_t *val_a, uint64_t *val_b, bool sums, int32_t *status,
+                          void *tmp, size_t tmp_bytes, void *stream);
+size_t numbers_by_key_buckets_scratch_bytes(int32_t n, int32_t m, int64_t n_groups, int64_t n_hits, int32_t n_edges, int32_t n_permille);
+bool numbers_by_key_buckets_windows(void *ws, size_t ws_bytes, int32_t n, int32_t m, int64_t n_groups, int64_t n_hits, int32_t n_edges,
+                                    int32_t n_permille, ValuesWindows *out);
+int launch_by_hist_codes(const int32_t *T, int32_t count, int32_t text_len, int n_cu, int32_t n, const int32_t *term_len, const int32_t *by_of,
+                         int32_t m, const int64_t *val_off, int32_t top, const int32_t *edges, int32_t n_edges, const int64_t *hit_off,
+                         const int32_t *locs, int64_t n_hits, const int64_t *first_off, const int32_t *first_lines, const int32_t *group_of_first,
+                         const int32_t *group_lines, const int32_t *permille, int32_t n_permille, int64_t *key_row_off_out,
+                         int32_t *key_row_group, int32_t *key_row_lines, int64_t *cell_off_out, void *ws, size_t ws_bytes, void *stream);
+int launch_by_hist_cells(int n_cu, int32_t n, const int32_t *by_of, int32_t m, const int64_t *val_off, int32_t top, int32_t n_edges,
+                         const int64_t *hit_off, int64_t n_hits, int32_t frac_digits, int32_t n_permille, int32_t *count, uint64_t *sum_lo,
+                         uint64_t *sum_hi, int64_t *min, int64_t *max, int64_t *pct, int32_t *no_key, int32_t *not_number, int32_t *overflow,
+                         int32_t *status, void *ws, size_t ws_bytes, void *stream);
+
 // fmx_hit_top.hip — packed hits of a batch of patterns -> the lines ranked by the number behind each hit (fmx_top_lines_of_hits_dev;
 // fmx_hit_top.hpp has the definition).  Compiled once; the grids are hit_lines_geometry's; the launchers return a hipError_t as int,
 // `stream` is a hipStream_t, nothing is synchronised or allocated.  term_len (n, none negative) and descending (n bytes) are HOST

@@ -222,6 +222,39 @@ class NumberStatsBy:
         return {grp["value"]: grp for grp in self.groups}
 
 
+class NumberStatsByHistogram:
+    """number pattern i of a number_stats_by_histogram_batch answer, by its key pattern by_of[i]: rows = [dict(value, lines, group, count
+    (B), sum (B exact Python ints), min, max (B), pct (B, P))] — the key rows in descending order of lines, ties in value order; group
+    the key's index among the pattern's groups —, other: the same shape without value, lines and group, over the keys that are no
+    row; n_groups and the per-pattern counters as ints"""
+
+    def __init__(self, out, i=0):
+        k, B = int(out["by_of"][i]), int(out["buckets"])
+        text_off, chars = out["text_off"], out["chars"]
+        k_lo, k_hi, c_lo = int(out["key_row_off"][k]), int(out["key_row_off"][k + 1]), int(out["cell_off"][i])
+        cells = int(out["cell_off"][i + 1]) - c_lo  # ((rows + 1) * B, or none at all where no key pattern has a kept hit)
+
+        def cell_row(r):
+            a, b = c_lo + r * B, c_lo + (r + 1) * B
+            if cells == 0:
+                P = out["pct"].shape[1]
+                return dict(count=[0] * B, sum=[0] * B, min=[0] * B, max=[0] * B, pct=[[0] * P for _ in range(B)])
+            return dict(count=out["count"][a:b].tolist(), sum=[(int(hi) << 64) | int(lo) for lo, hi in zip(out["sum_lo"][a:b], out["sum_hi"][a:b])],
+                        min=out["min"][a:b].tolist(), max=out["max"][a:b].tolist(), pct=out["pct"][a:b].tolist())
+
+        self.rows = [dict(value=chars[text_off[r]:text_off[r + 1]].tobytes().decode("utf-16-le", "surrogatepass"), lines=int(out["key_row_lines"][r]),
+                          group=int(out["key_row_group"][r]), **cell_row(r - k_lo)) for r in range(k_lo, k_hi)]
+        self.other = cell_row(k_hi - k_lo)
+        self.n_groups = int(out["n_groups"][k])
+        self.no_key, self.not_number, self.overflow = int(out["no_key"][i]), int(out["not_number"][i]), int(out["overflow"][i])
+        self.occurrences, self.kept = int(out["occurrences"][i]), int(out["kept"][i])
+        self.key_occurrences, self.key_kept = int(out["key_occurrences"][k]), int(out["key_kept"][k])
+
+    def by_value(self):
+        """{value: row}"""
+        return {row["value"]: row for row in self.rows}
+
+
 class FieldValuesHistogram:
     """pattern i of a field_values_histogram_where_batch answer: rows = [dict(value, count, group, hist)] — the top values in descending
     order of count, ties in value order; group the value's index among the pattern's distinct values, hist its B counters as a list —
@@ -992,6 +1025,97 @@ class FmIndex:
                     min=vmin, max=vmax, pct=pct, no_key=no_key, not_number=not_number, overflow=overflow, occurrences=occurrences, kept=kept,
                     status=status, key_occurrences=key_occurrences, key_kept=key_kept, key_status=key_status, term_status=term_status)
 
+    # ---- ... by the value of a field of the same line, per bucket of lines (fmx.h "STATISTICS BY KEY PER BUCKET") ----
+    def number_stats_by_histogram_batch(self, key_chars, key_offsets, chars, offsets, by_of, term_chars, term_offsets, query_off, term_kind,
+                                        key_where_of, where_of, stop, max_len, edges=None, top=10, permille=(500, 950), frac_digits=0):
+        """statistics of the number behind every hit of the n number patterns, by the key of its line (number_stats_by_batch's patterns,
+        by_of, terms, query_off, term_kind, key_where_of, where_of, stop, max_len) and per bucket of lines (hit_histogram_where_batch's
+        edges; None: one bucket, every line — the device-side top-k of number_stats_by): timechart p95(latency_ms=) by status=
+        (fmx_number_stats_by_histogram_batch).  With edges only the hits inside edges[0] .. edges[B] count.  Needs build_line_table().
+        Returns a dict of arrays: n_groups (m), key_row_off (m + 1) — the key rows of key pattern k are its min(top, n_groups[k]) groups
+        with the most lines, descending, ties in value order —, key_row_lines, key_row_group (R), text_off (R + 1), chars; cell_off
+        (n + 1) — cell cell_off[i] + r * B + b is number pattern i, key row r of by_of[i] (the last row: every other key), bucket b —,
+        count, sum_lo, sum_hi, min, max (cells), pct (cells, P); no_key, not_number, overflow, occurrences, kept, status (n);
+        key_occurrences, key_kept, key_status (m); term_status; buckets (B).  Only the key rows and the cells come down."""
+        key_chars = np.ascontiguousarray(key_chars, dtype=np.uint16)
+        key_offsets = np.ascontiguousarray(key_offsets, dtype=np.int32)
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        term_chars = np.ascontiguousarray(term_chars, dtype=np.uint16)
+        term_offsets = np.ascontiguousarray(term_offsets, dtype=np.int32)
+        by_of = np.ascontiguousarray(by_of, dtype=np.int32)
+        m, n, n_terms = len(key_offsets) - 1, len(offsets) - 1, len(term_offsets) - 1
+        head = (key_chars.ctypes.data, key_offsets.ctypes.data, m, chars.ctypes.data, offsets.ctypes.data, n, by_of.ctypes.data, term_chars.ctypes.data,
+                term_offsets.ctypes.data, n_terms)
+        return self._number_stats_by_histogram_call(lib.fmx_number_stats_by_histogram_batch, "fmx_number_stats_by_histogram_batch", head, m, n, n_terms,
+                                                    by_of, query_off, term_kind, key_where_of, where_of, stop, max_len, edges, top, permille,
+                                                    frac_digits)
+
+    def number_stats_by_histogram_class_batch(self, key_alt, key_pos_off, key_pat_off, alt, pos_off, pat_off, by_of, term_alt, term_pos_off,
+                                              term_pat_off, query_off, term_kind, key_where_of, where_of, stop, max_len, edges=None, top=10,
+                                              permille=(500, 950), frac_digits=0, max_ranges=CLASS_RANGES_DEFAULT):
+        """number_stats_by_histogram_batch with class patterns as key patterns, as number patterns and as terms
+        (fmx_number_stats_by_histogram_class_batch): the keys and numbers behind ALL spellings of a pattern make one answer; same returns"""
+        key_alt, key_pos_off, key_pat_off, key_n_pos, m = self._class_arrays(key_alt, key_pos_off, key_pat_off)
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        term_alt, term_pos_off, term_pat_off, term_n_pos, n_terms = self._class_arrays(term_alt, term_pos_off, term_pat_off)
+        by_of = np.ascontiguousarray(by_of, dtype=np.int32)
+        head = (key_alt.ctypes.data, key_pos_off.ctypes.data, key_n_pos, key_pat_off.ctypes.data, m, alt.ctypes.data, pos_off.ctypes.data, n_pos,
+                pat_off.ctypes.data, n, by_of.ctypes.data, term_alt.ctypes.data, term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms,
+                int(max_ranges))
+        return self._number_stats_by_histogram_call(lib.fmx_number_stats_by_histogram_class_batch, "fmx_number_stats_by_histogram_class_batch", head,
+                                                    m, n, n_terms, by_of, query_off, term_kind, key_where_of, where_of, stop, max_len, edges, top,
+                                                    permille, frac_digits)
+
+    def _number_stats_by_histogram_call(self, call, name, head, m, n, n_terms, by_of, query_off, term_kind, key_where_of, where_of, stop, max_len,
+                                        edges, top, permille, frac_digits):
+        if len(by_of) != n:
+            raise ValueError("by_of has %d entries for %d patterns" % (len(by_of), n))
+        query_off, term_kind, where_of, q, _, _ = self._where_arrays(n, n_terms, query_off, term_kind, where_of, None)
+        key_where_of = np.ascontiguousarray(key_where_of, dtype=np.int32)
+        if len(key_where_of) != m:
+            raise ValueError("key_where_of has %d entries for %d key patterns" % (len(key_where_of), m))
+        if edges is None:
+            edges_ptr, n_edges, B = None, 0, 1
+        else:
+            edges, B = self._edges(edges)
+            edges_ptr, n_edges = edges.ctypes.data, len(edges)
+        stop = as_chars(stop)
+        permille = np.ascontiguousarray(permille, dtype=np.int32).reshape(-1)
+        P = len(permille)
+        n_groups = np.zeros(m, dtype=np.int32)
+        key_row_off, cell_off = np.zeros(m + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        no_key, not_number, overflow, occurrences, kept, status = (np.zeros(n, dtype=np.int32) for _ in range(6))
+        key_occurrences, key_kept, key_status = (np.zeros(m, dtype=np.int32) for _ in range(3))
+        term_status = np.zeros(n_terms, dtype=np.int32)
+        ptr = [C.c_void_p() for _ in range(10)]  # key_row_lines (the allocation), key_row_group, text_off, chars, count, sum_lo, sum_hi, min, max, pct
+        check(call(self._h, *head, query_off.ctypes.data, term_kind.ctypes.data, q, key_where_of.ctypes.data, where_of.ctypes.data, edges_ptr, n_edges,
+                   int(top), stop.ctypes.data, len(stop), int(max_len), int(frac_digits), permille.ctypes.data, P, n_groups.ctypes.data,
+                   key_row_off.ctypes.data, *(C.byref(x) for x in ptr[:4]), cell_off.ctypes.data, *(C.byref(x) for x in ptr[4:]), no_key.ctypes.data,
+                   not_number.ctypes.data, overflow.ctypes.data, occurrences.ctypes.data, kept.ctypes.data, status.ctypes.data,
+                   key_occurrences.ctypes.data, key_kept.ctypes.data, key_status.ctypes.data, term_status.ctypes.data), name)
+        R, cells = int(key_row_off[m]), int(cell_off[n])
+
+        def take(at, ctype, dtype, count):  # (the library's buffer is copied into arrays of NumPy's own)
+            if not at or count == 0:
+                return np.zeros(count, dtype)
+            return np.ctypeslib.as_array(C.cast(at, C.POINTER(ctype)), shape=(count,)).copy()
+
+        try:
+            key_row_lines, key_row_group = take(ptr[0], C.c_int32, np.int32, R), take(ptr[1], C.c_int32, np.int32, R)
+            text_off = take(ptr[2], C.c_int64, np.int64, R + 1) if ptr[0] else np.zeros(1, np.int64)
+            text = take(ptr[3], C.c_uint16, np.uint16, int(text_off[R]))
+            count = take(ptr[4], C.c_int32, np.int32, cells)
+            sum_lo, sum_hi = take(ptr[5], C.c_uint64, np.uint64, cells), take(ptr[6], C.c_uint64, np.uint64, cells)
+            vmin, vmax = take(ptr[7], C.c_int64, np.int64, cells), take(ptr[8], C.c_int64, np.int64, cells)
+            pct = take(ptr[9], C.c_int64, np.int64, cells * P).reshape(cells, P)
+        finally:
+            lib.fmx_free_buffer(ptr[0])
+        return dict(by_of=by_of.copy(), buckets=B, n_groups=n_groups, key_row_off=key_row_off, key_row_lines=key_row_lines, key_row_group=key_row_group,
+                    text_off=text_off, chars=text, cell_off=cell_off, count=count, sum_lo=sum_lo, sum_hi=sum_hi, min=vmin, max=vmax, pct=pct,
+                    no_key=no_key, not_number=not_number, overflow=overflow, occurrences=occurrences, kept=kept, status=status,
+                    key_occurrences=key_occurrences, key_kept=key_kept, key_status=key_status, term_status=term_status)
+
     # ---- the top values of a field per bucket of lines, the stacked timeline (fmx.h "TOP VALUES PER BUCKET") ----
     def _field_values_histogram_call(self, call, name, head, n, n_terms, query_off, term_kind, where_of, edges, top, stop, max_len):
         query_off, term_kind, where_of, q, _, _ = self._where_arrays(n, n_terms, query_off, term_kind, where_of, None)
@@ -1478,6 +1602,39 @@ class FmIndex:
         for st in [out["status"][0], out["key_status"][0]] + out["term_status"].tolist():
             raise_for_status(st)
         return NumberStatsBy(out, top)
+
+    def number_stats_by_histogram(self, pattern, by, edges=None, top=10, stop=" \t\r\n", max_len=32, where=None, permille=(500, 950), frac_digits=0,
+                                  ignore_case=False):
+        """statistics of the number behind `pattern` by the value behind `by` on the same line, per bucket of lines: timechart
+        p95(latency_ms=) by status= — the `top` keys with the most lines, each with its statistics per bucket, and the rest as
+        "other".  The key of a line as in number_stats_by; edges as in hit_histogram (None: one bucket, every line — the top-k of
+        number_stats_by, ranked on the device); where=dict(all=, any=, none=) filters the hits of both patterns as in field_values.
+        Returns a NumberStatsByHistogram: rows = [dict(value, lines, group, count (B), sum (B Python ints), min, max, pct (B, P))] in
+        descending order of lines, ties in value order, other in the same shape, and n_groups, no_key, not_number, overflow, kept,
+        occurrences.  Needs build_line_table().  Only the rows come down, however many distinct keys there are."""
+        p, k = as_chars(pattern), as_chars(by)
+        terms, kinds = [], []
+        for kind, word in enumerate(("all", "any", "none")):
+            group = (where or {}).get(word, ())
+            for t in ([group] if isinstance(group, str) else group):  # (a lone str is one term)
+                terms.append(as_chars(t))
+                kinds.append(kind)
+        if where is not None and set(where) - {"all", "any", "none"}:
+            raise ValueError("where takes all=, any= and none=")
+        if min((len(t) for t in terms + [p, k]), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        query_off, where_of = ([0, len(terms)], [0]) if where is not None else ([0], [-1])
+        if ignore_case:
+            out = self.number_stats_by_histogram_class_batch(*pack_class_patterns([_ignore_case(k)]), *pack_class_patterns([_ignore_case(p)]), [0],
+                                                             *pack_class_patterns([_ignore_case(t) for t in terms]), query_off,
+                                                             np.array(kinds, np.uint8), where_of, where_of, stop, max_len, edges, top, permille,
+                                                             frac_digits)
+        else:
+            out = self.number_stats_by_histogram_batch(*pack_patterns([k]), *pack_patterns([p]), [0], *pack_patterns(terms), query_off,
+                                                       np.array(kinds, np.uint8), where_of, where_of, stop, max_len, edges, top, permille, frac_digits)
+        for st in [out["status"][0], out["key_status"][0]] + out["term_status"].tolist():
+            raise_for_status(st)
+        return NumberStatsByHistogram(out, 0)
 
     def field_values_histogram(self, pattern, edges=None, top=10, where=None, stop=" ", max_len=64, ignore_case=False):
         """the `top` most frequent values that follow `pattern`, each with its occurrences per bucket of lines, and the rest as

@@ -1,8 +1,10 @@
-// fmx_host_batch.cpp — the HOST arrays of the where, histogram and stats forms (fmx_host_stage.hpp): their checks, and the merge of
-// the filter terms and the value patterns into ONE batch, literal and class.  Plain C++: no HIP runtime call and nothing of a
-// handle, so that the CPU suite links this file alone, under sanitizers (tests/cpp/san_merged_batch.cpp).
+// fmx_host_batch.cpp — the HOST arrays of the where, histogram, stats, top and keyed forms (fmx_host_stage.hpp): their checks — the
+// offsets, where_of and the window of lines, by_of, the edges, the shape of the values and of the numbers, term_len, the limits of
+// the hits — and the merge of the filter terms and the value patterns into ONE batch, literal and class, with the key patterns
+// between them for the keyed forms.  Plain C++: no HIP runtime call and nothing of a handle, so that the CPU suite links this file
+// alone, under sanitizers (tests/cpp/san_merged_batch.cpp).
+#include "fmx_hit_numbers.hpp"
 #include "fmx_host_stage.hpp"
-#include "fmx_line_hist.hpp"
 
 namespace fmx {
 
@@ -75,6 +77,41 @@ int merge_class_batch(const uint16_t *alt, const int32_t *pos_off, int32_t n_pos
     return FMX_OK;
 }
 
+// the m + n lengths of the keys and the numbers from the offsets of their batch
+static void lengths_of(const std::vector<int32_t> &off, std::vector<int32_t> *len) {
+    len->clear();
+    for (size_t i = 0; i + 1 < off.size(); ++i) len->push_back(off[i + 1] - off[i]);
+}
+
+// ... the keys take the terms' slot of the first merge, the numbers lie behind them; then the terms in front
+int merge_keyed_literal_batch(const uint16_t *key_pat, const int32_t *key_off, int32_t m, const uint16_t *pat, const int32_t *pat_off, int32_t n,
+                              const uint16_t *term_pat, const int32_t *term_off, int32_t n_terms, MergedBatch *merged, ValuesBatch *batch,
+                              std::vector<int32_t> *term_len) {
+    MergedBatch both;
+    ValuesBatch both_batch;
+    int rc;
+    if ((rc = merge_literal_batch(pat, pat_off, n, key_pat, key_off, m, &both, &both_batch)) ||
+        (rc = merge_literal_batch(both.chars.data(), both.off.data(), m + n, term_pat, term_off, n_terms, merged, batch)))
+        return rc;
+    lengths_of(both.off, term_len);
+    return FMX_OK;
+}
+
+int merge_keyed_class_batch(const uint16_t *key_alt, const int32_t *key_pos_off, int32_t key_n_pos, const int32_t *key_off, int32_t m,
+                            const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
+                            const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges,
+                            MergedBatch *merged, ValuesBatch *batch, std::vector<int32_t> *term_len) {
+    MergedBatch both;
+    ValuesBatch both_batch;
+    int rc;
+    if ((rc = merge_class_batch(alt, pos_off, n_pos, pat_off, n, key_alt, key_pos_off, key_n_pos, key_off, m, max_ranges, &both, &both_batch)) ||
+        (rc = merge_class_batch(both.chars.data(), both.pos.data(), both_batch.n_pos, both.off.data(), m + n, term_alt, term_pos_off, term_n_pos,
+                                term_off, n_terms, max_ranges, merged, batch)))
+        return rc;
+    lengths_of(both.off, term_len);  // (a position is a character)
+    return FMX_OK;
+}
+
 bool hits_filter_asked(int32_t n, const int32_t *where_of, int32_t line_lo, int32_t line_hi) {
     if (line_lo != 0 || line_hi != INT32_MAX) return true;
     for (int32_t i = 0; i < n; ++i)
@@ -86,6 +123,39 @@ int check_where_of(int32_t n, const int32_t *where_of, int32_t q) {
     for (int32_t i = 0; i < n; ++i)
         if (where_of[i] < -1 || where_of[i] >= q) return api_fail(FMX_E_ARG, "where_of[" + std::to_string(i) + "] is outside -1 .. q - 1");
     return FMX_OK;
+}
+
+int check_where(int32_t n, const int32_t *where_of, int32_t q, int32_t line_lo, int32_t line_hi) {
+    if (n < 0 || q < 0 || line_lo < 0 || line_hi < 0 || (n > 0 && !where_of)) return api_fail(FMX_E_ARG, "bad arguments");
+    if (line_lo > line_hi) return api_fail(FMX_E_ARG, "the window of lines ends in front of its start");
+    return check_where_of(n, where_of, q);
+}
+
+int check_values_shape(const uint16_t *stop, int32_t n_stop, int32_t max_len) {
+    if (max_len < 1 || max_len > kValuesMaxLen) return api_fail(FMX_E_ARG, "max_len is outside [1, 64]");
+    if (n_stop < 0 || n_stop > kValuesMaxStop || (n_stop > 0 && !stop)) return api_fail(FMX_E_ARG, "the stop set is outside [0, 64] code units");
+    return FMX_OK;
+}
+
+int check_values_hits(int64_t n_hits, int32_t max_len) {
+    if (n_hits > 0x7fffffff) return api_fail(FMX_E_ARG, "more than 2^31 - 1 hits in one call");
+    if (n_hits * max_len > kValuesMaxUnits) return api_fail(FMX_E_ARG, "the windows of the hits hold more than 2^35 code units");
+    return FMX_OK;
+}
+
+int check_term_len(int32_t n, const int32_t *term_len) {
+    for (int32_t i = 0; i < n; ++i)
+        if (term_len[i] < 0) return api_fail(FMX_E_ARG, "term_len[" + std::to_string(i) + "] is negative");
+    return FMX_OK;
+}
+
+int check_numbers_shape(int32_t frac_digits, const int32_t *permille, int32_t n_permille) {
+    if (frac_digits < 0 || frac_digits > kNumFracMax) return api_fail(FMX_E_ARG, "frac_digits is outside [0, 9]");
+    switch (fm_num_permille_bad(permille, n_permille)) {
+        case 0: return FMX_OK;
+        case 1: return api_fail(FMX_E_ARG, "n_permille is outside [0, 16]");
+        default: return api_fail(FMX_E_ARG, "a permille is outside [0, 1000]");
+    }
 }
 
 int check_by_of(int32_t n, const int32_t *by_of, int32_t m) {

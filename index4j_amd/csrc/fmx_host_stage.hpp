@@ -1,11 +1,15 @@
 // fmx_host_stage.hpp — the host-stage layer of the C ABI: what the feature files (fmx_class_api.cpp, fmx_where_api.cpp,
-// fmx_hist_api.cpp, fmx_stats_api.cpp, fmx_range_api.cpp, fmx_by_api.cpp, fmx_value_hist_api.cpp, fmx_top_api.cpp, fmx_by_hist_api.cpp) see of a handle and of the packed host sequence of fmx_api.cpp, and what they share among
-// themselves.  Host code only: no .hip file includes it.
+// fmx_hist_api.cpp, fmx_stats_api.cpp, fmx_range_api.cpp, fmx_by_api.cpp, fmx_value_hist_api.cpp, fmx_top_api.cpp,
+// fmx_by_hist_api.cpp) see of a handle and of the packed host sequence of fmx_api.cpp, and what they share among themselves, each
+// piece defined ONCE.  Host code only: no .hip file includes it.
 //   fmx_api.cpp          the views of a handle, extract_windows, check_query_arrays, values_between_call, hits_stage_call
-//   fmx_host_batch.cpp   the checks of a call's HOST arrays and the merge of terms and value patterns into ONE batch: no HIP
-//                        runtime call, so that the CPU suite links it as plain C++ (tests/cpp/san_merged_batch.cpp)
+//   fmx_host_batch.cpp   the checks of a call's HOST arrays (offsets, where_of, by_of, edges, the values' and the numbers' shape,
+//                        term_len, the limits of the hits) and the merges into ONE batch, terms | value patterns and terms | key
+//                        patterns | number patterns: no HIP runtime call, so that the CPU suite links it as plain C++
+//                        (tests/cpp/san_merged_batch.cpp)
 //   fmx_host_stage.cpp   the stages on the device: the number filter over the terms' hits, the lines of the queries, the filter
-//                        over the value patterns' hits
+//                        over the value patterns' hits, the groups of hits; the statistics arrays and the packed result of a
+//                        stage; the keyed forms' call plumbing and their front half, from the filter to the group offsets
 // Every function that returns int returns an FMX_* code (fmx::api_fail has set the message).
 #pragma once
 
@@ -13,6 +17,8 @@
 #include "fmx_plan.hpp"
 
 #include <climits>
+#include <cstdlib>
+#include <initializer_list>
 #include <vector>
 
 namespace fmx {
@@ -101,6 +107,16 @@ int merge_literal_batch(const uint16_t *pat, const int32_t *pat_off, int32_t n, 
 int merge_class_batch(const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
                       const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges,
                       MergedBatch *m, ValuesBatch *batch);
+// the same with m key patterns and n number patterns for value patterns: ONE batch terms | keys | numbers (to values_between_call /
+// hits_stage_call the last two are m + n value patterns) and *term_len, the m + n lengths of the keys and the numbers (a position of
+// a class pattern is a character).  The two merges above, one behind the other, and their refusals.
+int merge_keyed_literal_batch(const uint16_t *key_pat, const int32_t *key_off, int32_t m, const uint16_t *pat, const int32_t *pat_off, int32_t n,
+                              const uint16_t *term_pat, const int32_t *term_off, int32_t n_terms, MergedBatch *merged, ValuesBatch *batch,
+                              std::vector<int32_t> *term_len);
+int merge_keyed_class_batch(const uint16_t *key_alt, const int32_t *key_pos_off, int32_t key_n_pos, const int32_t *key_off, int32_t m,
+                            const uint16_t *alt, const int32_t *pos_off, int32_t n_pos, const int32_t *pat_off, int32_t n, const uint16_t *term_alt,
+                            const int32_t *term_pos_off, int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges,
+                            MergedBatch *merged, ValuesBatch *batch, std::vector<int32_t> *term_len);
 // the number filter over the TERMS' hits (fmx_hit_range.hpp: term t is ranged iff num_lo[t] >= 0); the default is "none"
 struct NumberTerms {
     const int64_t *num_lo = nullptr, *num_hi = nullptr;  // n_terms each (host)
@@ -129,6 +145,15 @@ struct HitsFilter {
 // the call filters at all: a pattern asks for a query, or the window is not 0 .. INT32_MAX
 bool hits_filter_asked(int32_t n, const int32_t *where_of, int32_t line_lo = 0, int32_t line_hi = INT32_MAX);
 int check_where_of(int32_t n, const int32_t *where_of, int32_t q);
+// where_of and the window of lines 0 <= line_lo <= line_hi of a call that takes one
+int check_where(int32_t n, const int32_t *where_of, int32_t q, int32_t line_lo, int32_t line_hi);
+// the values stages' shape (fmx_hit_values.hpp): max_len in [1, 64], a stop set of [0, 64] code units
+int check_values_shape(const uint16_t *stop, int32_t n_stop, int32_t max_len);
+// their limits: at most 2^31 - 1 hits in one call and 2^35 code units in the hits' windows
+int check_values_hits(int64_t n_hits, int32_t max_len);
+int check_term_len(int32_t n, const int32_t *term_len);  // none negative
+// the numbers stages' shape (fmx_hit_numbers.hpp): frac_digits in [0, 9], at most 16 permilles, each in [0, 1000]
+int check_numbers_shape(int32_t frac_digits, const int32_t *permille, int32_t n_permille);
 // by_of (n entries, each 0 .. m - 1): the key pattern each number pattern is grouped by (fmx_number_stats_by_batch); n > 0 needs m > 0
 int check_by_of(int32_t n, const int32_t *by_of, int32_t m);
 // edges by fmx_line_hist.hpp's rules (n_edges >= 2, edges[0] >= 0, never decreasing)
@@ -171,5 +196,106 @@ int hits_in_lines_stage(const HitsBetween &h, const HitsFilter &f, int64_t *kept
 // the same for a stage that reads the hits where they lie: (*d_off: n + 1, *d_locs, *n_hits slots) — the packed block's own part
 // when the call does not filter, else what hits_in_lines_stage keeps, in blocks from block()
 int kept_hits_stage(const HitsBetween &h, const HitsFilter &f, const int64_t **d_off, const int32_t **d_locs, int64_t *n_hits);
+
+// ---- fmx_host_stage.cpp: what the stages of the feature files share ----------------------------------------------------------------
+int hip_fail(const char *what, int e);  // FMX_E_HIP, "<what>: <the text of HIP error e>"
+// the value patterns' statuses of a stage (h.status, h.n; nullable) = value, asynchronously
+int status_all(const HitsBetween &h, int32_t value, const char *what);
+// stage b of the keyed forms and fmx_values_of_hits_groups_dev behind its checks: the windows, their text, the groups and the group
+// of every hit (n > 0, n_hits > 0, an index with extraction)
+int values_groups_run(const ::fmx_index *idx, const LineView &view, const TextView &text, int32_t n, const int32_t *term_len, const uint16_t *stop,
+                      int32_t n_stop, int32_t max_len, const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, int64_t *d_val_off,
+                      int32_t *d_count, int64_t *d_text_off, int32_t *d_group_of_hit, int32_t *d_status, void *ws, size_t ws_bytes, void *stream);
+// the statistics arrays of the numbers stages, on the device or on the host: `cells` rows (pct: cells * P) and n counters per
+// pattern; an array that is not wanted is nullptr
+struct StatRows {
+    int32_t *count;
+    uint64_t *sum_lo, *sum_hi;
+    int64_t *min, *max, *pct;
+    int32_t *no_key, *not_number, *overflow;
+};
+// *d: device blocks from h.block for the arrays `wanted` has (nullptr: every one); pct only where P > 0
+int stat_rows_blocks(const HitsBetween &h, const StatRows *wanted, size_t cells, size_t P, int32_t n, StatRows *d);
+// the arrays `host` has, copied down asynchronously; the arrays `d` has, zeroed asynchronously
+int stat_rows_down(const StatRows &host, const StatRows &d, size_t cells, size_t P, int32_t n, void *stream);
+int stat_rows_zero(const StatRows &d, size_t cells, size_t P, int32_t n, void *stream);
+// the ONE zeroed allocation of a host form's answer: region i holds bytes[i], each region at a multiple of 8, 8 spare bytes behind
+// the last.  The caller owns it (fmx_free_buffer on region 0) once release() has run.
+struct PackedResult {
+    uint8_t *p = nullptr;
+    std::vector<size_t> at;
+    ~PackedResult() { free(p); }
+    bool alloc(std::initializer_list<size_t> bytes);
+    template <class T>
+    T *region(size_t i) const { return reinterpret_cast<T *>(p + at[i]); }
+    void release() { p = nullptr; }
+};
+
+// ---- fmx_host_stage.cpp: the keyed forms (statistics by key, and by key per bucket) ---------------------------------------------------
+// what their host forms take besides their patterns and what they hand back per pattern (each output nullable) ...
+struct KeyedCall {
+    int32_t m, n;
+    const int32_t *by_of;
+    int32_t n_terms;
+    const int32_t *query_off;
+    const uint8_t *term_kind;
+    int32_t q;
+    const int32_t *key_where_of, *where_of;
+    const uint16_t *stop;
+    int32_t n_stop, max_len, frac_digits;
+    const int32_t *permille;
+    int32_t n_permille;
+    int64_t **text_off;  // these eight point into the ONE allocation of the answer
+    uint16_t **chars;
+    int32_t **count;
+    uint64_t **sum_lo, **sum_hi;
+    int64_t **min, **max, **pct;
+    int32_t *no_key, *not_number, *overflow, *occurrences, *kept, *status, *key_occurrences, *key_kept, *key_status, *term_status;
+};
+void keyed_null_results(const KeyedCall &c);     // the eight that are there = NULL
+bool keyed_results_missing(const KeyedCall &c);  // one of the eight is not there
+// ... and what their stage needs of that, and leaves on the host (arrived when the call has synchronised)
+struct KeyedArgs {
+    int32_t m = 0, n = 0;
+    const int32_t *by_of = nullptr;
+    HitsFilter filter{};
+    std::vector<int32_t> where_all, term_len;  // m + n each: the key patterns', then the number patterns'
+    const uint16_t *stop = nullptr;
+    int32_t n_stop = 0, max_len = 0, frac_digits = 0;
+    const int32_t *permille = nullptr;
+    int32_t P = 0;
+    TextView text{};
+    std::vector<int64_t> kept_off, val_off;             // m + n + 1; m + 2: the group offsets, the units of the groups' text behind
+    std::vector<int64_t> part_off;                      // the key part's and the number part's own offsets (copied to the device)
+    std::vector<int32_t> no_key, not_number, overflow;  // n each
+    PackedResult result;
+};
+// the checks of the HOST arrays the forms share (behind their own batches'); the handle's views (keys are per line: no line table
+// is a refusal); *a from c with the window of the filter — false: n == 0, nothing is searched and the call is answered
+int keyed_call_checks(const KeyedCall &c);
+int keyed_call_views(const ::fmx_index *idx, TextView *text);
+bool keyed_call_fill(const KeyedCall &c, int32_t line_lo, int32_t line_hi, KeyedArgs *a);
+// the call over the merged batch terms | keys | numbers with `stage` (its argument: arg), then the per-pattern outputs of c
+int keyed_call_run(const ::fmx_index *idx, const KeyedCall &c, const ValuesBatch &batch, ValuesBetweenFn stage, void *arg, const KeyedArgs &a);
+// the host side of the statistics for stat_rows_down: count .. pct are regions first .. first + 5 of a.result, the counters a's
+StatRows keyed_host_rows(KeyedArgs &a, size_t first);
+// the caller's eight pointers: text_off, chars, count .. pct are regions first .. first + 7; the allocation is the caller's now
+void keyed_hand_over(const KeyedCall &c, KeyedArgs &a, size_t first);
+// the front half of their stages: the filter (kept_hits_stage), ONE read of the kept offsets, the two parts of the kept block with
+// offsets of their own, stage a (the first hit of every line) over the keys' part, stage b (values_groups_run) over the first hits,
+// ONE read of the m + 1 group offsets with the units of the groups' text behind them.  It leaves a.kept_off, a.val_off, K and N,
+// and the device arrays below (blocks of h.block).  *done: answered, nothing more to run — no key or number hit, an index without
+// extraction (FMX_ST_NOT_ENABLED), or K == 0: every kept number hit is a.no_key.
+struct KeyedFront {
+    int64_t K, N;                                      // the kept key hits, the kept number hits
+    const int64_t *key_off, *num_off;                  // m + 1, n + 1: the parts' own offsets, from 0
+    const int32_t *key_locs, *num_locs;
+    int64_t *first_off;                                // m + 1
+    int32_t *first_lines, *first_locs, *lines, *group;  // K slots each: stage a's lines and hits, stage b's count and group of hit
+    int64_t *text_off;                                 // K + 1
+    void *ws_b;                                        // stage b's workspace: launch_values_fill reads it
+    size_t b_bytes;
+};
+int keyed_front_stage(const HitsBetween &h, KeyedArgs &a, const char *what, KeyedFront *f, bool *done);
 
 }  // namespace fmx

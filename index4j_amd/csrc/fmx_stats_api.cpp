@@ -15,6 +15,7 @@ namespace {
 
 using fmx::api_fail;
 using fmx::guarded;
+using fmx::hip_fail;
 using fmx::no_line_table;
 using fmx::zero;
 
@@ -27,14 +28,9 @@ struct Shape {
     size_t cells(int32_t n) const { return (size_t)n * (size_t)B; }
 };
 int check_shape(int32_t n, const int32_t *edges, int32_t n_edges, int32_t frac_digits, const int32_t *permille, int32_t n_permille, Shape *s) {
-    if (frac_digits < 0 || frac_digits > fmx::kNumFracMax) return api_fail(FMX_E_ARG, "frac_digits is outside [0, 9]");
-    switch (fmx::fm_num_permille_bad(permille, n_permille)) {
-        case 0: break;
-        case 1: return api_fail(FMX_E_ARG, "n_permille is outside [0, 16]");
-        default: return api_fail(FMX_E_ARG, "a permille is outside [0, 1000]");
-    }
-    if (edges || n_edges != 0)
-        if (const int rc = fmx::check_edges_array(edges, n_edges)) return rc;
+    int rc;
+    if ((rc = fmx::check_numbers_shape(frac_digits, permille, n_permille)) || ((edges || n_edges != 0) && (rc = fmx::check_edges_array(edges, n_edges))))
+        return rc;
     *s = Shape{edges, n_edges, edges ? n_edges - 1 : 1, frac_digits, permille, n_permille};
     const int64_t cells = (int64_t)n * s->B;
     if (cells > fmx::kHistCellsMax) return api_fail(FMX_E_ARG, "more than 2^27 rows in one call (patterns * buckets)");
@@ -43,25 +39,8 @@ int check_shape(int32_t n, const int32_t *edges, int32_t n_edges, int32_t frac_d
     return FMX_OK;
 }
 
-// the outputs of the stage, on the device or on the host: count is required, every other one nullable
-struct Rows {
-    int32_t *count;
-    uint64_t *sum_lo, *sum_hi;
-    int64_t *min, *max, *pct;
-    int32_t *not_number, *overflow;
-};
-
-// rows and per-pattern counters of the device, all zero
-int zero_rows(const Rows &r, int32_t n, const Shape &s, hipStream_t st) {
-    const size_t cells = s.cells(n);
-    if (cells > 0) FMX_HIP_TRY(hipMemsetAsync(r.count, 0, cells * 4, st));
-    for (void *p : {(void *)r.sum_lo, (void *)r.sum_hi, (void *)r.min, (void *)r.max})
-        if (p && cells > 0) FMX_HIP_TRY(hipMemsetAsync(p, 0, cells * 8, st));
-    if (r.pct && cells * (size_t)s.P > 0) FMX_HIP_TRY(hipMemsetAsync(r.pct, 0, cells * (size_t)s.P * 8, st));
-    for (int32_t *p : {r.not_number, r.overflow})
-        if (p && n > 0) FMX_HIP_TRY(hipMemsetAsync(p, 0, (size_t)n * 4, st));
-    return FMX_OK;
-}
+// the outputs of the stage, on the device or on the host: count is required, every other one nullable, no_key is never there
+using Rows = fmx::StatRows;
 
 // the three steps behind the arguments' checks (n > 0, n_hits > 0, the workspace large enough): the windows and keys, the windows'
 // text, the rows.  An index without extraction: zero rows, FMX_ST_NOT_ENABLED for every pattern.
@@ -69,28 +48,20 @@ int numbers_impl(const fmx_index *idx, const fmx::LineView &view, const fmx::Tex
                  const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, const Shape &s, const Rows &r, int32_t *d_status, void *ws,
                  size_t ws_bytes, hipStream_t st) {
     if (!text.extract) {
-        if (const int rc = zero_rows(r, n, s, st)) return rc;
+        if (const int rc = fmx::stat_rows_zero(r, s.cells(n), (size_t)s.P, n, st)) return rc;
         const int e = fmx::launch_values_status_all(view.n_cu, d_status, n, FMX_ST_NOT_ENABLED, st);
-        if (e) return api_fail(FMX_E_HIP, std::string("numbers of hits: ") + hipGetErrorString((hipError_t)e));
-        return FMX_OK;
+        return e ? hip_fail("numbers of hits", e) : FMX_OK;
     }
     fmx::ValuesWindows w;
     if (!fmx::numbers_windows(ws, ws_bytes, n, n_hits, s.n_edges, s.P, &w))
         return api_fail(FMX_E_ARG, "the workspace is smaller than fmx_numbers_of_hits_scratch_bytes");
     int e = fmx::launch_numbers_ranges(view.table, view.count, text.text_len, view.n_cu, n, term_len, d_hit_off, d_locs, n_hits, s.edges, s.n_edges,
                                        s.permille, s.P, ws, ws_bytes, st);
-    if (e) return api_fail(FMX_E_HIP, std::string("windows of hits: ") + hipGetErrorString((hipError_t)e));
+    if (e) return hip_fail("windows of hits", e);
     if (const int rc = fmx::extract_windows(idx, w, (int32_t)n_hits, st)) return rc;
     e = fmx::launch_numbers_rows(view.n_cu, n, d_hit_off, n_hits, s.n_edges, s.frac_digits, s.P, r.count, r.sum_lo, r.sum_hi, r.min, r.max, r.pct,
                                  r.not_number, r.overflow, d_status, ws, ws_bytes, st);
-    if (e) return api_fail(FMX_E_HIP, std::string("numbers of hits: ") + hipGetErrorString((hipError_t)e));
-    return FMX_OK;
-}
-
-int check_term_len(int32_t n, const int32_t *term_len) {
-    for (int32_t i = 0; i < n; ++i)
-        if (term_len[i] < 0) return api_fail(FMX_E_ARG, "term_len[" + std::to_string(i) + "] is negative");
-    return FMX_OK;
+    return e ? hip_fail("numbers of hits", e) : FMX_OK;
 }
 
 // what the host forms' stage needs of the call's arguments
@@ -120,26 +91,15 @@ int stats_stage(const fmx::HitsBetween &h, void *arg) {
     StatsArgs &a = *static_cast<StatsArgs *>(arg);
     const hipStream_t st = static_cast<hipStream_t>(h.stream);
     const Shape &s = a.shape;
-    const size_t cells = s.cells(h.n), pcts = cells * (size_t)s.P;
+    const size_t cells = s.cells(h.n), P = (size_t)s.P;
     if (h.total - h.term_hits == 0) {  // (no value pattern has a hit: nothing runs on the device)
         zero_host_rows(a.host, h.n, s);
         a.kept_off.assign((size_t)h.n + 1, 0);
-        if (!a.text.extract) {
-            const int e = fmx::launch_values_status_all(h.view->n_cu, h.status, h.n, FMX_ST_NOT_ENABLED, st);
-            if (e) return api_fail(FMX_E_HIP, std::string("numbers of hits: ") + hipGetErrorString((hipError_t)e));
-        }
-        return FMX_OK;
+        return a.text.extract ? FMX_OK : fmx::status_all(h, FMX_ST_NOT_ENABLED, "numbers of hits");
     }
-    Rows d{};
+    Rows d;
     int rc;
-    auto room = [&](const void *wanted, size_t bytes, auto **out) -> int {
-        return wanted ? h.block(h.call, bytes + 8, reinterpret_cast<void **>(out)) : FMX_OK;
-    };
-    if ((rc = room(a.host.count, cells * 4, &d.count)) || (rc = room(a.host.sum_lo, cells * 8, &d.sum_lo)) ||
-        (rc = room(a.host.sum_hi, cells * 8, &d.sum_hi)) || (rc = room(a.host.min, cells * 8, &d.min)) ||
-        (rc = room(a.host.max, cells * 8, &d.max)) || (rc = room(pcts ? a.host.pct : nullptr, pcts * 8, &d.pct)) ||
-        (rc = room(a.host.not_number, (size_t)h.n * 4, &d.not_number)) || (rc = room(a.host.overflow, (size_t)h.n * 4, &d.overflow)))
-        return rc;
+    if ((rc = fmx::stat_rows_blocks(h, &a.host, cells, P, h.n, &d))) return rc;
     const int64_t *d_off = nullptr;
     const int32_t *d_locs = nullptr;
     int64_t n_hits = 0;
@@ -149,18 +109,7 @@ int stats_stage(const fmx::HitsBetween &h, void *arg) {
     if (ws_bytes > 0 && (rc = h.block(h.call, ws_bytes, &ws))) return rc;
     if ((rc = numbers_impl(h.idx, *h.view, a.text, h.n, a.term_len.data(), d_off, d_locs, n_hits, s, d, h.status, ws, ws_bytes, st))) return rc;
     FMX_HIP_TRY(hipMemcpyAsync(a.kept_off.data(), d_off, ((size_t)h.n + 1) * 8, hipMemcpyDeviceToHost, st));
-    auto down = [&](void *host, const void *dev, size_t bytes) -> hipError_t {
-        return host && bytes > 0 ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-    };
-    FMX_HIP_TRY(down(a.host.count, d.count, cells * 4));
-    FMX_HIP_TRY(down(a.host.sum_lo, d.sum_lo, cells * 8));
-    FMX_HIP_TRY(down(a.host.sum_hi, d.sum_hi, cells * 8));
-    FMX_HIP_TRY(down(a.host.min, d.min, cells * 8));
-    FMX_HIP_TRY(down(a.host.max, d.max, cells * 8));
-    FMX_HIP_TRY(down(a.host.pct, d.pct, pcts * 8));
-    FMX_HIP_TRY(down(a.host.not_number, d.not_number, (size_t)h.n * 4));
-    FMX_HIP_TRY(down(a.host.overflow, d.overflow, (size_t)h.n * 4));
-    return FMX_OK;
+    return fmx::stat_rows_down(a.host, d, cells, P, h.n, st);
 }
 
 // the checks the two host forms share, behind their own batches'; *done: an empty call that has been answered
@@ -202,15 +151,15 @@ int fmx_numbers_of_hits_dev(const fmx_index *idx, int32_t n, const int32_t *term
     Shape s;
     int rc = check_shape(n, edges, n_edges, frac_digits, permille, n_permille, &s);
     if (rc) return rc;
-    if ((rc = check_term_len(n, term_len))) return rc;
+    if ((rc = fmx::check_term_len(n, term_len))) return rc;
     fmx::LineView view;
     fmx::TextView text;
     if ((rc = fmx::line_view(idx, &view)) || (rc = fmx::text_view(idx, &text))) return rc;
     if (edges && !view.table) return no_line_table();
     if (n == 0) return FMX_OK;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const Rows rows{d_count, d_sum_lo, d_sum_hi, d_min, d_max, n_permille > 0 ? d_pct : nullptr, d_not_number, d_overflow};
-    if (n_hits == 0) return zero_rows(rows, n, s, st);
+    const Rows rows{d_count, d_sum_lo, d_sum_hi, d_min, d_max, n_permille > 0 ? d_pct : nullptr, nullptr, d_not_number, d_overflow};
+    if (n_hits == 0) return fmx::stat_rows_zero(rows, s.cells(n), (size_t)s.P, n, st);
     if (!d_ws || ws_bytes < fmx::numbers_of_hits_scratch_bytes(n, n_hits, n_edges, n_permille))
         return api_fail(FMX_E_ARG, "the workspace is smaller than fmx_numbers_of_hits_scratch_bytes");
     return numbers_impl(idx, view, text, n, term_len, d_hit_off, d_locs, n_hits, s, rows, d_status, d_ws, ws_bytes, st);
@@ -231,7 +180,7 @@ int fmx_number_stats_where_batch(const fmx_index *idx, const uint16_t *pat, cons
     int rc;
     if ((rc = fmx::check_literal_batches(pat_off, n, term_off, n_terms))) return rc;
     if ((rc = stats_call_args(idx, n, n_terms, query_off, term_kind, q, where_of, edges, n_edges, frac_digits, permille, n_permille,
-                              Rows{count, sum_lo, sum_hi, min, max, pct, not_number, overflow}, term_status, &args, &done)) ||
+                              Rows{count, sum_lo, sum_hi, min, max, pct, nullptr, not_number, overflow}, term_status, &args, &done)) ||
         done)
         return rc;
     fmx::MergedBatch merged;
@@ -260,7 +209,7 @@ int fmx_number_stats_where_class_batch(const fmx_index *idx, const uint16_t *alt
     StatsArgs args;
     bool done = false;
     if ((rc = stats_call_args(idx, n, n_terms, query_off, term_kind, q, where_of, edges, n_edges, frac_digits, permille, n_permille,
-                              Rows{count, sum_lo, sum_hi, min, max, pct, not_number, overflow}, term_status, &args, &done)) ||
+                              Rows{count, sum_lo, sum_hi, min, max, pct, nullptr, not_number, overflow}, term_status, &args, &done)) ||
         done)
         return rc;
     fmx::MergedBatch merged;

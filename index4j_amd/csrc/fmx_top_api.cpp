@@ -14,6 +14,7 @@ namespace {
 
 using fmx::api_fail;
 using fmx::guarded;
+using fmx::hip_fail;
 using fmx::no_line_table;
 using fmx::zero;
 
@@ -62,19 +63,17 @@ int top_impl(const fmx_index *idx, const fmx::LineView &view, const fmx::TextVie
     if (!text.extract) {
         if (const int rc = zero_rows(r, n, s, st)) return rc;
         const int e = fmx::launch_values_status_all(view.n_cu, d_status, n, FMX_ST_NOT_ENABLED, st);
-        if (e) return api_fail(FMX_E_HIP, std::string("top lines of hits: ") + hipGetErrorString((hipError_t)e));
-        return FMX_OK;
+        return e ? hip_fail("top lines of hits", e) : FMX_OK;
     }
     fmx::ValuesWindows w;
     if (!fmx::top_lines_windows(ws, ws_bytes, n, n_hits, s.top, &w))
         return api_fail(FMX_E_ARG, "the workspace is smaller than fmx_top_lines_of_hits_scratch_bytes");
     int e = fmx::launch_top_lines_windows(text.text_len, view.n_cu, n, term_len, descending, d_hit_off, d_locs, n_hits, s.top, ws, ws_bytes, st);
-    if (e) return api_fail(FMX_E_HIP, std::string("windows of hits: ") + hipGetErrorString((hipError_t)e));
+    if (e) return hip_fail("windows of hits", e);
     if (const int rc = fmx::extract_windows(idx, w, (int32_t)n_hits, st)) return rc;
     e = fmx::launch_top_lines_rows(view.table, view.count, text.text_len, view.n_cu, n, d_hit_off, n_hits, s.frac_digits, s.first, s.top, r.rows,
                                    r.row_line, r.row_value, r.row_loc, r.lines, r.numbers, r.not_number, r.overflow, d_status, ws, ws_bytes, st);
-    if (e) return api_fail(FMX_E_HIP, std::string("top lines of hits: ") + hipGetErrorString((hipError_t)e));
-    return FMX_OK;
+    return e ? hip_fail("top lines of hits", e) : FMX_OK;
 }
 
 // what the host forms' stage needs of the call's arguments
@@ -109,11 +108,7 @@ int top_stage(const fmx::HitsBetween &h, void *arg) {
     if (h.total - h.term_hits == 0) {  // (no value pattern has a hit: nothing runs on the device)
         zero_host_rows(a.host, h.n, s);
         a.kept_off.assign((size_t)h.n + 1, 0);
-        if (!a.text.extract) {
-            const int e = fmx::launch_values_status_all(h.view->n_cu, h.status, h.n, FMX_ST_NOT_ENABLED, st);
-            if (e) return api_fail(FMX_E_HIP, std::string("top lines of hits: ") + hipGetErrorString((hipError_t)e));
-        }
-        return FMX_OK;
+        return a.text.extract ? FMX_OK : fmx::status_all(h, FMX_ST_NOT_ENABLED, "top lines of hits");
     }
     Rows d{};
     int rc;
@@ -149,13 +144,6 @@ int top_stage(const fmx::HitsBetween &h, void *arg) {
     return FMX_OK;
 }
 
-// the HOST arrays of the filter: where_of (n entries, -1 .. q - 1) and the window of lines, as fmx_field_values_where_batch judges them
-int check_where(int32_t n, const int32_t *where_of, int32_t q, int32_t line_lo, int32_t line_hi) {
-    if (line_lo < 0 || line_hi < 0) return api_fail(FMX_E_ARG, "bad arguments");
-    if (line_lo > line_hi) return api_fail(FMX_E_ARG, "the window of lines ends in front of its start");
-    return fmx::check_where_of(n, where_of, q);
-}
-
 // the checks the two host forms share, behind their own batches'; *done: an empty call that has been answered.  The pattern
 // lengths are made by the caller from its own offsets (judged by then).
 int top_call_args(const fmx_index *idx, int32_t n, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
@@ -163,7 +151,7 @@ int top_call_args(const fmx_index *idx, int32_t n, int32_t n_terms, const int32_
                   int32_t top, const Rows &host, int32_t *term_status, TopArgs *args, bool *done) {
     fmx::LineView view;
     int rc;
-    if ((rc = fmx::check_query_arrays(n_terms, q, query_off, term_kind)) || (rc = check_where(n, where_of, q, line_lo, line_hi)) ||
+    if ((rc = fmx::check_query_arrays(n_terms, q, query_off, term_kind)) || (rc = fmx::check_where(n, where_of, q, line_lo, line_hi)) ||
         (rc = check_shape(n, args->term_len.data(), descending, frac_digits, first, top, &args->shape)) || (rc = fmx::line_view(idx, &view)) ||
         (rc = fmx::text_view(idx, &args->text)))
         return rc;

@@ -11,17 +11,15 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <cstring>
 
 namespace {
 
 using fmx::api_fail;
 using fmx::guarded;
+using fmx::hip_fail;
 using fmx::no_line_table;
 using fmx::zero;
-
-int hip_fail(const char *what, int e) { return api_fail(FMX_E_HIP, std::string(what) + ": " + hipGetErrorString((hipError_t)e)); }
 
 // the shape of the answer and the HOST arrays that cut it: the edges (none at all: one bucket, every line) and top
 struct Shape {
@@ -48,35 +46,10 @@ int check_groups(int32_t n, const int64_t *val_off, const Shape &s, int64_t *row
         default: return api_fail(FMX_E_ARG, "the sort key pattern | rank | bucket is wider than 64 bits");
     }
 }
-int check_values_shape(const uint16_t *stop, int32_t n_stop, int32_t max_len) {
-    if (max_len < 1 || max_len > 64) return api_fail(FMX_E_ARG, "max_len is outside [1, 64]");
-    if (n_stop < 0 || n_stop > 64 || (n_stop > 0 && !stop)) return api_fail(FMX_E_ARG, "the stop set is outside [0, 64] code units");
-    return FMX_OK;
-}
 
 // ---- the host form --------------------------------------------------------------------------------------------------------------------
-// the ONE allocation of the answer: row_count | row_group | text_off | chars | hist, each at a multiple of 8
-struct Result {
-    uint8_t *p = nullptr;
-    size_t row_count = 0, row_group = 0, text_off = 0, chars = 0, hist = 0, total = 0;
-    ~Result() { free(p); }
-    bool alloc(size_t R, size_t units, size_t B) {
-        size_t at = 0;
-        auto take = [&](size_t bytes) {
-            const size_t here = at;
-            at += (bytes + 7) / 8 * 8;
-            return here;
-        };
-        row_count = take(R * 4);
-        row_group = take(R * 4);
-        text_off = take((R + 1) * 8);
-        chars = take(units * 2 + 2);
-        hist = take(R * B * 4);
-        total = at + 8;
-        p = static_cast<uint8_t *>(calloc(total, 1));
-        return p != nullptr;
-    }
-};
+// the regions of the ONE allocation of the answer
+enum { kRowCount, kRowGroup, kTextOff, kChars, kHist };
 
 struct HistArgs {
     fmx::HitsFilter filter{};
@@ -88,13 +61,8 @@ struct HistArgs {
     int32_t *other = nullptr;  // the caller's n * B ints, zeroed before the stage runs
     // what the stage leaves (host; arrived when the call has synchronised)
     std::vector<int64_t> kept_off, part_off, val_off, row_off;  // n + 1, n + 1, n + 2 (the units of the groups' text behind), n + 1
-    Result result;
+    fmx::PackedResult result;
 };
-
-int status_all(const fmx::HitsBetween &h, int32_t value) {
-    const int e = fmx::launch_values_status_all(h.view->n_cu, h.status, h.n, value, h.stream);
-    return e ? hip_fail("top values per bucket", e) : FMX_OK;
-}
 
 // n > 0 value patterns behind n_terms filter terms
 int hist_stage(const fmx::HitsBetween &h, void *arg) {
@@ -103,7 +71,7 @@ int hist_stage(const fmx::HitsBetween &h, void *arg) {
     const Shape &s = a.shape;
     const int32_t n = h.n;
     if (h.total - h.term_hits == 0)  // (no value pattern has a hit: nothing runs on the device)
-        return a.text.extract ? FMX_OK : status_all(h, FMX_ST_NOT_ENABLED);
+        return a.text.extract ? FMX_OK : fmx::status_all(h, FMX_ST_NOT_ENABLED, "top values per bucket");
     int rc;
     const int64_t *d_off = nullptr;
     const int32_t *d_locs = nullptr;
@@ -111,7 +79,7 @@ int hist_stage(const fmx::HitsBetween &h, void *arg) {
     if ((rc = fmx::kept_hits_stage(h, a.filter, &d_off, &d_locs, &slots))) return rc;
     FMX_HIP_TRY(hipMemcpyAsync(a.kept_off.data(), d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
     FMX_HIP_TRY(hipStreamSynchronize(st));
-    if (!a.text.extract) return status_all(h, FMX_ST_NOT_ENABLED);
+    if (!a.text.extract) return fmx::status_all(h, FMX_ST_NOT_ENABLED, "top values per bucket");
     const int64_t K = a.kept_off[(size_t)n] - a.kept_off[0];
     if (K == 0) return FMX_OK;  // (no hit is kept: no groups, no rows, `other` stays zero)
     if (K > 0x7fffffff) return api_fail(FMX_E_ARG, "more than 2^31 - 1 hits in one call");
@@ -165,13 +133,13 @@ int hist_stage(const fmx::HitsBetween &h, void *arg) {
     int64_t row_units = 0;  // ONE 8-byte read: the packed length of the rows' text sizes the allocation
     FMX_HIP_TRY(hipMemcpyAsync(&row_units, d_row_text_off + R, 8, hipMemcpyDeviceToHost, st));
     FMX_HIP_TRY(hipStreamSynchronize(st));
-    if (!a.result.alloc(R, (size_t)row_units, B)) return api_fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(R) + " rows");
-    uint8_t *out = a.result.p;
-    FMX_HIP_TRY(hipMemcpyAsync(out + a.result.row_count, d_row_count, R * 4, hipMemcpyDeviceToHost, st));
-    FMX_HIP_TRY(hipMemcpyAsync(out + a.result.row_group, d_row_group, R * 4, hipMemcpyDeviceToHost, st));
-    FMX_HIP_TRY(hipMemcpyAsync(out + a.result.text_off, d_row_text_off, (R + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (row_units > 0) FMX_HIP_TRY(hipMemcpyAsync(out + a.result.chars, d_row_chars, (size_t)row_units * 2, hipMemcpyDeviceToHost, st));
-    FMX_HIP_TRY(hipMemcpyAsync(out + a.result.hist, d_hist, R * B * 4, hipMemcpyDeviceToHost, st));
+    if (!a.result.alloc({R * 4, R * 4, (R + 1) * 8, (size_t)row_units * 2 + 2, R * B * 4}))
+        return api_fail(FMX_E_NOMEM, "out of host memory for " + std::to_string(R) + " rows");
+    FMX_HIP_TRY(hipMemcpyAsync(a.result.region<int32_t>(kRowCount), d_row_count, R * 4, hipMemcpyDeviceToHost, st));
+    FMX_HIP_TRY(hipMemcpyAsync(a.result.region<int32_t>(kRowGroup), d_row_group, R * 4, hipMemcpyDeviceToHost, st));
+    FMX_HIP_TRY(hipMemcpyAsync(a.result.region<int64_t>(kTextOff), d_row_text_off, (R + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (row_units > 0) FMX_HIP_TRY(hipMemcpyAsync(a.result.region<uint16_t>(kChars), d_row_chars, (size_t)row_units * 2, hipMemcpyDeviceToHost, st));
+    FMX_HIP_TRY(hipMemcpyAsync(a.result.region<int32_t>(kHist), d_hist, R * B * 4, hipMemcpyDeviceToHost, st));
     return FMX_OK;
 }
 
@@ -206,7 +174,7 @@ bool results_missing(const HistCall &c) {
 int hist_call_args(const fmx_index *idx, const HistCall &c, HistArgs *a, bool *done) {
     int rc;
     fmx::LineView view;
-    if ((rc = check_values_shape(c.stop, c.n_stop, c.max_len)) || (rc = fmx::check_query_arrays(c.n_terms, c.q, c.query_off, c.term_kind)) ||
+    if ((rc = fmx::check_values_shape(c.stop, c.n_stop, c.max_len)) || (rc = fmx::check_query_arrays(c.n_terms, c.q, c.query_off, c.term_kind)) ||
         (rc = fmx::check_where_of(c.n, c.where_of, c.q)) || (rc = check_shape(c.n, c.edges, c.n_edges, c.top, &a->shape)) ||
         (rc = fmx::line_view(idx, &view)) || (rc = fmx::text_view(idx, &a->text)))
         return rc;
@@ -243,14 +211,12 @@ int hist_call_run(const fmx_index *idx, const HistCall &c, const fmx::ValuesBatc
     for (int32_t i = 0; i < c.n && c.n_values; ++i) c.n_values[i] = (int32_t)(a.val_off[(size_t)i + 1] - a.val_off[(size_t)i]);
     memcpy(c.row_off, a.row_off.data(), ((size_t)c.n + 1) * 8);
     if (a.result.p) {  // the ONE allocation: freed with fmx_free_buffer((uint8_t *)*row_count)
-        uint8_t *out = a.result.p;
-        const Result &r = a.result;
-        *c.row_count = reinterpret_cast<int32_t *>(out + r.row_count);
-        *c.row_group = reinterpret_cast<int32_t *>(out + r.row_group);
-        *c.text_off = reinterpret_cast<int64_t *>(out + r.text_off);
-        *c.chars = reinterpret_cast<uint16_t *>(out + r.chars);
-        *c.hist = reinterpret_cast<int32_t *>(out + r.hist);
-        a.result.p = nullptr;
+        *c.row_count = a.result.region<int32_t>(kRowCount);
+        *c.row_group = a.result.region<int32_t>(kRowGroup);
+        *c.text_off = a.result.region<int64_t>(kTextOff);
+        *c.chars = a.result.region<uint16_t>(kChars);
+        *c.hist = a.result.region<int32_t>(kHist);
+        a.result.release();
     }
     return FMX_OK;
 }

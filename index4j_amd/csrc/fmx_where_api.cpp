@@ -13,13 +13,6 @@ namespace {
 using fmx::api_fail;
 using fmx::guarded;
 
-// the HOST arrays of a filter: where_of (n entries, -1 .. q - 1) and the window of lines
-int check_where(int32_t n, const int32_t *where_of, int32_t q, int32_t line_lo, int32_t line_hi) {
-    if (n < 0 || q < 0 || line_lo < 0 || line_hi < 0 || (n > 0 && !where_of)) return api_fail(FMX_E_ARG, "bad arguments");
-    if (line_lo > line_hi) return api_fail(FMX_E_ARG, "the window of lines ends in front of its start");
-    return fmx::check_where_of(n, where_of, q);
-}
-
 // the value patterns' hits that lie in the lines of their queries and in the window.  A call that does not filter needs no line
 // table: every hit is kept.
 int where_between(const fmx::HitsBetween &h, void *arg) {
@@ -30,19 +23,13 @@ int where_between(const fmx::HitsBetween &h, void *arg) {
     return fmx::hits_in_lines_stage(h, *static_cast<const fmx::HitsFilter *>(arg), h.kept_off, h.kept_locs);
 }
 
-// what the two host forms share in front of their own batches' checks ...
-int where_call_head(int32_t max_len, const uint16_t *stop, int32_t n_stop) {
-    if (max_len < 1 || max_len > 64) return api_fail(FMX_E_ARG, "max_len is outside [1, 64]");
-    if (n_stop < 0 || n_stop > 64 || (n_stop > 0 && !stop)) return api_fail(FMX_E_ARG, "the stop set is outside [0, 64] code units");
-    return FMX_OK;
-}
-// ... and behind them; *done: an empty call that has been answered
+// what the two host forms share behind their own batches' checks; *done: an empty call that has been answered
 int where_call_args(const fmx_index *idx, int32_t n, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind, int32_t q,
                     const int32_t *where_of, int32_t line_lo, int32_t line_hi, int64_t *val_off, int32_t *term_status, fmx::HitsFilter *filter,
                     bool *done) {
     fmx::LineView view;
     int rc;
-    if ((rc = fmx::check_query_arrays(n_terms, q, query_off, term_kind)) || (rc = check_where(n, where_of, q, line_lo, line_hi)) ||
+    if ((rc = fmx::check_query_arrays(n_terms, q, query_off, term_kind)) || (rc = fmx::check_where(n, where_of, q, line_lo, line_hi)) ||
         (rc = fmx::line_view(idx, &view)))
         return rc;
     *filter = fmx::HitsFilter{query_off, term_kind, q, where_of, line_lo, line_hi, fmx::hits_filter_asked(n, where_of, line_lo, line_hi)};
@@ -75,7 +62,7 @@ int fmx_hits_in_lines_dev(const fmx_index *idx, int32_t n, const int32_t *where_
         (n > 0 && n_hits > 0 && (!d_locs || !d_kept_locs)))
         return api_fail(FMX_E_ARG, "bad arguments");
     if (n_hits > 0x7fffffff) return api_fail(FMX_E_ARG, "more than 2^31 - 1 hits in one call");
-    int rc = check_where(n, where_of, q, line_lo, line_hi);
+    int rc = fmx::check_where(n, where_of, q, line_lo, line_hi);
     if (rc) return rc;
     for (int32_t i = 0; i < n; ++i)
         if (where_of[i] >= 0 && !d_line_off) return api_fail(FMX_E_ARG, "bad arguments");
@@ -91,8 +78,7 @@ int fmx_hits_in_lines_dev(const fmx_index *idx, int32_t n, const int32_t *where_
         return api_fail(FMX_E_ARG, "the workspace is smaller than fmx_hits_in_lines_scratch_bytes");
     const int e = fmx::launch_hits_in_lines(view.table, view.count, view.n_cu, n, where_of, d_line_off, d_lines, line_lo, line_hi, d_hit_off,
                                             d_locs, n_hits, d_kept_off, d_kept_locs, d_ws, ws_bytes, stream);
-    if (e) return api_fail(FMX_E_HIP, std::string("hits in lines: ") + hipGetErrorString((hipError_t)e));
-    return FMX_OK;
+    return e ? fmx::hip_fail("hits in lines", e) : FMX_OK;
     });
 }
 
@@ -108,7 +94,7 @@ int fmx_field_values_where_batch(const fmx_index *idx, const uint16_t *pat, cons
     fmx::HitsFilter filter;
     bool done = false;
     int rc;
-    if ((rc = where_call_head(max_len, stop, n_stop)) || (rc = fmx::check_literal_batches(pat_off, n, term_off, n_terms)) ||
+    if ((rc = fmx::check_values_shape(stop, n_stop, max_len)) || (rc = fmx::check_literal_batches(pat_off, n, term_off, n_terms)) ||
         (rc = where_call_args(idx, n, n_terms, query_off, term_kind, q, where_of, line_lo, line_hi, val_off, term_status, &filter, &done)) || done)
         return rc;
     fmx::MergedBatch merged;
@@ -134,7 +120,7 @@ int fmx_field_values_where_class_batch(const fmx_index *idx, const uint16_t *alt
     fmx::HitsFilter filter;
     bool done = false;
     int rc;
-    if ((rc = where_call_head(max_len, stop, n_stop)) ||
+    if ((rc = fmx::check_values_shape(stop, n_stop, max_len)) ||
         (rc = fmx::check_class_batches(alt, pos_off, n_pos, pat_off, n, term_alt, term_pos_off, term_n_pos, term_off, n_terms)) ||
         (rc = where_call_args(idx, n, n_terms, query_off, term_kind, q, where_of, line_lo, line_hi, val_off, term_status, &filter, &done)) || done)
         return rc;

@@ -3,7 +3,9 @@
 // stand-alone program for -fsanitize=address,undefined.  Every array lies on the heap with exactly the size the contract gives it
 // (an array of no entries is NULL), so a read or a store outside one is a report.  The judge is the merge written out naively
 // below: the strings of the terms, then those of the value patterns, laid end to end.  The refusals are checked by their message,
-// and by a MergedBatch that is still empty.  Prints one " ok: " line per case; exit code 0 = clean.
+// and by a MergedBatch that is still empty.  The keyed merges (terms | key patterns | number patterns) are judged by two successive
+// merges; the checks of the values' and the numbers' shape, the limits of the hits, term_len and the window of lines at their
+// edges, by their message.  Prints one " ok: " line per case; exit code 0 = clean.
 #include "fmx_host_stage.hpp"
 
 #include <cstdio>
@@ -148,7 +150,68 @@ void class_case(const char *name, const std::vector<ClassPat> &terms, const std:
     passed(name);
 }
 
+// the keyed merges: ONE batch terms | keys | numbers.  The judge is what two successive calls of the merges above give — the keys in
+// the terms' slot of the first, its answer as the value patterns of the second — and the lengths of the strings themselves.
+void same_batch(const char *name, const fmx::MergedBatch &m, const fmx::ValuesBatch &b, const fmx::MergedBatch &ref, const fmx::ValuesBatch &rb) {
+    require(m.chars == ref.chars && m.pos == ref.pos && m.off == ref.off, name, "another merged batch than two successive merges give");
+    require(b.n_terms == rb.n_terms && b.n == rb.n && b.n_pos == rb.n_pos && b.max_ranges == rb.max_ranges && b.chars == m.chars.data() &&
+                b.pat_off == m.off.data() && (rb.pos_off ? b.pos_off == m.pos.data() : !b.pos_off),
+            name, "the shape");
+}
+
+void keyed_literal_case(const char *name, const std::vector<Str> &terms, const std::vector<Str> &keys, const std::vector<Str> &pats,
+                        int32_t term_lead, int32_t key_lead, int32_t pat_lead) {
+    const Literal t(terms, term_lead, true), k(keys, key_lead, true), p(pats, pat_lead, false);
+    const auto t_chars = exact(t.chars), k_chars = exact(k.chars), p_chars = exact(p.chars);
+    const auto t_off = exact(t.off), k_off = exact(k.off), p_off = exact(p.off);
+    fmx::MergedBatch both, ref, m;
+    fmx::ValuesBatch bb{}, rb{}, b{};
+    std::vector<int32_t> len{-7};  // (what was in it goes)
+    require(fmx::merge_literal_batch(p_chars.get(), p_off.get(), p.count, k_chars.get(), k_off.get(), k.count, &both, &bb) == FMX_OK &&
+                fmx::merge_literal_batch(both.chars.data(), both.off.data(), k.count + p.count, t_chars.get(), t_off.get(), t.count, &ref, &rb) == FMX_OK,
+            name, "the two successive merges refuse");
+    require(fmx::merge_keyed_literal_batch(k_chars.get(), k_off.get(), k.count, p_chars.get(), p_off.get(), p.count, t_chars.get(), t_off.get(), t.count,
+                                           &m, &b, &len) == FMX_OK,
+            name, "the keyed merge refuses");
+    same_batch(name, m, b, ref, rb);
+    require(len.size() == keys.size() + pats.size(), name, "the count of term_len");
+    for (size_t i = 0; i < len.size(); ++i)
+        require(len[i] == (int32_t)(i < keys.size() ? keys[i] : pats[i - keys.size()]).size(), name, "a term_len");
+    passed(name);
+}
+
+void keyed_class_case(const char *name, const std::vector<ClassPat> &terms, const std::vector<ClassPat> &keys, const std::vector<ClassPat> &pats,
+                      int32_t lead_alt, int32_t lead_pos) {
+    const Class t(terms, lead_alt, lead_pos), k(keys, lead_alt, lead_pos), p(pats, lead_alt, lead_pos);
+    const bool no_terms = terms.empty();  // (no terms: the three arrays of the terms are NULL; the keys' are always there)
+    const auto t_alt = exact(t.alt), k_alt = exact(k.alt), p_alt = exact(p.alt);
+    const auto t_pos = exact(no_terms ? std::vector<int32_t>() : t.pos_off), k_pos = exact(k.pos_off), p_pos = exact(p.pos_off);
+    const auto t_off = exact(no_terms ? std::vector<int32_t>() : t.pat_off), k_off = exact(k.pat_off), p_off = exact(p.pat_off);
+    const int32_t t_n_pos = no_terms ? 0 : t.n_pos;
+    fmx::MergedBatch both, ref, m;
+    fmx::ValuesBatch bb{}, rb{}, b{};
+    std::vector<int32_t> len{-7};
+    require(fmx::merge_class_batch(p_alt.get(), p_pos.get(), p.n_pos, p_off.get(), p.count, k_alt.get(), k_pos.get(), k.n_pos, k_off.get(), k.count, 7,
+                                   &both, &bb) == FMX_OK &&
+                fmx::merge_class_batch(both.chars.data(), both.pos.data(), (int32_t)both.pos.size() - 1, both.off.data(), k.count + p.count, t_alt.get(),
+                                       t_pos.get(), t_n_pos, t_off.get(), t.count, 7, &ref, &rb) == FMX_OK,
+            name, "the two successive merges refuse");
+    require(fmx::merge_keyed_class_batch(k_alt.get(), k_pos.get(), k.n_pos, k_off.get(), k.count, p_alt.get(), p_pos.get(), p.n_pos, p_off.get(), p.count,
+                                         t_alt.get(), t_pos.get(), t_n_pos, t_off.get(), t.count, 7, &m, &b, &len) == FMX_OK,
+            name, "the keyed merge refuses");
+    same_batch(name, m, b, ref, rb);
+    require(len.size() == keys.size() + pats.size(), name, "the count of term_len");
+    for (size_t i = 0; i < len.size(); ++i)  // (a position is a character)
+        require(len[i] == (int32_t)(i < keys.size() ? keys[i] : pats[i - keys.size()]).size(), name, "a term_len");
+    passed(name);
+}
+
 bool untouched(const fmx::MergedBatch &m) { return m.chars.empty() && m.pos.empty() && m.off.empty(); }
+
+void accepted(const char *name, int rc) {
+    require(rc == FMX_OK && g_code == 0, name, "refused");
+    passed(name);
+}
 
 void refused(const char *name, int rc, const char *message, const fmx::MergedBatch *m = nullptr) {
     require(rc == FMX_E_ARG && g_code == FMX_E_ARG, name, "not refused with FMX_E_ARG");
@@ -269,6 +332,85 @@ int main() {
                     fmx::hits_filter_asked(3, no.get(), 1, INT32_MAX) && fmx::hits_filter_asked(0, nullptr, 0, INT32_MAX - 1),
                 "hits_filter_asked", "a wrong answer");
         passed("the filter is asked for");
+    }
+    // ---- the keyed merges: terms | keys | numbers
+    {
+        const std::vector<Str> keys{str("user="), str("k")}, nums{str("latency_ms="), str(" took "), {0x20AC}};
+        keyed_literal_case("keyed literal, m = 0 and n = 0", {}, {}, {}, 0, 0, 0);
+        keyed_literal_case("keyed literal, m = 0 and n = 0 behind terms", terms, {}, {}, 0, 0, 0);
+        keyed_literal_case("keyed literal, one empty key and one empty number pattern", {}, std::vector<Str>(1), std::vector<Str>(1), 0, 0, 0);
+        keyed_literal_case("keyed literal, no terms", {}, keys, nums, 0, 0, 0);
+        keyed_literal_case("keyed literal, terms in front", terms, keys, nums, 0, 0, 0);
+        keyed_literal_case("keyed literal, key_off[0] > 0 and pat_off[0] > 0", terms, keys, nums, 1, 4, 2);
+        keyed_literal_case("keyed literal, empty strings among the others", {{}, str("a")}, {{}, str("bc"), {}}, {str("d"), {}}, 0, 3, 0);
+        const ClassPat user{{'u', 'U'}, {'s', 'S'}, {'e', 'E', 0x212F}, {'r'}, {'=', ':', ' '}};
+        keyed_class_case("keyed class, m = 0 and n = 0", {}, {}, {}, 0, 0);
+        keyed_class_case("keyed class, one empty key and one empty number pattern", {}, std::vector<ClassPat>(1), std::vector<ClassPat>(1), 0, 0);
+        keyed_class_case("keyed class, a key with several alternatives per position, no terms", {}, {user}, {digits}, 0, 0);
+        keyed_class_case("keyed class, terms in front", {info}, {user, digits}, {digits, {{'m'}, {'s', 'S'}}}, 0, 0);
+        keyed_class_case("keyed class, offsets that start above 0", {info, {}}, {user}, {{{}, {'x'}}, digits}, 3, 2);
+        // a NULL pattern array with characters in it
+        const std::vector<uint16_t> chars{'a', 'b', 'c'};
+        const std::vector<int32_t> off{0, 1, 3};
+        const auto c = exact(chars);
+        const auto o = exact(off);
+        fmx::MergedBatch m;
+        fmx::ValuesBatch b{};
+        std::vector<int32_t> len;
+        refused("keyed literal, no characters of the keys",
+                fmx::merge_keyed_literal_batch(nullptr, o.get(), 2, c.get(), o.get(), 2, c.get(), o.get(), 2, &m, &b, &len), "bad arguments", &m);
+        refused("keyed literal, no characters of the numbers",
+                fmx::merge_keyed_literal_batch(c.get(), o.get(), 2, nullptr, o.get(), 2, c.get(), o.get(), 2, &m, &b, &len), "bad arguments", &m);
+        refused("keyed literal, no characters of the terms",
+                fmx::merge_keyed_literal_batch(c.get(), o.get(), 2, c.get(), o.get(), 2, nullptr, o.get(), 2, &m, &b, &len), "bad arguments", &m);
+        require(!b.chars && !b.pat_off && len.empty(), "keyed refusals", "the batch or term_len was written");
+    }
+    // ---- the shape of the values and of the numbers, the limits of the hits, term_len, the window of lines: at their edges
+    {
+        const std::vector<uint16_t> stop64(64, ';'), stop65(65, ';');
+        const auto s64 = exact(stop64), s65 = exact(stop65);
+        const char *const len_msg = "max_len is outside [1, 64]", *const stop_msg = "the stop set is outside [0, 64] code units";
+        refused("max_len 0", fmx::check_values_shape(nullptr, 0, 0), len_msg);
+        accepted("max_len 1", fmx::check_values_shape(nullptr, 0, 1));
+        accepted("max_len 64", fmx::check_values_shape(nullptr, 0, 64));
+        refused("max_len 65", fmx::check_values_shape(nullptr, 0, 65), len_msg);
+        refused("n_stop -1", fmx::check_values_shape(s64.get(), -1, 8), stop_msg);
+        accepted("n_stop 0", fmx::check_values_shape(nullptr, 0, 8));
+        accepted("n_stop 64", fmx::check_values_shape(s64.get(), 64, 8));
+        refused("n_stop 65", fmx::check_values_shape(s65.get(), 65, 8), stop_msg);
+        refused("n_stop 1 without a stop set", fmx::check_values_shape(nullptr, 1, 8), stop_msg);
+
+        const int64_t two31 = (int64_t)1 << 31, two29 = (int64_t)1 << 29;  // (2^29 windows of 64 code units: 2^35)
+        accepted("2^31 - 1 hits", fmx::check_values_hits(two31 - 1, 1));
+        refused("2^31 hits", fmx::check_values_hits(two31, 1), "more than 2^31 - 1 hits in one call");
+        accepted("2^35 code units", fmx::check_values_hits(two29, 64));
+        refused("2^35 code units and one window", fmx::check_values_hits(two29 + 1, 64), "the windows of the hits hold more than 2^35 code units");
+
+        const std::vector<int32_t> pm16{0, 1, 10, 50, 100, 250, 500, 750, 900, 950, 990, 995, 999, 1000, 500, 0}, pm_high{500, 1001};
+        std::vector<int32_t> pm17(pm16);
+        pm17.push_back(7);
+        const auto p16 = exact(pm16), p17 = exact(pm17), ph = exact(pm_high);
+        refused("frac_digits -1", fmx::check_numbers_shape(-1, nullptr, 0), "frac_digits is outside [0, 9]");
+        accepted("frac_digits 0", fmx::check_numbers_shape(0, nullptr, 0));
+        accepted("frac_digits 9", fmx::check_numbers_shape(9, nullptr, 0));
+        refused("frac_digits 10", fmx::check_numbers_shape(10, nullptr, 0), "frac_digits is outside [0, 9]");
+        accepted("n_permille 16", fmx::check_numbers_shape(3, p16.get(), 16));
+        refused("n_permille 17", fmx::check_numbers_shape(3, p17.get(), 17), "n_permille is outside [0, 16]");
+        refused("a permille of 1001", fmx::check_numbers_shape(3, ph.get(), 2), "a permille is outside [0, 1000]");
+
+        const std::vector<int32_t> lens{3, 0, 64}, neg{3, 0, -1};
+        const auto l = exact(lens), ng = exact(neg);
+        accepted("term_len, none negative", fmx::check_term_len(3, l.get()));
+        accepted("term_len, none at all", fmx::check_term_len(0, nullptr));
+        refused("a negative term_len", fmx::check_term_len(3, ng.get()), "term_len[2] is negative");
+
+        const std::vector<int32_t> where{-1, 0, 1}, high{0, 1, 2};
+        const auto w = exact(where), hi = exact(high);
+        accepted("the window of one line", fmx::check_where(3, w.get(), 2, 5, 5));
+        accepted("every line, no patterns", fmx::check_where(0, nullptr, 0, 0, INT32_MAX));
+        refused("a window that starts below 0", fmx::check_where(3, w.get(), 2, -1, 5), "bad arguments");
+        refused("a window that ends in front of its start", fmx::check_where(3, w.get(), 2, 6, 5), "the window of lines ends in front of its start");
+        refused("where_of at q behind a good window", fmx::check_where(3, hi.get(), 2, 0, 9), "where_of[2] is outside -1 .. q - 1");
     }
     std::printf("merged batch: %d cases ok\n", g_cases);
     return 0;

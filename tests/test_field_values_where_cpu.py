@@ -307,7 +307,7 @@ def test_merged_batch_is_sanitizer_clean(tmp_path):
     subprocess.check_call(cmd)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stdout[-3000:] + r.stderr[-6000:]
-    assert r.stdout.count(" ok: ") == 38 and "merged batch: 38 cases ok" in r.stdout, r.stdout[-3000:]
+    assert r.stdout.count(" ok: ") == 81 and "merged batch: 81 cases ok" in r.stdout, r.stdout[-3000:]
 
 
 def test_error_returns_without_a_device():

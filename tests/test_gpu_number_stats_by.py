@@ -303,6 +303,9 @@ def test_filters(edge):
     assert mixed.strings(0) == ["far"] and mixed.row(0, "far")[:2] == (2, 2200) and mixed.no_key[0] == mixed.kept[0] - 2
     s = fm.number_stats_by("n=", "k=", " \n", where=dict(all=["k=far"]), lines=(0, 2000))
     assert [(g["value"], g["lines"], g["sum"]) for g in s.groups] == [("far", 1, 100)] and s.no_key == 0 and s.kept == 1
+    for kw in (dict(), dict(where=dict(all=["k=far"]))):  # neither pattern has a hit, without a filter and with one
+        s = fm.number_stats_by("zzqq%", "zzqq#", " \n", **kw)
+        assert s.groups == [] and (s.no_key, s.not_number, s.overflow, s.kept, s.key_kept) == (0, 0, 0, 0, 0)
 
 
 # ---- 6. refusals ----
@@ -374,6 +377,12 @@ def test_index_without_extraction():
         assert (out["status"] == ST_NOT_ENABLED).all() and (out["key_status"] == ST_NOT_ENABLED).all()
         assert out["kept"].tolist() == [text.count("n="), text.count("m=")] == out["occurrences"].tolist() and out["key_kept"].tolist() == [text.count("k=")]
         assert out["no_key"].tolist() == [0, 0] and out["not_number"].tolist() == [0, 0]
+        # neither the key pattern nor the number pattern has a hit: nothing runs, the statuses still say why there are no groups
+        out = fm.number_stats_by_batch(*ia.pack_patterns([ia.as_chars("zzqq#")]), *ia.pack_patterns([ia.as_chars("zzqq%")]), [0],
+                                       *ia.pack_patterns([]), [0], [], [-1], [-1], " \n", 32)
+        assert out["val_off"].tolist() == [0, 0] and out["row_off"].tolist() == [0, 0] and len(out["count"]) == 0
+        assert (out["status"] == ST_NOT_ENABLED).all() and (out["key_status"] == ST_NOT_ENABLED).all()
+        assert out["kept"].tolist() == [0] == out["occurrences"].tolist() and out["key_kept"].tolist() == [0] and out["no_key"].tolist() == [0]
     finally:
         fm.close()
 

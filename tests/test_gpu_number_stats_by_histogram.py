@@ -258,6 +258,9 @@ def test_degenerate_calls(hd, edge):
     assert [r["lines"] for r in empty.rows] == [525, 480, 283] and all(r["count"] == [0] * 8 and r["sum"] == [0] * 8 for r in empty.rows + [empty.other])
     assert empty.kept == 0 and empty.n_groups == 356
     text, eo, efm, eT = edge
+    for kw in (dict(), dict(where=dict(all=["k=far"]))):  # neither pattern has a hit, without a query and with one
+        s = efm.number_stats_by_histogram("zzqq%", "zzqq#", [0, 1000, 3000], 3, " \n", 32, **kw)
+        assert s.rows == [] and s.other["count"] == [0, 0] and (s.no_key, s.not_number, s.overflow, s.kept, s.n_groups) == (0, 0, 0, 0, 0)
     q = [dict(all=["nokey"]), dict(all=["k=far"]), dict(all=["only"])]
     thirds = np.array([0, 1000, 2000, 3000], np.int32)
     none = case("edge byhist", efm, eo, eT, ["k="], ["n="], [0], " \n", 32, thirds, 5, queries=q, key_where=[0], where=[-1])
@@ -285,6 +288,12 @@ def test_degenerate_calls(hd, edge):
         assert out["key_row_off"].tolist() == [0, 0] and out["cell_off"].tolist() == [0, 0, 0] and out["n_groups"].tolist() == [0]
         assert (out["status"] == ST_NOT_ENABLED).all() and (out["key_status"] == ST_NOT_ENABLED).all()
         assert out["kept"].tolist() == [sub.count("n="), sub.count("m=")] == out["occurrences"].tolist() and out["no_key"].tolist() == [0, 0]
+        # neither the key pattern nor the number pattern has a hit: nothing runs, the statuses still say why there are no key rows
+        out = plain.number_stats_by_histogram_batch(*ia.pack_patterns([ia.as_chars("zzqq#")]), *ia.pack_patterns([ia.as_chars("zzqq%")]), [0],
+                                                    *ia.pack_patterns([]), [0], [], [-1], [-1], " \n", 32, None, 3)
+        assert out["key_row_off"].tolist() == [0, 0] and out["cell_off"].tolist() == [0, 0] and out["n_groups"].tolist() == [0]
+        assert (out["status"] == ST_NOT_ENABLED).all() and (out["key_status"] == ST_NOT_ENABLED).all()
+        assert out["kept"].tolist() == [0] == out["occurrences"].tolist() and out["no_key"].tolist() == [0]
     finally:
         mixed.close()
         bare.close()

@@ -678,6 +678,46 @@ int fmx_field_values_histogram_where_class_batch(const fmx_index *idx, const uin
                                                  int64_t **text_off, uint16_t **chars, int32_t **hist, int32_t *other, int32_t *occurrences,
                                                  int32_t *kept, int32_t *status, int32_t *term_status);
 
+/* DISTINCT VALUES PER BUCKET: THE NUMBER OF DIFFERENT VALUES OF A FIELD PER BUCKET OF LINES (timechart dc(user=); countDistinct,
+ * cardinality) and, beside it, THE VALUES SEEN FOR THE FIRST TIME in each bucket (new block ids, new error classes, new users per
+ * minute) — the host forms of fmx_values_of_hits_groups_dev and fmx_values_distinct_histogram_dev (below: the stage).  The arguments
+ * are fmx_field_values_histogram_where_batch's without top: the value patterns, terms, query_off, term_kind, q, where_of, stop,
+ * n_stop and max_len, and edges with n_edges (edges == NULL with n_edges == 0 means B = 1, every line; no line table is needed then
+ * unless a pattern asks for a query).  THE HITS OF THE CALL: with edges the filter's window of lines is [edges[0], edges[B]), so
+ * every kept hit has a bucket.  The value of a hit is fmx_field_values_batch's, exactly; a hit belongs to the line of its first
+ * character; the buckets follow the edge rules above.  Per pattern i:
+ *   distinct[i * B + b]    the number of different values among the kept hits of i in bucket b;
+ *   first_seen[i * B + b]  the number of values of i whose FIRST kept hit — the one with the smallest line, and therefore the
+ *                          smallest bucket — lies in bucket b;
+ *   n_values[i] (nullable), occurrences[i], kept[i], status[i] and term_status[t] as in fmx_field_values_histogram_where_batch.
+ * distinct and first_seen are the caller's n * B ints each: nothing is allocated, nothing is to be freed.  It follows that the sum
+ * over b of first_seen[i, b] is n_values[i]; first_seen <= distinct <= fmx_hit_histogram_where_batch's counter, elementwise, and
+ * distinct is 0 exactly where that counter is; max_b distinct[i, b] <= n_values[i] <= the sum over b of distinct[i, b]; without
+ * edges distinct[i] == first_seen[i] == n_values[i]; and distinct[i, b] is the number of rows of
+ * fmx_field_values_histogram_where_batch with top >= G_i whose hist[r, b] is positive.
+ * n * B pairs of ints come down, whatever the number of values is, and no value's text is filled.  Two waits beyond the filter's
+ * own: the kept offsets (they size the stages) and ONE read of the n + 1 group offsets.  Scratch:
+ * fmx_values_of_hits_groups_scratch_bytes and fmx_values_distinct_histogram_scratch_bytes per kept hit.  On an index built without
+ * extraction every status is FMX_ST_NOT_ENABLED and every counter is zero; occurrences and kept are still filled.
+ * FMX_ST_TOO_MANY_RANGES (class form) as in fmx_field_values_where_class_batch.  n == 0: FMX_OK, nothing is searched, term_status
+ * is zeroed.  FMX_E_ARG as fmx_field_values_histogram_where_batch (an index without a line table — see fmx_line_table_build — only
+ * when edges are given or a pattern asks for a query) and for (int64) n * B above 2^27; FMX_E_NO_DEVICE for a handle that is not
+ * resident.  A refused call stores nothing. */
+int fmx_distinct_values_histogram_where_batch(const fmx_index *idx, const uint16_t *pat, const int32_t *pat_off, int32_t n, const uint16_t *term_pat,
+                                              const int32_t *term_off, int32_t n_terms, const int32_t *query_off, const uint8_t *term_kind,
+                                              int32_t q, const int32_t *where_of, const int32_t *edges, int32_t n_edges, const uint16_t *stop,
+                                              int32_t n_stop, int32_t max_len, int32_t *distinct, int32_t *first_seen, int32_t *n_values,
+                                              int32_t *occurrences, int32_t *kept, int32_t *status, int32_t *term_status);
+/* ... with class patterns as value patterns and as terms, as fmx_field_values_where_class_batch; a position is one character of the
+ * pattern's length.  The values behind ALL spellings of a pattern make one answer. */
+int fmx_distinct_values_histogram_where_class_batch(const fmx_index *idx, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos,
+                                                    const int32_t *pat_off, int32_t n, const uint16_t *term_alt, const int32_t *term_pos_off,
+                                                    int32_t term_n_pos, const int32_t *term_off, int32_t n_terms, int32_t max_ranges,
+                                                    const int32_t *query_off, const uint8_t *term_kind, int32_t q, const int32_t *where_of,
+                                                    const int32_t *edges, int32_t n_edges, const uint16_t *stop, int32_t n_stop, int32_t max_len,
+                                                    int32_t *distinct, int32_t *first_seen, int32_t *n_values, int32_t *occurrences, int32_t *kept,
+                                                    int32_t *status, int32_t *term_status);
+
 /* THE LINES THAT MATCH A QUERY WITH TERMS ON NUMBERS (latency_ms >= 500; size in 0 .. 67108863; status in 500 .. 599) — the host
  * forms of the two packed stages + fmx_hits_in_number_range_dev (below: the stage) + fmx_query_lines_of_hits_dev.  They are
  * fmx_match_query_batch's calls and its definitions hold unchanged: the n TERMS, query_off, term_kind (ALL / ANY / NONE; a query of
@@ -1241,6 +1281,32 @@ size_t fmx_values_gather_rows_scratch_bytes(int32_t n, int64_t n_rows);
 int fmx_values_gather_rows_dev(const fmx_index *idx, int32_t n, const int64_t *val_off, int32_t top, int64_t max_units, const int32_t *d_row_group,
                                const int64_t *d_text_off, const uint16_t *d_chars, int64_t *d_row_text_off, uint16_t *d_row_chars, void *d_ws,
                                size_t ws_bytes, void *stream);
+/* DISTINCT VALUES PER BUCKET over device pointers (distinct, first_seen and the invariants:
+ * fmx_distinct_values_histogram_where_batch above), one stage on one stream behind fmx_values_of_hits_groups_dev; the caller reads
+ * that stage's n + 1 group offsets in front of it.  val_off, edges, the packed hits (d_hit_off, d_locs, n_hits) and d_group_of_hit
+ * are fmx_values_top_histogram_dev's; d_distinct and d_first_seen get n * B ints each, entries behind them keep the caller's
+ * values.  A slot that is no hit, a hit whose line lies in no bucket and a hit whose group is outside its pattern's groups (-1)
+ * count nowhere: the first_seen of a group without a hit in a bucket is 0 everywhere.
+ *   1. keys: a lane per slot finds its pattern, its line and its bucket as fmx_values_top_histogram_dev's step 2 does and makes the
+ *      key pattern | group | bucket, fm_bits(n) + fm_bits(max G_i) + fm_bits(B) bits: n * B <= 2^27 and G <= 2^31 - 1 keep it at 60
+ *      bits or below; what counts nowhere gets the pattern n, which sorts last;
+ *   2. sort: ONE rocPRIM radix sort over the bits in use;
+ *   3. heads: a lane per sorted slot; the head of a run of equal keys becomes (pattern | bucket) << 1 | (0 where it is the first
+ *      bucket of its (pattern, group), else 1), every other slot the pattern n;
+ *   4. sort: ONE rocPRIM radix sort over fm_bits(n) + fm_bits(B) + 1 bits;
+ *   5. counters: a lane per (pattern, bucket) takes three lower bounds over all slots.
+ * Integers only, no atomics; lanes go to slots and counters, never to patterns; the grids are fmx_hit_lines_geometry's;
+ * asynchronous on `stream`, nothing is allocated, nothing is synchronised beyond the staged host copy of the small arrays.  Nothing
+ * is tuned in this version.  Workspace: 32 bytes per slot and rocPRIM's.  n == 0: nothing is written; n_hits == 0: both outputs are
+ * zeroed.  FMX_E_ARG, before anything is launched or written: null or negative arguments, n_hits > 2^31 - 1, a val_off that does
+ * not start at 0, decreases or holds more than 2^31 - 1 groups, bad edges, (int64) n * B above 2^27, an index without a line table
+ * when edges are given, a workspace smaller than fmx_values_distinct_histogram_scratch_bytes says (which is 0 for an empty call or
+ * a shape the call refuses), a SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not
+ * resident. */
+size_t fmx_values_distinct_histogram_scratch_bytes(int32_t n, int64_t n_groups, int64_t n_hits, int32_t n_edges);
+int fmx_values_distinct_histogram_dev(const fmx_index *idx, int32_t n, const int64_t *val_off, const int32_t *edges, int32_t n_edges,
+                                      const int64_t *d_hit_off, const int32_t *d_locs, int64_t n_hits, const int32_t *d_group_of_hit,
+                                      int32_t *d_distinct, int32_t *d_first_seen, void *d_ws, size_t ws_bytes, void *stream);
 /* THE HITS WHOSE NUMBER LIES IN A RANGE over device pointers (ranged patterns, the value of a hit and when it passes:
  * fmx_match_query_number_batch above).  Packed hits (d_hit_off, d_locs, n_hits) of n patterns exactly as fmx_hits_in_lines_dev takes
  * them — d_hit_off[0] may be non-zero, slots behind d_hit_off[n] and beyond n_hits are no hits, the order is SA-row order — and the

@@ -1041,6 +1041,59 @@ public:
         return h;
     }
 
+    // the distinct values of a field per bucket of lines, dc over time (fmx.h "DISTINCT VALUES PER BUCKET"; timechart dc(user=)
+    // where line has ...): fieldValuesHistogramBatch's arguments without top.  distinct[i * B + b] = the different values among the
+    // kept hits of pattern i in bucket b; firstSeen[i * B + b] = the values of i whose first kept hit lies in bucket b.  Two ints per
+    // bucket come down, however many values there are.  Statuses are not thrown by the batch form; distinctValues answers one pattern
+    // and throws them.
+    struct DistinctValues {
+        int32_t buckets = 1;
+        std::vector<int32_t> distinct, firstSeen, nValues, occurrences, kept, status, termStatus;
+        std::vector<int32_t> distinctOf(size_t i) const { return {distinct.begin() + i * (size_t)buckets, distinct.begin() + (i + 1) * (size_t)buckets}; }
+        std::vector<int32_t> firstSeenOf(size_t i) const { return {firstSeen.begin() + i * (size_t)buckets, firstSeen.begin() + (i + 1) * (size_t)buckets}; }
+    };
+    DistinctValues distinctValuesBatch(const std::vector<std::u16string> &patterns, const std::vector<Query> &queries,
+                                       const std::vector<int32_t> &whereOf, const std::vector<int32_t> &edges = {},
+                                       const std::u16string &stop = u" ", int32_t maxLen = 64) const {
+        if (whereOf.size() != patterns.size()) throw std::invalid_argument("whereOf has one entry per pattern");
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        flattenQueries(queries, terms, kind, queryOff);
+        std::vector<uint16_t> chars, termChars;
+        std::vector<int32_t> off, termOff;
+        pack(patterns, chars, off);
+        pack(terms, termChars, termOff);
+        DistinctValues out;
+        const size_t n = patterns.size();
+        out.buckets = edges.empty() ? 1 : edges.size() > 1 ? (int32_t)edges.size() - 1 : 0;
+        for (std::vector<int32_t> *v : {&out.distinct, &out.firstSeen}) v->assign(n * (size_t)out.buckets + 1, 0);
+        for (std::vector<int32_t> *v : {&out.nValues, &out.occurrences, &out.kept, &out.status}) v->assign(n + 1, 0);
+        out.termStatus.assign(terms.size(), 0);
+        detail::check(fmx_distinct_values_histogram_where_batch(h_, chars.data(), off.data(), (int32_t)n, termChars.data(), termOff.data(),
+                                                                (int32_t)terms.size(), queryOff.data(), kind.data(), (int32_t)queries.size(),
+                                                                whereOf.data(), edges.empty() ? nullptr : edges.data(), (int32_t)edges.size(),
+                                                                reinterpret_cast<const uint16_t *>(stop.data()), (int32_t)stop.size(), maxLen,
+                                                                out.distinct.data(), out.firstSeen.data(), out.nValues.data(),
+                                                                out.occurrences.data(), out.kept.data(), out.status.data(), out.termStatus.data()),
+                      "fmx_distinct_values_histogram_where_batch");
+        for (std::vector<int32_t> *v : {&out.distinct, &out.firstSeen, &out.nValues, &out.occurrences, &out.kept, &out.status}) v->pop_back();
+        return out;
+    }
+    DistinctValues distinctValues(const std::u16string &pattern, const std::vector<int32_t> &edges = {}, const Query *where = nullptr,
+                                  const std::u16string &stop = u" ", int32_t maxLen = 64) const {
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        if (where)
+            for (const std::vector<std::u16string> *g : {&where->all, &where->any, &where->none})
+                for (const std::u16string &t : *g)
+                    if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const DistinctValues d = distinctValuesBatch({pattern}, where ? std::vector<Query>{*where} : std::vector<Query>{}, {where ? 0 : -1}, edges,
+                                                     stop, maxLen);
+        detail::raise_for_status(d.status[0]);
+        for (int st : d.termStatus) detail::raise_for_status(st);
+        return d;
+    }
+
     // the text of ranges and of lines in ONE packed array (fmx.h "THE TEXT OF RANGES AND LINES IN ONE PACKED ARRAY"): range / line
     // i is chars[offsets[i] .. offsets[i + 1]) — what extract(start, stop, destination, 0) leaves in destination; memory follows
     // the sum of the lengths.  status[i] is the range's own (not thrown: one range out of the text does not hide the others);

@@ -5,6 +5,7 @@ library holding the host-side index builder / serializer and the HIP kernels (cs
 CPU query path; the HIP library must be built (``__graft_entry__.build()``)."""
 from ._lib import FmxError, LIB_PATH, SYMBOLS, lib  # noqa: F401
 from .fmindex import (  # noqa: F401
+    DistinctValues,
     FieldValuesHistogram,
     FmIndex,
     FmIndexBuilder,
@@ -31,5 +32,5 @@ from . import bwt  # noqa: F401
 from .bwt import computeRedundancyOfText, createBurrowsWheelerTransform  # noqa: F401
 from .wavelet import WaveletFixedBlockBoosting  # noqa: F401
 
-__all__ = ["SuffixArray", "bwt", "createBurrowsWheelerTransform", "computeRedundancyOfText", "ReplicaSet", "SegmentReplicaSet", "shard_range", "WaveletFixedBlockBoosting", "RrrVector", "SegmentedFmIndex", "cut_points", "FmIndex", "FmIndexBuilder", "NumberStats", "NumberStatsBy", "NumberStatsByHistogram", "TopLines", "FieldValuesHistogram", "FmxError", "as_chars", "chars_to_str", "pack_patterns", "pack_class_patterns", "ignore_case", "parse_classes",
+__all__ = ["SuffixArray", "bwt", "createBurrowsWheelerTransform", "computeRedundancyOfText", "ReplicaSet", "SegmentReplicaSet", "shard_range", "WaveletFixedBlockBoosting", "RrrVector", "SegmentedFmIndex", "cut_points", "FmIndex", "FmIndexBuilder", "NumberStats", "NumberStatsBy", "NumberStatsByHistogram", "TopLines", "FieldValuesHistogram", "DistinctValues", "FmxError", "as_chars", "chars_to_str", "pack_patterns", "pack_class_patterns", "ignore_case", "parse_classes",
            "raise_for_status", "synth_log", "synth_log_multichar", "synth_patterns", "lib", "LIB_PATH", "SYMBOLS"]

@@ -357,4 +357,46 @@ int keyed_front_stage(const HitsBetween &h, KeyedArgs &a, const char *what, Keye
     return FMX_OK;
 }
 
+// n > 0 value patterns behind n_terms filter terms
+int groups_front_stage(const HitsBetween &h, GroupsArgs &a, bool units, const char *what, GroupsFront *f, bool *done) {
+    const hipStream_t st = static_cast<hipStream_t>(h.stream);
+    const int32_t n = h.n;
+    *done = true;
+    if (h.total - h.term_hits == 0)  // (no value pattern has a hit: nothing runs on the device)
+        return a.text.extract ? FMX_OK : status_all(h, FMX_ST_NOT_ENABLED, what);
+    int rc;
+    const int64_t *d_off = nullptr;
+    const int32_t *d_locs = nullptr;
+    int64_t slots = 0;
+    if ((rc = kept_hits_stage(h, a.filter, &d_off, &d_locs, &slots))) return rc;
+    FMX_HIP_TRY(hipMemcpyAsync(a.kept_off.data(), d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
+    FMX_HIP_TRY(hipStreamSynchronize(st));
+    if (!a.text.extract) return status_all(h, FMX_ST_NOT_ENABLED, what);
+    const int64_t K = a.kept_off[(size_t)n] - a.kept_off[0];
+    f->K = K;
+    if (K == 0) return FMX_OK;  // (no hit is kept: no groups)
+    if (K > 0x7fffffff) return api_fail(FMX_E_ARG, "more than 2^31 - 1 hits in one call");
+    auto block = [&](size_t bytes, auto **out) -> int { return h.block(h.call, bytes + 8, reinterpret_cast<void **>(out)); };
+    // the kept hits with offsets of their own that start at 0 (the host has them: no kernel), so that the values stage and the
+    // sorts of the caller's stage run over the K kept hits, not over every slot from the terms' first hit on
+    for (int32_t i = 0; i <= n; ++i) a.part_off[(size_t)i] = a.kept_off[(size_t)i] - a.kept_off[0];
+    int64_t *d_part_off = nullptr, *d_val_off = nullptr;
+    f->b_bytes = fmx_values_of_hits_groups_scratch_bytes(n, K, a.max_len);
+    if ((rc = block(((size_t)n + 1) * 8, &d_part_off)) || (rc = block(((size_t)n + 2) * 8, &d_val_off)) || (rc = block((size_t)K * 4, &f->count)) ||
+        (rc = block(((size_t)K + 1) * 8, &f->text_off)) || (rc = block((size_t)K * 4, &f->group)) || (rc = block(f->b_bytes, &f->ws_b)))
+        return rc;
+    FMX_HIP_TRY(hipMemcpyAsync(d_part_off, a.part_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    f->part_off = d_part_off;
+    f->locs = d_locs + a.kept_off[0];
+    if ((rc = fmx_values_of_hits_groups_dev(h.idx, n, a.term_len.data(), a.stop, a.n_stop, a.max_len, d_part_off, f->locs, K, d_val_off, f->count,
+                                            f->text_off, f->group, h.status, f->ws_b, f->b_bytes, st)))
+        return rc;
+    if (units)
+        if (const int e = launch_values_groups_units(d_val_off, n, f->text_off, d_val_off + n + 1, st)) return hip_fail(what, e);
+    FMX_HIP_TRY(hipMemcpyAsync(a.val_off.data(), d_val_off, ((size_t)n + (units ? 2 : 1)) * 8, hipMemcpyDeviceToHost, st));
+    FMX_HIP_TRY(hipStreamSynchronize(st));
+    *done = false;
+    return FMX_OK;
+}
+
 }  // namespace fmx

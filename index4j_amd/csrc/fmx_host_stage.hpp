@@ -298,4 +298,35 @@ struct KeyedFront {
 };
 int keyed_front_stage(const HitsBetween &h, KeyedArgs &a, const char *what, KeyedFront *f, bool *done);
 
+// ---- fmx_host_stage.cpp: the forms over the groups of the kept hits (top values per bucket, distinct values per bucket) -------------
+// what their stage needs of a call, and leaves on the host (arrived when the call has synchronised)
+struct GroupsArgs {
+    HitsFilter filter{};
+    TextView text{};
+    std::vector<int32_t> term_len;  // the value patterns'
+    const uint16_t *stop = nullptr;
+    int32_t n_stop = 0, max_len = 0;
+    std::vector<int64_t> kept_off, part_off, val_off;  // n + 1, n + 1, n + 2 (the units of the groups' text behind, where asked for)
+    void sized(int32_t n) {
+        kept_off.assign((size_t)n + 1, 0);
+        part_off.assign((size_t)n + 1, 0);
+        val_off.assign((size_t)n + 2, 0);
+    }
+};
+// the front half of their stages: the filter (kept_hits_stage), ONE read of the kept offsets, the kept block with offsets of its own
+// that start at 0, fmx_values_of_hits_groups_dev over it, ONE read of the n + 1 group offsets — with `units` the units of the groups'
+// text behind them (text_off[G], picked on the device).  It leaves a.kept_off, a.part_off, a.val_off, K and the device arrays below
+// (blocks of h.block).  *done: answered, nothing more to run — no value pattern has a hit, an index without extraction
+// (FMX_ST_NOT_ENABLED), or no hit is kept.
+struct GroupsFront {
+    int64_t K;                // the kept hits
+    const int64_t *part_off;  // n + 1: the kept block's own offsets, from 0
+    const int32_t *locs;
+    int32_t *count, *group;   // K slots each: the groups' counts, the group of every hit
+    int64_t *text_off;        // K + 1
+    void *ws_b;               // the values stage's workspace: fmx_values_fill_dev reads it
+    size_t b_bytes;
+};
+int groups_front_stage(const HitsBetween &h, GroupsArgs &a, bool units, const char *what, GroupsFront *f, bool *done);
+
 }  // namespace fmx

@@ -264,6 +264,18 @@ int launch_values_gather_rows(int n_cu, int32_t n, const int64_t *val_off, int32
                               const int64_t *text_off, const uint16_t *chars, int64_t *row_text_off, uint16_t *row_chars, void *ws,
                               size_t ws_bytes, void *stream);
 
+// fmx_distinct.hip — THE DISTINCT VALUES OF A FIELD PER BUCKET OF LINES (fmx_values_distinct_histogram_dev; fmx_distinct.hpp has the
+// definition).  Compiled once; the grids are hit_lines_geometry's; the launcher returns a hipError_t as int, `stream` is a
+// hipStream_t, nothing is synchronised or allocated.  val_off and edges are HOST arrays as launch_values_top_histogram takes them,
+// judged again (fm_dv_shape_bad) and copied into the workspace before the launcher returns; group_of_hit (n_hits ints) is
+// launch_values_groups_of_hits' over the same packed hits; distinct and first_seen: n * B ints each, nothing behind them.
+// hipErrorInvalidValue before anything is launched or written: too small a workspace, a shape outside the scratch-size function's
+// (which is 0 then), n * B beyond 2^27.  n <= 0 or n_hits <= 0: nothing is done.
+size_t values_distinct_histogram_scratch_bytes(int32_t n, int64_t n_groups, int64_t n_hits, int32_t n_edges);
+int launch_values_distinct_histogram(const int32_t *T, int32_t count, int n_cu, int32_t n, const int64_t *val_off, const int32_t *edges,
+                                     int32_t n_edges, const int64_t *hit_off, const int32_t *locs, int64_t n_hits, const int32_t *group_of_hit,
+                                     int32_t *distinct, int32_t *first_seen, void *ws, size_t ws_bytes, void *stream);
+
 // fmx_by_hist.hip — "STATS ... BY KEY" PER BUCKET OF LINES (fmx_numbers_by_key_buckets_dev; fmx_by_hist.hpp has the definition).
 // Compiled once; the grids are hit_lines_geometry's; the launchers return a hipError_t as int, `stream` is a hipStream_t, nothing is
 // synchronised or allocated.  term_len, by_of (n, each in [0, m)), val_off (m + 1: the key patterns' group offsets, stage b's answer

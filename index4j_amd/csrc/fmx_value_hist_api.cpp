@@ -3,9 +3,9 @@
 // over fmx_value_hist.hip's launchers, and the host forms fmx_field_values_histogram_where_batch /
 // fmx_field_values_histogram_where_class_batch.  Of a handle this file sees what fmx::line_view and fmx::text_view hand out; a host
 // form runs the packed sequence of fmx_api.cpp up to the stage of this file (fmx::hits_stage_call) over ONE merged batch terms |
-// value patterns, then the filter with the edges' span as its window (fmx::kept_hits_stage), fmx_values_of_hits_groups_dev over the
-// kept hits, ONE read of the group offsets and the size of the groups' text, the ranking and binning stage, the fill of the groups'
-// text, the gather of the rows' text and the copies down.
+// value patterns, then the filter with the edges' span as its window, fmx_values_of_hits_groups_dev over the kept hits and ONE
+// read of the group offsets and the size of the groups' text (fmx::groups_front_stage, the front half it shares with the distinct
+// values per bucket), the ranking and binning stage, the fill of the groups' text, the gather of the rows' text and the copies down.
 #include "fmx_host_stage.hpp"
 #include "fmx_value_hist.hpp"
 
@@ -51,16 +51,11 @@ int check_groups(int32_t n, const int64_t *val_off, const Shape &s, int64_t *row
 // the regions of the ONE allocation of the answer
 enum { kRowCount, kRowGroup, kTextOff, kChars, kHist };
 
-struct HistArgs {
-    fmx::HitsFilter filter{};
+struct HistArgs : fmx::GroupsArgs {
     Shape shape{};
-    fmx::TextView text{};
-    std::vector<int32_t> term_len;  // the value patterns'
-    const uint16_t *stop = nullptr;
-    int32_t n_stop = 0, max_len = 0;
     int32_t *other = nullptr;  // the caller's n * B ints, zeroed before the stage runs
-    // what the stage leaves (host; arrived when the call has synchronised)
-    std::vector<int64_t> kept_off, part_off, val_off, row_off;  // n + 1, n + 1, n + 2 (the units of the groups' text behind), n + 1
+    // what the stage leaves beside GroupsArgs' (host; arrived when the call has synchronised)
+    std::vector<int64_t> row_off;  // n + 1
     fmx::PackedResult result;
 };
 
@@ -70,40 +65,16 @@ int hist_stage(const fmx::HitsBetween &h, void *arg) {
     const hipStream_t st = static_cast<hipStream_t>(h.stream);
     const Shape &s = a.shape;
     const int32_t n = h.n;
-    if (h.total - h.term_hits == 0)  // (no value pattern has a hit: nothing runs on the device)
-        return a.text.extract ? FMX_OK : fmx::status_all(h, FMX_ST_NOT_ENABLED, "top values per bucket");
-    int rc;
-    const int64_t *d_off = nullptr;
-    const int32_t *d_locs = nullptr;
-    int64_t slots = 0;
-    if ((rc = fmx::kept_hits_stage(h, a.filter, &d_off, &d_locs, &slots))) return rc;
-    FMX_HIP_TRY(hipMemcpyAsync(a.kept_off.data(), d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
-    FMX_HIP_TRY(hipStreamSynchronize(st));
-    if (!a.text.extract) return fmx::status_all(h, FMX_ST_NOT_ENABLED, "top values per bucket");
-    const int64_t K = a.kept_off[(size_t)n] - a.kept_off[0];
-    if (K == 0) return FMX_OK;  // (no hit is kept: no groups, no rows, `other` stays zero)
-    if (K > 0x7fffffff) return api_fail(FMX_E_ARG, "more than 2^31 - 1 hits in one call");
+    int rc, e;
+    fmx::GroupsFront f{};
+    bool done = false;
+    if ((rc = fmx::groups_front_stage(h, a, true, "top values per bucket", &f, &done)) || done) return rc;  // (no hit is kept: `other` stays zero)
     auto block = [&](size_t bytes, auto **out) -> int { return h.block(h.call, bytes + 8, reinterpret_cast<void **>(out)); };
-    // the kept hits with offsets of their own that start at 0 (the host has them: no kernel), so that the values stage and the
-    // sorts of the new stage run over the K kept hits, not over every slot from the terms' first hit on
-    for (int32_t i = 0; i <= n; ++i) a.part_off[(size_t)i] = a.kept_off[(size_t)i] - a.kept_off[0];
-    int64_t *d_part_off = nullptr, *d_val_off = nullptr, *d_text_off = nullptr;
-    int32_t *d_count = nullptr, *d_group = nullptr;
-    void *ws_b = nullptr;
-    const size_t b_bytes = fmx_values_of_hits_groups_scratch_bytes(n, K, a.max_len);
-    if ((rc = block(((size_t)n + 1) * 8, &d_part_off)) || (rc = block(((size_t)n + 2) * 8, &d_val_off)) || (rc = block((size_t)K * 4, &d_count)) ||
-        (rc = block(((size_t)K + 1) * 8, &d_text_off)) || (rc = block((size_t)K * 4, &d_group)) || (rc = block(b_bytes, &ws_b)))
-        return rc;
-    FMX_HIP_TRY(hipMemcpyAsync(d_part_off, a.part_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-    const int32_t *d_klocs = d_locs + a.kept_off[0];
-    if ((rc = fmx_values_of_hits_groups_dev(h.idx, n, a.term_len.data(), a.stop, a.n_stop, a.max_len, d_part_off, d_klocs, K, d_val_off, d_count,
-                                            d_text_off, d_group, h.status, ws_b, b_bytes, st)))
-        return rc;
-    // ONE read: the n + 1 group offsets and, behind them, the units of the groups' text (text_off[G], picked on the device)
-    int e = fmx::launch_values_groups_units(d_val_off, n, d_text_off, d_val_off + n + 1, st);
-    if (e) return hip_fail("top values per bucket", e);
-    FMX_HIP_TRY(hipMemcpyAsync(a.val_off.data(), d_val_off, ((size_t)n + 2) * 8, hipMemcpyDeviceToHost, st));
-    FMX_HIP_TRY(hipStreamSynchronize(st));
+    const int64_t K = f.K;
+    const int64_t *d_part_off = f.part_off, *d_text_off = f.text_off;
+    const int32_t *d_klocs = f.locs, *d_count = f.count, *d_group = f.group;
+    void *ws_b = f.ws_b;
+    const size_t b_bytes = f.b_bytes;
     if ((rc = check_groups(n, a.val_off.data(), s, a.row_off.data()))) return rc;
     const size_t G = (size_t)a.val_off[(size_t)n], R = (size_t)a.row_off[(size_t)n], B = (size_t)s.B;
     const int64_t units = a.val_off[(size_t)n + 1];
@@ -194,9 +165,7 @@ int hist_call_args(const fmx_index *idx, const HistCall &c, HistArgs *a, bool *d
     a->n_stop = c.n_stop;
     a->max_len = c.max_len;
     a->other = c.other;
-    a->kept_off.assign((size_t)c.n + 1, 0);
-    a->part_off.assign((size_t)c.n + 1, 0);
-    a->val_off.assign((size_t)c.n + 2, 0);
+    a->sized(c.n);
     a->row_off.assign((size_t)c.n + 1, 0);
     return FMX_OK;
 }

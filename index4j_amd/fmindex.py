@@ -273,6 +273,15 @@ class FieldValuesHistogram:
         return {row["value"]: row for row in self.rows}
 
 
+class DistinctValues:
+    """pattern i of a distinct_values_histogram_where_batch answer: distinct (B ints: the different values among the kept hits of each
+    bucket), first_seen (B ints: the values whose first kept hit lies in the bucket), and n_values, kept, occurrences as ints"""
+
+    def __init__(self, out, i=0):
+        self.distinct, self.first_seen = out["distinct"][i].tolist(), out["first_seen"][i].tolist()
+        self.n_values, self.kept, self.occurrences = int(out["n_values"][i]), int(out["kept"][i]), int(out["occurrences"][i])
+
+
 class FmIndex:
     """fm/FmIndex.java query surface.  `device=None` keeps the index on the host (build / save /
     load only); any query then fails loudly."""
@@ -1180,6 +1189,52 @@ class FmIndex:
         return self._field_values_histogram_call(lib.fmx_field_values_histogram_where_class_batch, "fmx_field_values_histogram_where_class_batch",
                                                  head, n, n_terms, query_off, term_kind, where_of, edges, top, stop, max_len)
 
+    # ---- the distinct values of a field per bucket of lines, dc over time (fmx.h "DISTINCT VALUES PER BUCKET") ----
+    def _distinct_values_histogram_call(self, call, name, head, n, n_terms, query_off, term_kind, where_of, edges, stop, max_len):
+        query_off, term_kind, where_of, q, _, _ = self._where_arrays(n, n_terms, query_off, term_kind, where_of, None)
+        if edges is None:
+            edges_ptr, n_edges, B = None, 0, 1
+        else:
+            edges, B = self._edges(edges)
+            edges_ptr, n_edges = edges.ctypes.data, len(edges)
+        stop = as_chars(stop)
+        n_values, occurrences, kept, status = (np.zeros(n, dtype=np.int32) for _ in range(4))
+        distinct, first_seen = np.zeros((n, B), dtype=np.int32), np.zeros((n, B), dtype=np.int32)
+        term_status = np.zeros(n_terms, dtype=np.int32)
+        check(call(self._h, *head, query_off.ctypes.data, term_kind.ctypes.data, q, where_of.ctypes.data, edges_ptr, n_edges, stop.ctypes.data,
+                   len(stop), int(max_len), distinct.ctypes.data, first_seen.ctypes.data, n_values.ctypes.data, occurrences.ctypes.data,
+                   kept.ctypes.data, status.ctypes.data, term_status.ctypes.data), name)
+        return dict(distinct=distinct, first_seen=first_seen, n_values=n_values, occurrences=occurrences, kept=kept, status=status,
+                    term_status=term_status)
+
+    def distinct_values_histogram_where_batch(self, chars, offsets, term_chars, term_offsets, query_off, term_kind, where_of, edges=None, stop=" ",
+                                              max_len=64):
+        """the number of different values that follow every pattern per bucket of lines, and the number of values seen for the first
+        time in each bucket (fmx_distinct_values_histogram_where_batch; timechart dc(user=) where line has ...):
+        field_values_histogram_where_batch's arguments without top.  With edges only the hits inside edges[0] .. edges[B] count;
+        edges None: one bucket, every line.  Returns a dict of arrays: distinct (n, B), first_seen (n, B), n_values, occurrences, kept,
+        status (n), term_status.  n * B pairs of ints come down, however many values a pattern has."""
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        term_chars = np.ascontiguousarray(term_chars, dtype=np.uint16)
+        term_offsets = np.ascontiguousarray(term_offsets, dtype=np.int32)
+        n, n_terms = len(offsets) - 1, len(term_offsets) - 1
+        head = (chars.ctypes.data, offsets.ctypes.data, n, term_chars.ctypes.data, term_offsets.ctypes.data, n_terms)
+        return self._distinct_values_histogram_call(lib.fmx_distinct_values_histogram_where_batch, "fmx_distinct_values_histogram_where_batch", head,
+                                                    n, n_terms, query_off, term_kind, where_of, edges, stop, max_len)
+
+    def distinct_values_histogram_where_class_batch(self, alt, pos_off, pat_off, term_alt, term_pos_off, term_pat_off, query_off, term_kind,
+                                                    where_of, edges=None, stop=" ", max_len=64, max_ranges=CLASS_RANGES_DEFAULT):
+        """distinct_values_histogram_where_batch with class patterns as value patterns and as terms
+        (fmx_distinct_values_histogram_where_class_batch): the values behind ALL spellings of a pattern make one answer; same returns"""
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        term_alt, term_pos_off, term_pat_off, term_n_pos, n_terms = self._class_arrays(term_alt, term_pos_off, term_pat_off)
+        head = (alt.ctypes.data, pos_off.ctypes.data, n_pos, pat_off.ctypes.data, n, term_alt.ctypes.data, term_pos_off.ctypes.data, term_n_pos,
+                term_pat_off.ctypes.data, n_terms, int(max_ranges))
+        return self._distinct_values_histogram_call(lib.fmx_distinct_values_histogram_where_class_batch,
+                                                    "fmx_distinct_values_histogram_where_class_batch", head, n, n_terms, query_off, term_kind,
+                                                    where_of, edges, stop, max_len)
+
     def extract_batch(self, starts, stops, dst_len, offset=0, dst=None, want_steps=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         stops = np.ascontiguousarray(stops, dtype=np.int32)
@@ -1664,6 +1719,34 @@ class FmIndex:
         for st in [out["status"][0]] + out["term_status"].tolist():
             raise_for_status(st)
         return FieldValuesHistogram(out, 0)
+
+    def distinct_values(self, pattern, edges=None, where=None, stop=" ", max_len=64, ignore_case=False):
+        """how many different values follow `pattern` per bucket of lines, and how many of them are seen for the first time there:
+        timechart dc(user=) where line has ..., new block ids per minute.  edges as in hit_histogram (None: one bucket, every line);
+        where=dict(all=, any=, none=) as in field_values.  Returns a DistinctValues: distinct and first_seen (B ints each), n_values,
+        kept, occurrences.  Two ints per bucket come down, however many distinct values there are."""
+        p = as_chars(pattern)
+        terms, kinds = [], []
+        for kind, word in enumerate(("all", "any", "none")):
+            group = (where or {}).get(word, ())
+            for t in ([group] if isinstance(group, str) else group):  # (a lone str is one term)
+                terms.append(as_chars(t))
+                kinds.append(kind)
+        if where is not None and set(where) - {"all", "any", "none"}:
+            raise ValueError("where takes all=, any= and none=")
+        if min((len(t) for t in terms + [p]), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        query_off, where_of = ([0, len(terms)], [0]) if where is not None else ([0], [-1])
+        if ignore_case:
+            out = self.distinct_values_histogram_where_class_batch(*pack_class_patterns([_ignore_case(p)]),
+                                                                   *pack_class_patterns([_ignore_case(t) for t in terms]), query_off,
+                                                                   np.array(kinds, np.uint8), where_of, edges, stop, max_len)
+        else:
+            out = self.distinct_values_histogram_where_batch(*pack_patterns([p]), *pack_patterns(terms), query_off, np.array(kinds, np.uint8),
+                                                             where_of, edges, stop, max_len)
+        for st in [out["status"][0]] + out["term_status"].tolist():
+            raise_for_status(st)
+        return DistinctValues(out, 0)
 
     def line_text(self, lines):
         """the lines with these ids as a list of str (the boundary excluded); raises for an id that is no line"""

@@ -570,6 +570,60 @@ int fmx_number_stats_by_class_batch(const fmx_index *idx, const uint16_t *key_al
                                     int32_t *kept, int32_t *status, int32_t *key_occurrences, int32_t *key_kept, int32_t *key_status,
                                     int32_t *term_status);
 
+/* STATISTICS BY TWO KEYS: THE NUMBER BEHIND A PATTERN, AND THE LINES, GROUPED BY THE VALUES OF TWO FIELDS OF THE SAME LINE (stats
+ * p95(latency_ms=) by host=, status=; the pivot table count by host=, status=) — the host form of stages a and b of STATISTICS BY
+ * KEY, fmx_pairs_of_first_hits_dev and fmx_numbers_by_key_dev (below).  The arguments are fmx_number_stats_by_batch's — the m key
+ * patterns, the n number patterns, the terms, query_off, term_kind, q, key_where_of, where_of, the window of lines, stop / n_stop /
+ * max_len, frac_digits, permille / n_permille — plus n_pairs = c PAIRS pair_a[j], pair_b[j], each in [0, m) and the two may be
+ * equal; by_of[i] in [0, c) names the PAIR number pattern i is grouped by.
+ * THE GROUPS of the key patterns — val_off, *lines, *text_off, *chars — are fmx_number_stats_by_batch's, so a pair is printed as two
+ * values.  Line L has a PAIR KEY for pair j iff it has a key for pair_a[j] and one for pair_b[j]: (ga, gb), the two groups' indexes
+ * among their key patterns' groups.  THE PAIRS of j are the distinct (ga, gb) of its lines, ascending by ga, then gb: pair_off (c + 1
+ * int64, out), entry r of pair j at pair_off[j] + r of (*pair_group_a), (*pair_group_b) and (*pair_lines) = the lines that have it
+ * (at least 1).  The lines of j's pairs add up to the lines with both keys; a pair (k, k) has the pairs (g, g) with pair_lines =
+ * lines.
+ * THE ROWS are packed: row_off (n + 1 int64, out), row_off[i + 1] - row_off[i] = the pairs of by_of[i]; row (i, r) at row_off[i] + r
+ * is over the kept hits of number pattern i whose line has pair r and that parse: (*count) .. (*pct) as fmx_number_stats_by_batch.
+ * no_key[i] = the kept hits of i on a line without a pair key, decided before parsing and counted there and nowhere else;
+ * not_number[i], overflow[i] as there.  For every i
+ *     sum over r of count[row_off[i] + r] + no_key[i] + not_number[i] + overflow[i] = kept[i].
+ * occurrences .. term_status as fmx_number_stats_by_batch.  *lines, *text_off, *chars, *pair_group_a, *pair_group_b, *pair_lines,
+ * *count .. *pct point into ONE allocation owned by the library until fmx_free_buffer((uint8_t *)*lines); all are NULL when there is
+ * no group (and on every failure).
+ * n == 0 IS A REAL CALL: the groups, the pairs and their lines (count by a, b); no number stage runs.  m == 0 (then n_pairs and n
+ * must be 0): FMX_OK, nothing is searched.  No kept key hit: no groups, no pairs, no_key[i] = kept[i].  No pair at all: the groups
+ * are reported, no rows, no_key[i] = kept[i].  No kept number hit: the pairs with zero rows.  An index without extraction: as
+ * fmx_number_stats_by_batch (FMX_ST_NOT_ENABLED).  The line table is always required.
+ * The waits are fmx_number_stats_by_batch's and ONE more 8 * (c + 1)-byte read of the pair offsets, which sizes the rows.
+ * FMX_E_ARG as fmx_number_stats_by_batch, with the pairs in the place of the key patterns for by_of and the rows' limits, and for a
+ * pair_a / pair_b outside [0, m), n_pairs > 0 with m == 0, n > 0 with n_pairs == 0, more than 2^31 - 1 kept hits of the a-sides,
+ * fm_bits(c) + fm_bits(the most groups of an a-side) + fm_bits(the most groups of a b-side) > 64 (fm_bits(v): the bits of v, at
+ * least 1). */
+int fmx_number_stats_by_pair_batch(const fmx_index *idx, const uint16_t *key_pat, const int32_t *key_off, int32_t m, const uint16_t *pat,
+                                   const int32_t *pat_off, int32_t n, const int32_t *by_of, int32_t n_pairs, const int32_t *pair_a,
+                                   const int32_t *pair_b, const uint16_t *term_pat, const int32_t *term_off, int32_t n_terms, const int32_t *query_off,
+                                   const uint8_t *term_kind, int32_t q, const int32_t *key_where_of, const int32_t *where_of, int32_t line_lo,
+                                   int32_t line_hi, const uint16_t *stop, int32_t n_stop, int32_t max_len, int32_t frac_digits, const int32_t *permille,
+                                   int32_t n_permille, int64_t *val_off, int32_t **lines, int64_t **text_off, uint16_t **chars, int64_t *pair_off,
+                                   int32_t **pair_group_a, int32_t **pair_group_b, int32_t **pair_lines, int64_t *row_off, int32_t **count,
+                                   uint64_t **sum_lo, uint64_t **sum_hi, int64_t **min, int64_t **max, int64_t **pct, int32_t *no_key,
+                                   int32_t *not_number, int32_t *overflow, int32_t *occurrences, int32_t *kept, int32_t *status,
+                                   int32_t *key_occurrences, int32_t *key_kept, int32_t *key_status, int32_t *term_status);
+/* ... with class patterns as key patterns, as number patterns and as terms, each batch as fmx_number_stats_by_class_batch takes its
+ * own; its refusals of a class batch */
+int fmx_number_stats_by_pair_class_batch(const fmx_index *idx, const uint16_t *key_alt, const int32_t *key_pos_off, int32_t key_n_pos,
+                                         const int32_t *key_off, int32_t m, const uint16_t *alt, const int32_t *pos_off, int32_t n_pos,
+                                         const int32_t *pat_off, int32_t n, const int32_t *by_of, int32_t n_pairs, const int32_t *pair_a,
+                                         const int32_t *pair_b, const uint16_t *term_alt, const int32_t *term_pos_off, int32_t term_n_pos,
+                                         const int32_t *term_off, int32_t n_terms, int32_t max_ranges, const int32_t *query_off,
+                                         const uint8_t *term_kind, int32_t q, const int32_t *key_where_of, const int32_t *where_of, int32_t line_lo,
+                                         int32_t line_hi, const uint16_t *stop, int32_t n_stop, int32_t max_len, int32_t frac_digits,
+                                         const int32_t *permille, int32_t n_permille, int64_t *val_off, int32_t **lines, int64_t **text_off,
+                                         uint16_t **chars, int64_t *pair_off, int32_t **pair_group_a, int32_t **pair_group_b, int32_t **pair_lines,
+                                         int64_t *row_off, int32_t **count, uint64_t **sum_lo, uint64_t **sum_hi, int64_t **min, int64_t **max,
+                                         int64_t **pct, int32_t *no_key, int32_t *not_number, int32_t *overflow, int32_t *occurrences, int32_t *kept,
+                                         int32_t *status, int32_t *key_occurrences, int32_t *key_kept, int32_t *key_status, int32_t *term_status);
+
 /* STATISTICS BY KEY PER BUCKET: THE NUMBER BEHIND A PATTERN, BY THE VALUE OF A FIELD OF THE SAME LINE, PER BUCKET OF LINES (timechart
  * p95(latency_ms=) by status=: the top few values, each with its statistics per bucket, plus "other") — the host form of stages a
  * and b of STATISTICS BY KEY and fmx_numbers_by_key_buckets_dev (below).  The arguments are fmx_number_stats_by_batch's, word for
@@ -1192,6 +1246,36 @@ int fmx_numbers_by_key_dev(const fmx_index *idx, int32_t n, const int32_t *term_
                            int32_t n_permille, int64_t *d_row_off, int32_t *d_count, uint64_t *d_sum_lo, uint64_t *d_sum_hi, int64_t *d_min,
                            int64_t *d_max, int64_t *d_pct, int32_t *d_no_key, int32_t *d_not_number, int32_t *d_overflow, int32_t *d_status,
                            void *d_ws, size_t ws_bytes, void *stream);
+/* STATISTICS BY TWO KEYS over device pointers (the pair key, the pairs and the invariants: fmx_number_stats_by_pair_batch above):
+ * ONE join stage on one stream between stages b and c of STATISTICS BY KEY.  fmx_pairs_of_first_hits_dev takes stage a's
+ * d_first_off (m + 1) and d_first_lines and stage b's d_group_of_hit over them as d_group_of_first; val_off (m + 1: stage b's
+ * d_val_off, read by the caller), pair_a and pair_b (n_pairs = c, each in [0, m)) are HOST arrays: validated, and copied into d_ws
+ * before the call returns.  n_slots: the caller's upper bound of the first hits of the a-sides, pair_a[0] .. pair_a[c - 1], added
+ * up (the kept hits of those key patterns will do).  Outputs: d_pair_off (c + 1 int64); d_pair_group_a, d_pair_group_b, d_pair_lines
+ * (entry r of pair j at d_pair_off[j] + r; room for n_slots each, entries behind d_pair_off[c] keep the caller's values); and THE
+ * JOINED LISTS in the form of the inputs: d_joined_off (c + 1 int64), d_joined_lines (per pair the lines with a pair key,
+ * ascending) and d_joined_group (the index of that line's pair among the pairs of j), room for n_slots each, entries behind
+ * d_joined_off[c] keep the caller's values.  fmx_numbers_by_key_dev takes the joined lists as (d_first_off, d_first_lines,
+ * d_group_of_first) with m := c and val_off := d_pair_off, read by the caller; by_of then names pairs.
+ * A lane per a-side slot finds its pair in the slots' offsets (runs of equal offsets: a pair whose a-side is empty) and takes ONE
+ * lower bound of its line in the b-side's first lines; its key is pair | ga | gb, a slot without a partner and every slot behind
+ * the real ones gets a key that sorts last; ONE stable rocPRIM radix sort of (key, slot) over the bits in use; a lane per sorted
+ * slot flags the head of a run of equal keys; a scan; a head stores ga, gb and the run's length (a binary search: no lane's work
+ * grows with the lines of a pair); a lane per sorted slot writes its pair's index back to its slot; a scan and a stable
+ * compaction over the slots in their original order leave the joined lists.  Integers only, no atomics; the grids are
+ * fmx_hit_lines_geometry's over n_slots; asynchronous on `stream`, nothing is allocated, nothing is synchronised beyond the staged
+ * host copy of the small arrays.  About 40 bytes of workspace per slot.  n_pairs == 0: nothing is written; n_slots == 0: d_pair_off
+ * and d_joined_off are zeroed.  No line table is needed.
+ * FMX_E_ARG, before anything is launched or written and before the handle is asked for its device: null or negative arguments, a
+ * pair_a / pair_b outside [0, m), n_pairs > 0 with m == 0, a val_off that starts below 0, decreases or holds more than 2^31 - 1
+ * groups of one key pattern, n_slots > 2^31 - 1, fm_bits(c) + fm_bits(the most groups of an a-side) + fm_bits(the most groups of a
+ * b-side) > 64, a workspace smaller than fmx_pairs_of_first_hits_scratch_bytes says (which is 0 for an empty call or a shape the
+ * call refuses); then a SuffixArray / RrrVector / stand-alone wavelet handle; FMX_E_NO_DEVICE for a handle that is not resident. */
+size_t fmx_pairs_of_first_hits_scratch_bytes(int32_t m, int32_t n_pairs, int64_t n_slots);
+int fmx_pairs_of_first_hits_dev(const fmx_index *idx, int32_t m, const int64_t *val_off, int32_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                                const int64_t *d_first_off, const int32_t *d_first_lines, const int32_t *d_group_of_first, int64_t n_slots,
+                                int64_t *d_pair_off, int32_t *d_pair_group_a, int32_t *d_pair_group_b, int32_t *d_pair_lines, int64_t *d_joined_off,
+                                int32_t *d_joined_lines, int32_t *d_joined_group, void *d_ws, size_t ws_bytes, void *stream);
 /* STATISTICS BY KEY PER BUCKET over device pointers (the key rows, the cells and the invariants:
  * fmx_number_stats_by_histogram_batch above): ONE stage on one stream behind stages a and b of STATISTICS BY KEY; the caller reads
  * stage b's m + 1 group offsets in front of it.  Integers only, no atomics, no hashes — the results do not depend on scheduling;

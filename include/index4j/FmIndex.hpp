@@ -872,6 +872,107 @@ public:
         return s;
     }
 
+    // ... GROUPED BY THE VALUES OF TWO FIELDS of the same line (fmx.h "STATISTICS BY TWO KEYS"; stats p95(latency_ms=) by host=,
+    // status=): pair j is (pairA[j], pairB[j]), two of the key patterns, and byOf[i] names the PAIR number pattern i is grouped by.  The
+    // groups (valOff, values, lines) are the single keys', as numberStatsByBatch returns them; the pairs of j are pairOff[j] ..
+    // pairOff[j + 1]: pairGroupA[r] and pairGroupB[r] index the groups of the two key patterns (values[valOff[pairA[j]] +
+    // pairGroupA[r]] is a's value), pairLines[r] = the lines that have the pair.  The rows run over the pairs of byOf[i], row (i, r) at
+    // rowOff[i] + r.  Without a number pattern the call answers the pairs and their lines: fieldValuePairs is that call.
+    struct NumberStatsByPair : NumberStatsBy {
+        std::vector<int32_t> pairA, pairB;
+        std::vector<int64_t> pairOff;
+        std::vector<int32_t> pairGroupA, pairGroupB, pairLines;
+        // the two values of packed pair r of pair j
+        std::pair<std::u16string, std::u16string> pairValues(size_t j, size_t r) const {
+            return {values[(size_t)valOff[(size_t)pairA[j]] + (size_t)pairGroupA[r]], values[(size_t)valOff[(size_t)pairB[j]] + (size_t)pairGroupB[r]]};
+        }
+    };
+    NumberStatsByPair numberStatsByPairBatch(const std::vector<std::u16string> &patterns, const std::vector<std::u16string> &keys,
+                                             const std::vector<int32_t> &byOf, const std::vector<int32_t> &pairA, const std::vector<int32_t> &pairB,
+                                             const std::u16string &stop, int32_t maxLen, const std::vector<Query> &queries,
+                                             const std::vector<int32_t> &keyWhereOf, const std::vector<int32_t> &whereOf,
+                                             const std::vector<int32_t> &permille = {500, 950}, int32_t fracDigits = 0, int32_t lineLo = 0,
+                                             int32_t lineHi = INT32_MAX) const {
+        if (whereOf.size() != patterns.size() || byOf.size() != patterns.size()) throw std::invalid_argument("whereOf and byOf have one entry per pattern");
+        if (keyWhereOf.size() != keys.size()) throw std::invalid_argument("keyWhereOf has one entry per key pattern");
+        if (pairA.size() != pairB.size()) throw std::invalid_argument("pairA and pairB have one entry per pair");
+        std::vector<std::u16string> terms;
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> queryOff{0};
+        flattenQueries(queries, terms, kind, queryOff);
+        std::vector<uint16_t> chars, keyChars, termChars;
+        std::vector<int32_t> off, keyOff, termOff;
+        pack(patterns, chars, off);
+        pack(keys, keyChars, keyOff);
+        pack(terms, termChars, termOff);
+        NumberStatsByPair out;
+        const size_t n = patterns.size(), m = keys.size(), c = pairA.size(), P = permille.size();
+        out.permilles = (int32_t)P;
+        out.pairA = pairA;
+        out.pairB = pairB;
+        out.valOff.assign(m + 1, 0);
+        out.pairOff.assign(c + 1, 0);
+        out.rowOff.assign(n + 1, 0);
+        for (std::vector<int32_t> *v : {&out.noKey, &out.notNumber, &out.overflow, &out.occurrences, &out.kept, &out.status}) v->assign(n + 1, 0);
+        for (std::vector<int32_t> *v : {&out.keyOccurrences, &out.keyKept, &out.keyStatus}) v->assign(m + 1, 0);
+        out.termStatus.assign(terms.size(), 0);
+        int32_t *lines = nullptr, *count = nullptr, *groupA = nullptr, *groupB = nullptr, *pairLines = nullptr;
+        int64_t *textOff = nullptr, *vmin = nullptr, *vmax = nullptr, *pct = nullptr;
+        uint64_t *sumLo = nullptr, *sumHi = nullptr;
+        uint16_t *text = nullptr;
+        detail::check(fmx_number_stats_by_pair_batch(h_, keyChars.data(), keyOff.data(), (int32_t)m, chars.data(), off.data(), (int32_t)n, byOf.data(),
+                                                     (int32_t)c, pairA.data(), pairB.data(), termChars.data(), termOff.data(), (int32_t)terms.size(),
+                                                     queryOff.data(), kind.data(), (int32_t)queries.size(), keyWhereOf.data(), whereOf.data(), lineLo,
+                                                     lineHi, reinterpret_cast<const uint16_t *>(stop.data()), (int32_t)stop.size(), maxLen, fracDigits,
+                                                     permille.data(), (int32_t)P, out.valOff.data(), &lines, &textOff, &text, out.pairOff.data(), &groupA,
+                                                     &groupB, &pairLines, out.rowOff.data(), &count, &sumLo, &sumHi, &vmin, &vmax, &pct, out.noKey.data(),
+                                                     out.notNumber.data(), out.overflow.data(), out.occurrences.data(), out.kept.data(), out.status.data(),
+                                                     out.keyOccurrences.data(), out.keyKept.data(), out.keyStatus.data(), out.termStatus.data()),
+                      "fmx_number_stats_by_pair_batch");
+        const size_t G = (size_t)out.valOff[m], R = (size_t)out.rowOff[n], pairs = (size_t)out.pairOff[c];
+        if (lines) {  // the ONE allocation: copied, then handed back
+            out.lines.assign(lines, lines + G);
+            for (size_t g = 0; g < G; ++g)
+                out.values.emplace_back(reinterpret_cast<const char16_t *>(text) + textOff[g], (size_t)(textOff[g + 1] - textOff[g]));
+            out.pairGroupA.assign(groupA, groupA + pairs);
+            out.pairGroupB.assign(groupB, groupB + pairs);
+            out.pairLines.assign(pairLines, pairLines + pairs);
+            out.count.assign(count, count + R);
+            out.sumLo.assign(sumLo, sumLo + R);
+            out.sumHi.assign(sumHi, sumHi + R);
+            out.min.assign(vmin, vmin + R);
+            out.max.assign(vmax, vmax + R);
+            out.pct.assign(pct, pct + R * P);
+            fmx_free_buffer(reinterpret_cast<uint8_t *>(lines));
+        }
+        for (std::vector<int32_t> *v : {&out.noKey, &out.notNumber, &out.overflow, &out.occurrences, &out.kept, &out.status, &out.keyOccurrences,
+                                        &out.keyKept, &out.keyStatus})
+            v->pop_back();
+        return out;
+    }
+    // one number pattern by the pair (byA, byB); the rows are in pair order: ascending by a's value, then b's
+    NumberStatsByPair numberStatsByPair(const std::u16string &pattern, const std::u16string &byA, const std::u16string &byB,
+                                        const std::u16string &stop = u" \t\r\n", int32_t maxLen = 32, const Query *where = nullptr,
+                                        const std::vector<int32_t> &permille = {500, 950}, int32_t fracDigits = 0) const {
+        if (pattern.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        return byPair({pattern}, byA, byB, stop, maxLen, where, permille, fracDigits);
+    }
+    // the pivot table count by a, b: (a's value, b's value, the lines that have both) in pair order
+    struct ValuePair {
+        std::u16string a, b;
+        int32_t lines;
+    };
+    std::vector<ValuePair> fieldValuePairs(const std::u16string &byA, const std::u16string &byB, const std::u16string &stop = u" \t\r\n",
+                                           int32_t maxLen = 32, const Query *where = nullptr) const {
+        const NumberStatsByPair s = byPair({}, byA, byB, stop, maxLen, where, {}, 0);
+        std::vector<ValuePair> out;
+        for (size_t r = 0; r < s.pairLines.size(); ++r) {
+            const auto v = s.pairValues(0, r);
+            out.push_back(ValuePair{v.first, v.second, s.pairLines[r]});
+        }
+        return out;
+    }
+
     // ... per bucket of lines (fmx.h "STATISTICS BY KEY PER BUCKET"; timechart p95(latency_ms=) by status=): numberStatsByBatch's
     // patterns, keys, byOf, stop, maxLen, queries, keyWhereOf and whereOf, hitHistogramWhereBatch's edges — none at all: one bucket,
     // every line, the device-side top-k of numberStatsBy; with edges only the hits inside edges[0] .. edges[B] count — and top.  The
@@ -1248,6 +1349,23 @@ private:
             queryOff.push_back((int32_t)terms.size());
         }
         kind.push_back(0);
+    }
+    // numberStatsByPairBatch for the one pair (byA, byB) and at most one number pattern, the statuses thrown
+    NumberStatsByPair byPair(const std::vector<std::u16string> &patterns, const std::u16string &byA, const std::u16string &byB, const std::u16string &stop,
+                             int32_t maxLen, const Query *where, const std::vector<int32_t> &permille, int32_t fracDigits) const {
+        if (byA.empty() || byB.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        if (where)
+            for (const std::vector<std::u16string> *g : {&where->all, &where->any, &where->none})
+                for (const std::u16string &t : *g)
+                    if (t.empty()) throw std::out_of_range("ArrayIndexOutOfBoundsException");
+        const int32_t w = where ? 0 : -1;
+        const NumberStatsByPair s =
+            numberStatsByPairBatch(patterns, {byA, byB}, std::vector<int32_t>(patterns.size(), 0), {0}, {1}, stop, maxLen,
+                                   where ? std::vector<Query>{*where} : std::vector<Query>{}, {w, w}, std::vector<int32_t>(patterns.size(), w), permille, fracDigits);
+        for (int st : s.status) detail::raise_for_status(st);
+        for (int st : s.keyStatus) detail::raise_for_status(st);
+        for (int st : s.termStatus) detail::raise_for_status(st);
+        return s;
     }
     // the three packed arrays of a batch of class patterns (fmx_count_class_batch)
     static FieldValues emptyFieldValues(size_t n) {

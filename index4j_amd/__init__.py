@@ -12,6 +12,7 @@ from .fmindex import (  # noqa: F401
     NumberStats,
     NumberStatsBy,
     NumberStatsByHistogram,
+    NumberStatsByPair,
     TopLines,
     as_chars,
     chars_to_str,
@@ -32,5 +33,5 @@ from . import bwt  # noqa: F401
 from .bwt import computeRedundancyOfText, createBurrowsWheelerTransform  # noqa: F401
 from .wavelet import WaveletFixedBlockBoosting  # noqa: F401
 
-__all__ = ["SuffixArray", "bwt", "createBurrowsWheelerTransform", "computeRedundancyOfText", "ReplicaSet", "SegmentReplicaSet", "shard_range", "WaveletFixedBlockBoosting", "RrrVector", "SegmentedFmIndex", "cut_points", "FmIndex", "FmIndexBuilder", "NumberStats", "NumberStatsBy", "NumberStatsByHistogram", "TopLines", "FieldValuesHistogram", "DistinctValues", "FmxError", "as_chars", "chars_to_str", "pack_patterns", "pack_class_patterns", "ignore_case", "parse_classes",
+__all__ = ["SuffixArray", "bwt", "createBurrowsWheelerTransform", "computeRedundancyOfText", "ReplicaSet", "SegmentReplicaSet", "shard_range", "WaveletFixedBlockBoosting", "RrrVector", "SegmentedFmIndex", "cut_points", "FmIndex", "FmIndexBuilder", "NumberStats", "NumberStatsBy", "NumberStatsByHistogram", "NumberStatsByPair", "TopLines", "FieldValuesHistogram", "DistinctValues", "FmxError", "as_chars", "chars_to_str", "pack_patterns", "pack_class_patterns", "ignore_case", "parse_classes",
            "raise_for_status", "synth_log", "synth_log_multichar", "synth_patterns", "lib", "LIB_PATH", "SYMBOLS"]

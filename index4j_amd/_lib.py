@@ -28,8 +28,8 @@ SYMBOLS = [
     "fmx_build", "fmx_build_on_device", "fmx_build_wavelet_seconds", "fmx_suffix_table_info", "fmx_window_cells_info", "fmx_locate_rows_info", "fmx_load", "fmx_save", "fmx_save_key_order_modelled", "fmx_free_buffer", "fmx_free",
     "fmx_input_length", "fmx_alphabet_length", "fmx_sample_rate", "fmx_extract_enabled",
     "fmx_blob", "fmx_to_device", "fmx_attach_device_blob", "fmx_device_blob", "fmx_host_register", "fmx_host_unregister",
-    "fmx_count_batch", "fmx_locate_batch", "fmx_locate_all_batch", "fmx_match_lines_batch", "fmx_match_query_batch", "fmx_count_class_batch", "fmx_locate_all_class_batch", "fmx_match_query_class_batch", "fmx_match_sequence_batch", "fmx_match_sequence_class_batch", "fmx_field_values_batch", "fmx_field_values_class_batch", "fmx_field_values_where_batch", "fmx_field_values_where_class_batch", "fmx_line_histogram_batch", "fmx_line_histogram_class_batch", "fmx_hit_histogram_where_batch", "fmx_hit_histogram_where_class_batch", "fmx_number_stats_where_batch", "fmx_number_stats_where_class_batch", "fmx_number_stats_by_batch", "fmx_number_stats_by_class_batch", "fmx_number_stats_by_histogram_batch", "fmx_number_stats_by_histogram_class_batch", "fmx_field_values_histogram_where_batch", "fmx_field_values_histogram_where_class_batch", "fmx_distinct_values_histogram_where_batch", "fmx_distinct_values_histogram_where_class_batch", "fmx_match_query_number_batch", "fmx_match_query_number_class_batch", "fmx_top_lines_where_batch", "fmx_top_lines_where_class_batch", "fmx_line_bounds_batch", "fmx_extract_packed_batch", "fmx_line_text_batch", "fmx_extract_packed_last_redo", "fmx_extract_batch", "fmx_extract_boundary_batch",
-    "fmx_count_batch_dev", "fmx_count_plan_dev", "fmx_count_ordered_dev", "fmx_count_batch_is_planned", "fmx_batch_policy", "fmx_locate_batch_dev", "fmx_locate_all_ranges_dev", "fmx_locate_all_fill_dev", "fmx_line_table_build", "fmx_line_table_info", "fmx_line_bounds_batch_dev", "fmx_lines_of_hits_scratch_bytes", "fmx_lines_of_hits_dev", "fmx_hit_lines_geometry", "fmx_query_lines_scratch_bytes", "fmx_query_lines_of_hits_dev", "fmx_sequence_lines_scratch_bytes", "fmx_sequence_lines_of_hits_dev", "fmx_values_of_hits_scratch_bytes", "fmx_values_of_hits_dev", "fmx_values_fill_dev", "fmx_hits_in_lines_scratch_bytes", "fmx_hits_in_lines_dev", "fmx_lines_histogram_scratch_bytes", "fmx_hits_histogram_scratch_bytes", "fmx_lines_histogram_dev", "fmx_hits_histogram_dev", "fmx_numbers_of_hits_scratch_bytes", "fmx_numbers_of_hits_dev", "fmx_first_hits_of_lines_scratch_bytes", "fmx_first_hits_of_lines_dev", "fmx_values_of_hits_groups_scratch_bytes", "fmx_values_of_hits_groups_dev", "fmx_numbers_by_key_scratch_bytes", "fmx_numbers_by_key_dev", "fmx_numbers_by_key_buckets_scratch_bytes", "fmx_numbers_by_key_buckets_dev", "fmx_values_top_histogram_scratch_bytes", "fmx_values_top_histogram_dev", "fmx_values_gather_rows_scratch_bytes", "fmx_values_gather_rows_dev", "fmx_values_distinct_histogram_scratch_bytes", "fmx_values_distinct_histogram_dev", "fmx_hits_in_number_range_scratch_bytes", "fmx_hits_in_number_range_dev", "fmx_top_lines_of_hits_scratch_bytes", "fmx_top_lines_of_hits_dev", "fmx_class_ranges_scratch_bytes", "fmx_class_ranges_count_dev", "fmx_class_ranges_fill_dev", "fmx_class_hit_offsets_scratch_bytes", "fmx_class_hit_offsets_dev", "fmx_class_fold_status_dev", "fmx_extract_packed_scratch_bytes", "fmx_extract_packed_offsets_dev", "fmx_extract_packed_fill_dev", "fmx_extract_batch_dev", "fmx_extract_boundary_batch_dev",
+    "fmx_count_batch", "fmx_locate_batch", "fmx_locate_all_batch", "fmx_match_lines_batch", "fmx_match_query_batch", "fmx_count_class_batch", "fmx_locate_all_class_batch", "fmx_match_query_class_batch", "fmx_match_sequence_batch", "fmx_match_sequence_class_batch", "fmx_field_values_batch", "fmx_field_values_class_batch", "fmx_field_values_where_batch", "fmx_field_values_where_class_batch", "fmx_line_histogram_batch", "fmx_line_histogram_class_batch", "fmx_hit_histogram_where_batch", "fmx_hit_histogram_where_class_batch", "fmx_number_stats_where_batch", "fmx_number_stats_where_class_batch", "fmx_number_stats_by_batch", "fmx_number_stats_by_class_batch", "fmx_number_stats_by_pair_batch", "fmx_number_stats_by_pair_class_batch", "fmx_number_stats_by_histogram_batch", "fmx_number_stats_by_histogram_class_batch", "fmx_field_values_histogram_where_batch", "fmx_field_values_histogram_where_class_batch", "fmx_distinct_values_histogram_where_batch", "fmx_distinct_values_histogram_where_class_batch", "fmx_match_query_number_batch", "fmx_match_query_number_class_batch", "fmx_top_lines_where_batch", "fmx_top_lines_where_class_batch", "fmx_line_bounds_batch", "fmx_extract_packed_batch", "fmx_line_text_batch", "fmx_extract_packed_last_redo", "fmx_extract_batch", "fmx_extract_boundary_batch",
+    "fmx_count_batch_dev", "fmx_count_plan_dev", "fmx_count_ordered_dev", "fmx_count_batch_is_planned", "fmx_batch_policy", "fmx_locate_batch_dev", "fmx_locate_all_ranges_dev", "fmx_locate_all_fill_dev", "fmx_line_table_build", "fmx_line_table_info", "fmx_line_bounds_batch_dev", "fmx_lines_of_hits_scratch_bytes", "fmx_lines_of_hits_dev", "fmx_hit_lines_geometry", "fmx_query_lines_scratch_bytes", "fmx_query_lines_of_hits_dev", "fmx_sequence_lines_scratch_bytes", "fmx_sequence_lines_of_hits_dev", "fmx_values_of_hits_scratch_bytes", "fmx_values_of_hits_dev", "fmx_values_fill_dev", "fmx_hits_in_lines_scratch_bytes", "fmx_hits_in_lines_dev", "fmx_lines_histogram_scratch_bytes", "fmx_hits_histogram_scratch_bytes", "fmx_lines_histogram_dev", "fmx_hits_histogram_dev", "fmx_numbers_of_hits_scratch_bytes", "fmx_numbers_of_hits_dev", "fmx_first_hits_of_lines_scratch_bytes", "fmx_first_hits_of_lines_dev", "fmx_values_of_hits_groups_scratch_bytes", "fmx_values_of_hits_groups_dev", "fmx_numbers_by_key_scratch_bytes", "fmx_numbers_by_key_dev", "fmx_pairs_of_first_hits_scratch_bytes", "fmx_pairs_of_first_hits_dev", "fmx_numbers_by_key_buckets_scratch_bytes", "fmx_numbers_by_key_buckets_dev", "fmx_values_top_histogram_scratch_bytes", "fmx_values_top_histogram_dev", "fmx_values_gather_rows_scratch_bytes", "fmx_values_gather_rows_dev", "fmx_values_distinct_histogram_scratch_bytes", "fmx_values_distinct_histogram_dev", "fmx_hits_in_number_range_scratch_bytes", "fmx_hits_in_number_range_dev", "fmx_top_lines_of_hits_scratch_bytes", "fmx_top_lines_of_hits_dev", "fmx_class_ranges_scratch_bytes", "fmx_class_ranges_count_dev", "fmx_class_ranges_fill_dev", "fmx_class_hit_offsets_scratch_bytes", "fmx_class_hit_offsets_dev", "fmx_class_fold_status_dev", "fmx_extract_packed_scratch_bytes", "fmx_extract_packed_offsets_dev", "fmx_extract_packed_fill_dev", "fmx_extract_batch_dev", "fmx_extract_boundary_batch_dev",
     "fmx_locate_extract_batch", "fmx_locate_lines_batch", "fmx_locate_extract_batch_dev", "fmx_locate_lines_batch_dev",
     "fmx_count_segments", "fmx_locate_segments", "fmx_count_segments_dev", "fmx_locate_segments_dev", "fmx_count_locate_segments_dev",
     "fmx_count_locate_segments", "fmx_resident_bytes",
@@ -155,6 +155,14 @@ def _load():
                                             vp, P(vp), P(vp), P(vp), vp] + [P(vp)] * 6 + [vp] * 10
     L.fmx_number_stats_by_class_batch.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32,
                                                   i32, vp, i32, i32, i32, vp, i32, vp, P(vp), P(vp), P(vp), vp] + [P(vp)] * 6 + [vp] * 10
+    L.fmx_pairs_of_first_hits_scratch_bytes.restype = C.c_size_t
+    L.fmx_pairs_of_first_hits_scratch_bytes.argtypes = [i32, i32, C.c_int64]
+    L.fmx_pairs_of_first_hits_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, C.c_int64] + [vp] * 8 + [C.c_size_t, vp]
+    L.fmx_number_stats_by_pair_batch.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, vp, i32, i32,
+                                                 i32, vp, i32, vp, P(vp), P(vp), P(vp), vp, P(vp), P(vp), P(vp), vp] + [P(vp)] * 6 + [vp] * 10
+    L.fmx_number_stats_by_pair_class_batch.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp,
+                                                       i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, P(vp), P(vp), P(vp), vp, P(vp), P(vp),
+                                                       P(vp), vp] + [P(vp)] * 6 + [vp] * 10
     L.fmx_numbers_by_key_buckets_scratch_bytes.restype = C.c_size_t
     L.fmx_numbers_by_key_buckets_scratch_bytes.argtypes = [i32, i32, C.c_int64, C.c_int64, i32, i32]
     L.fmx_numbers_by_key_buckets_dev.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, C.c_int64, vp, vp, vp, vp, i32, vp, i32] + [vp] * 15 + [

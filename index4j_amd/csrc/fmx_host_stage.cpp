@@ -251,6 +251,11 @@ bool keyed_call_fill(const KeyedCall &c, int32_t line_lo, int32_t line_hi, Keyed
         zero(c.term_status, (size_t)c.n_terms);
         return false;
     }
+    keyed_args_fill(c, line_lo, line_hi, a);
+    return true;
+}
+
+void keyed_args_fill(const KeyedCall &c, int32_t line_lo, int32_t line_hi, KeyedArgs *a) {
     const int32_t all = c.m + c.n;
     a->m = c.m;
     a->n = c.n;
@@ -270,7 +275,6 @@ bool keyed_call_fill(const KeyedCall &c, int32_t line_lo, int32_t line_hi, Keyed
     a->no_key.assign((size_t)c.n, 0);
     a->not_number.assign((size_t)c.n, 0);
     a->overflow.assign((size_t)c.n, 0);
-    return true;
 }
 
 template <class T>

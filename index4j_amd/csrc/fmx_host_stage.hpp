@@ -275,6 +275,8 @@ struct KeyedArgs {
 int keyed_call_checks(const KeyedCall &c);
 int keyed_call_views(const ::fmx_index *idx, TextView *text);
 bool keyed_call_fill(const KeyedCall &c, int32_t line_lo, int32_t line_hi, KeyedArgs *a);
+// the fill alone, for a form whose n == 0 is a call of its own (the pairs and their lines of fmx_number_stats_by_pair_batch)
+void keyed_args_fill(const KeyedCall &c, int32_t line_lo, int32_t line_hi, KeyedArgs *a);
 // the call over the merged batch terms | keys | numbers with `stage` (its argument: arg), then the per-pattern outputs of c
 int keyed_call_run(const ::fmx_index *idx, const KeyedCall &c, const ValuesBatch &batch, ValuesBetweenFn stage, void *arg, const KeyedArgs &a);
 // the host side of the statistics for stat_rows_down: count .. pct are regions first .. first + 5 of a.result, the counters a's

@@ -239,6 +239,20 @@ int launch_numbers_by_key_rows(int n_cu, int32_t n, const int32_t *by_of, int32_
                                int64_t *min, int64_t *max, int64_t *pct, int32_t *no_key, int32_t *not_number, int32_t *overflow,
                                int32_t *status, void *ws, size_t ws_bytes, void *stream);
 
+// fmx_hit_pairs.hip — "STATS ... BY TWO KEYS" (fmx_pairs_of_first_hits_dev; fmx_hit_pairs.hpp has the definition): stage a's and b's
+// answers joined through the line.  Compiled once; the grids are hit_lines_geometry's over n_slots; the launcher returns a
+// hipError_t as int, `stream` is a hipStream_t, nothing is synchronised or allocated.  val_off (m + 1), pair_a and pair_b (c, each in
+// [0, m)) are HOST arrays, judged again (fm_pair_args_bad) and copied into the workspace before the launcher returns.  n_slots: at
+// least the first hits of the a-sides, pair after pair.  pair_off and joined_off get c + 1 entries; pair_group_a, pair_group_b and
+// pair_lines pair_off[c] entries, joined_lines and joined_group joined_off[c], nothing behind them (each has room for n_slots).
+// hipErrorInvalidValue before anything is launched or written: too small a workspace, a shape outside the scratch-size function's
+// (which is 0 then: m, c or n_slots <= 0, n_slots beyond 2^31 - 1), a key of more than 64 bits.
+size_t pairs_of_first_hits_scratch_bytes(int32_t m, int32_t n_pairs, int64_t n_slots);
+int launch_pairs_of_first_hits(int n_cu, int32_t m, const int64_t *val_off, int32_t c, const int32_t *pair_a, const int32_t *pair_b,
+                               const int64_t *first_off, const int32_t *first_lines, const int32_t *group_of_first, int64_t n_slots,
+                               int64_t *pair_off, int32_t *pair_group_a, int32_t *pair_group_b, int32_t *pair_lines, int64_t *joined_off,
+                               int32_t *joined_lines, int32_t *joined_group, void *ws, size_t ws_bytes, void *stream);
+
 // fmx_value_hist.hip — THE TOP VALUES OF A FIELD PER BUCKET OF LINES (fmx_values_top_histogram_dev, fmx_values_gather_rows_dev;
 // fmx_value_hist.hpp has the definition).  Compiled once; the grids are hit_lines_geometry's; the launchers return a hipError_t as
 // int, `stream` is a hipStream_t, nothing is synchronised or allocated.  val_off (n + 1: the values stage's group offsets, read by the

@@ -222,6 +222,46 @@ class NumberStatsBy:
         return {grp["value"]: grp for grp in self.groups}
 
 
+def _group_strings(out, k):
+    """the values of key pattern k's groups of a keyed answer"""
+    text_off, chars = out["text_off"], out["chars"]
+    return [chars[text_off[g]:text_off[g + 1]].tobytes().decode("utf-16-le", "surrogatepass") for g in range(int(out["val_off"][k]), int(out["val_off"][k + 1]))]
+
+
+def _pair_values(out, j):
+    """[((a, b), lines)] of pair j of a number_stats_by_pair_batch answer, in pair order"""
+    a, b = _group_strings(out, int(out["pair_a"][j])), _group_strings(out, int(out["pair_b"][j]))
+    lo, hi = int(out["pair_off"][j]), int(out["pair_off"][j + 1])
+    return [((a[int(out["pair_group_a"][r])], b[int(out["pair_group_b"][r])]), int(out["pair_lines"][r])) for r in range(lo, hi)]
+
+
+class NumberStatsByPair:
+    """number pattern i of a number_stats_by_pair_batch answer, by its pair by_of[i]: groups = [dict(values=(a, b), lines, count, sum,
+    min, max, pct, mean)] — sum an exact Python int, mean a float (nan for a pair without numbers) — in pair order (the value order of
+    a, then of b), or with top=k the k pairs with the most lines, ties in pair order; the per-pattern counters as ints"""
+
+    def __init__(self, out, top=None, i=0):
+        j = int(out["by_of"][i])  # the pair number pattern i is grouped by
+        r_lo = int(out["row_off"][i])
+        self.groups = []
+        for g, (values, lines) in enumerate(_pair_values(out, j) if int(out["row_off"][i + 1]) > r_lo else []):
+            r = r_lo + g
+            c, total = int(out["count"][r]), (int(out["sum_hi"][r]) << 64) | int(out["sum_lo"][r])
+            self.groups.append(dict(values=values, lines=lines, count=c, sum=total, min=int(out["min"][r]), max=int(out["max"][r]),
+                                    pct=out["pct"][r].tolist(), mean=total / c if c else float("nan")))
+        if top is not None:  # (a stable sort: equal line counts keep the pair order)
+            self.groups = sorted(self.groups, key=lambda grp: -grp["lines"])[:max(int(top), 0)]
+        self.no_key, self.not_number, self.overflow = int(out["no_key"][i]), int(out["not_number"][i]), int(out["overflow"][i])
+        self.occurrences, self.kept = int(out["occurrences"][i]), int(out["kept"][i])
+        a, b = int(out["pair_a"][j]), int(out["pair_b"][j])
+        self.key_occurrences = (int(out["key_occurrences"][a]), int(out["key_occurrences"][b]))
+        self.key_kept = (int(out["key_kept"][a]), int(out["key_kept"][b]))
+
+    def by_values(self):
+        """{(a, b): group}"""
+        return {grp["values"]: grp for grp in self.groups}
+
+
 class NumberStatsByHistogram:
     """number pattern i of a number_stats_by_histogram_batch answer, by its key pattern by_of[i]: rows = [dict(value, lines, group, count
     (B), sum (B exact Python ints), min, max (B), pct (B, P))] — the key rows in descending order of lines, ties in value order; group
@@ -1034,6 +1074,93 @@ class FmIndex:
                     min=vmin, max=vmax, pct=pct, no_key=no_key, not_number=not_number, overflow=overflow, occurrences=occurrences, kept=kept,
                     status=status, key_occurrences=key_occurrences, key_kept=key_kept, key_status=key_status, term_status=term_status)
 
+    # ---- ... grouped by the values of two fields of the same line (fmx.h "STATISTICS BY TWO KEYS") ----
+    def number_stats_by_pair_batch(self, key_chars, key_offsets, chars, offsets, by_of, pair_a, pair_b, term_chars, term_offsets, query_off, term_kind,
+                                   key_where_of, where_of, stop, max_len, lines=None, permille=(500, 950), frac_digits=0):
+        """number_stats_by_batch grouped by PAIRS of key patterns (fmx_number_stats_by_pair_batch; stats p95(latency_ms=) by host=,
+        status=): pair j is (pair_a[j], pair_b[j]), two key patterns of the call (they may be equal), and by_of[i] names the pair
+        number pattern i is grouped by.  A line has a pair key where it has a key of both patterns; the pairs of j are the distinct
+        (group of a, group of b) of its lines, ascending by a's value, then b's.  With no number pattern at all the call answers the
+        pairs and their lines (count by a, b).  Returns number_stats_by_batch's dict — val_off, lines, text_off, chars are the single
+        keys' groups, the rows run over the pairs of by_of[i] — and pair_a, pair_b, pair_off (c + 1), pair_group_a, pair_group_b,
+        pair_lines (one entry per pair: the two groups' indexes among their key patterns' groups, the lines that have the pair)."""
+        key_chars = np.ascontiguousarray(key_chars, dtype=np.uint16)
+        key_offsets = np.ascontiguousarray(key_offsets, dtype=np.int32)
+        chars = np.ascontiguousarray(chars, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        term_chars = np.ascontiguousarray(term_chars, dtype=np.uint16)
+        term_offsets = np.ascontiguousarray(term_offsets, dtype=np.int32)
+        by_of, pair_a, pair_b = (np.ascontiguousarray(x, dtype=np.int32).reshape(-1) for x in (by_of, pair_a, pair_b))
+        m, n, n_terms = len(key_offsets) - 1, len(offsets) - 1, len(term_offsets) - 1
+        head = (key_chars.ctypes.data, key_offsets.ctypes.data, m, chars.ctypes.data, offsets.ctypes.data, n, by_of.ctypes.data, len(pair_a),
+                pair_a.ctypes.data, pair_b.ctypes.data, term_chars.ctypes.data, term_offsets.ctypes.data, n_terms)
+        return self._number_stats_by_pair_call(lib.fmx_number_stats_by_pair_batch, "fmx_number_stats_by_pair_batch", head, m, n, n_terms, by_of, pair_a,
+                                               pair_b, query_off, term_kind, key_where_of, where_of, stop, max_len, lines, permille, frac_digits)
+
+    def number_stats_by_pair_class_batch(self, key_alt, key_pos_off, key_pat_off, alt, pos_off, pat_off, by_of, pair_a, pair_b, term_alt, term_pos_off,
+                                         term_pat_off, query_off, term_kind, key_where_of, where_of, stop, max_len, lines=None, permille=(500, 950),
+                                         frac_digits=0, max_ranges=CLASS_RANGES_DEFAULT):
+        """number_stats_by_pair_batch with class patterns as key patterns, as number patterns and as terms
+        (fmx_number_stats_by_pair_class_batch); same returns"""
+        key_alt, key_pos_off, key_pat_off, key_n_pos, m = self._class_arrays(key_alt, key_pos_off, key_pat_off)
+        alt, pos_off, pat_off, n_pos, n = self._class_arrays(alt, pos_off, pat_off)
+        term_alt, term_pos_off, term_pat_off, term_n_pos, n_terms = self._class_arrays(term_alt, term_pos_off, term_pat_off)
+        by_of, pair_a, pair_b = (np.ascontiguousarray(x, dtype=np.int32).reshape(-1) for x in (by_of, pair_a, pair_b))
+        head = (key_alt.ctypes.data, key_pos_off.ctypes.data, key_n_pos, key_pat_off.ctypes.data, m, alt.ctypes.data, pos_off.ctypes.data, n_pos,
+                pat_off.ctypes.data, n, by_of.ctypes.data, len(pair_a), pair_a.ctypes.data, pair_b.ctypes.data, term_alt.ctypes.data,
+                term_pos_off.ctypes.data, term_n_pos, term_pat_off.ctypes.data, n_terms, int(max_ranges))
+        return self._number_stats_by_pair_call(lib.fmx_number_stats_by_pair_class_batch, "fmx_number_stats_by_pair_class_batch", head, m, n, n_terms, by_of,
+                                               pair_a, pair_b, query_off, term_kind, key_where_of, where_of, stop, max_len, lines, permille, frac_digits)
+
+    def _number_stats_by_pair_call(self, call, name, head, m, n, n_terms, by_of, pair_a, pair_b, query_off, term_kind, key_where_of, where_of, stop,
+                                   max_len, lines, permille, frac_digits):
+        if len(by_of) != n:
+            raise ValueError("by_of has %d entries for %d patterns" % (len(by_of), n))
+        if len(pair_a) != len(pair_b):
+            raise ValueError("pair_a has %d entries and pair_b %d" % (len(pair_a), len(pair_b)))
+        c = len(pair_a)
+        query_off, term_kind, where_of, q, lo, hi = self._where_arrays(n, n_terms, query_off, term_kind, where_of, lines)
+        key_where_of = np.ascontiguousarray(key_where_of, dtype=np.int32)
+        if len(key_where_of) != m:
+            raise ValueError("key_where_of has %d entries for %d key patterns" % (len(key_where_of), m))
+        stop = as_chars(stop)
+        permille = np.ascontiguousarray(permille, dtype=np.int32).reshape(-1)
+        P = len(permille)
+        val_off, pair_off, row_off = np.zeros(m + 1, dtype=np.int64), np.zeros(c + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        no_key, not_number, overflow, occurrences, kept, status = (np.zeros(n, dtype=np.int32) for _ in range(6))
+        key_occurrences, key_kept, key_status = (np.zeros(m, dtype=np.int32) for _ in range(3))
+        term_status = np.zeros(n_terms, dtype=np.int32)
+        # lines (the allocation), text_off, chars, pair_group_a, pair_group_b, pair_lines, count, sum_lo, sum_hi, min, max, pct
+        ptr = [C.c_void_p() for _ in range(12)]
+        check(call(self._h, *head, query_off.ctypes.data, term_kind.ctypes.data, q, key_where_of.ctypes.data, where_of.ctypes.data, lo, hi,
+                   stop.ctypes.data, len(stop), int(max_len), int(frac_digits), permille.ctypes.data, P, val_off.ctypes.data, C.byref(ptr[0]),
+                   C.byref(ptr[1]), C.byref(ptr[2]), pair_off.ctypes.data, C.byref(ptr[3]), C.byref(ptr[4]), C.byref(ptr[5]), row_off.ctypes.data,
+                   *(C.byref(x) for x in ptr[6:]), no_key.ctypes.data, not_number.ctypes.data, overflow.ctypes.data, occurrences.ctypes.data,
+                   kept.ctypes.data, status.ctypes.data, key_occurrences.ctypes.data, key_kept.ctypes.data, key_status.ctypes.data,
+                   term_status.ctypes.data), name)
+        G, R, pairs = int(val_off[m]), int(row_off[n]), int(pair_off[c])
+
+        def take(at, ctype, dtype, count):  # (the library's buffer is copied into arrays of NumPy's own)
+            if not at or count == 0:
+                return np.zeros(count, dtype)
+            return np.ctypeslib.as_array(C.cast(at, C.POINTER(ctype)), shape=(count,)).copy()
+
+        try:
+            group_lines = take(ptr[0], C.c_int32, np.int32, G)
+            text_off = take(ptr[1], C.c_int64, np.int64, G + 1) if ptr[0] else np.zeros(1, np.int64)
+            text = take(ptr[2], C.c_uint16, np.uint16, int(text_off[G]))
+            group_a, group_b, pair_lines = (take(ptr[k], C.c_int32, np.int32, pairs) for k in (3, 4, 5))
+            count = take(ptr[6], C.c_int32, np.int32, R)
+            sum_lo, sum_hi = take(ptr[7], C.c_uint64, np.uint64, R), take(ptr[8], C.c_uint64, np.uint64, R)
+            vmin, vmax = take(ptr[9], C.c_int64, np.int64, R), take(ptr[10], C.c_int64, np.int64, R)
+            pct = take(ptr[11], C.c_int64, np.int64, R * P).reshape(R, P)
+        finally:
+            lib.fmx_free_buffer(ptr[0])
+        return dict(by_of=by_of.copy(), pair_a=pair_a.copy(), pair_b=pair_b.copy(), val_off=val_off, lines=group_lines, text_off=text_off, chars=text,
+                    pair_off=pair_off, pair_group_a=group_a, pair_group_b=group_b, pair_lines=pair_lines, row_off=row_off, count=count, sum_lo=sum_lo,
+                    sum_hi=sum_hi, min=vmin, max=vmax, pct=pct, no_key=no_key, not_number=not_number, overflow=overflow, occurrences=occurrences,
+                    kept=kept, status=status, key_occurrences=key_occurrences, key_kept=key_kept, key_status=key_status, term_status=term_status)
+
     # ---- ... by the value of a field of the same line, per bucket of lines (fmx.h "STATISTICS BY KEY PER BUCKET") ----
     def number_stats_by_histogram_batch(self, key_chars, key_offsets, chars, offsets, by_of, term_chars, term_offsets, query_off, term_kind,
                                         key_where_of, where_of, stop, max_len, edges=None, top=10, permille=(500, 950), frac_digits=0):
@@ -1657,6 +1784,56 @@ class FmIndex:
         for st in [out["status"][0], out["key_status"][0]] + out["term_status"].tolist():
             raise_for_status(st)
         return NumberStatsBy(out, top)
+
+    def _by_pair(self, pattern, by_a, by_b, stop, max_len, where, lines, permille, frac_digits, ignore_case):
+        """one call of number_stats_by_pair_batch for the pair (by_a, by_b): one number pattern, or none at all (pattern is None)"""
+        numbers = [] if pattern is None else [as_chars(pattern)]
+        keys = [as_chars(by_a), as_chars(by_b)]
+        terms, kinds = [], []
+        for kind, word in enumerate(("all", "any", "none")):
+            group = (where or {}).get(word, ())
+            for t in ([group] if isinstance(group, str) else group):  # (a lone str is one term)
+                terms.append(as_chars(t))
+                kinds.append(kind)
+        if where is not None and set(where) - {"all", "any", "none"}:
+            raise ValueError("where takes all=, any= and none=")
+        if min((len(t) for t in terms + numbers + keys), default=1) == 0:
+            raise IndexError("ArrayIndexOutOfBoundsException")
+        query_off, w = ([0, len(terms)], 0) if where is not None else ([0], -1)
+        by_of, key_where, num_where = [0] * len(numbers), [w, w], [w] * len(numbers)
+        if ignore_case:
+            out = self.number_stats_by_pair_class_batch(*pack_class_patterns([_ignore_case(k) for k in keys]),
+                                                        *pack_class_patterns([_ignore_case(p) for p in numbers]), by_of, [0], [1],
+                                                        *pack_class_patterns([_ignore_case(t) for t in terms]), query_off, np.array(kinds, np.uint8),
+                                                        key_where, num_where, stop, max_len, lines, permille, frac_digits)
+        else:
+            out = self.number_stats_by_pair_batch(*pack_patterns(keys), *pack_patterns(numbers), by_of, [0], [1], *pack_patterns(terms), query_off,
+                                                  np.array(kinds, np.uint8), key_where, num_where, stop, max_len, lines, permille, frac_digits)
+        for st in out["status"].tolist() + out["key_status"].tolist() + out["term_status"].tolist():
+            raise_for_status(st)
+        return out
+
+    def number_stats_by_pair(self, pattern, by_a, by_b, stop=" \t\r\n", max_len=32, where=None, lines=None, permille=(500, 950), frac_digits=0, top=None,
+                             ignore_case=False):
+        """statistics of the number behind `pattern` grouped by the values behind `by_a` and `by_b` on the same line: stats count,
+        p95(latency_ms=) by host=, status=.  The key of a line for each of the two is number_stats_by's; a line counts where it has
+        both.  where, lines, permille, frac_digits and ignore_case as there.  Returns a NumberStatsByPair: groups = [dict(values=(a, b),
+        lines, count, sum (a Python int, exact), min, max, pct, mean)] in pair order — ascending by a's value, then b's; with top=k
+        the k pairs with the most lines, ties in pair order, sorted on the host — and no_key (the kept hits on a line without both
+        keys), not_number, overflow, occurrences, kept, key_occurrences, key_kept.  Needs build_line_table().  Only the groups, the
+        pairs and the rows come down."""
+        return NumberStatsByPair(self._by_pair(pattern, by_a, by_b, stop, max_len, where, lines, permille, frac_digits, ignore_case), top)
+
+    def field_value_pairs(self, by_a, by_b, stop=" \t\r\n", max_len=32, where=None, lines=None, top=None, ignore_case=False):
+        """[(a, b, lines)] of the distinct pairs of values behind `by_a` and `by_b` on the same line, each with the lines that have
+        it: the pivot table count by host=, status=.  Ascending by a's value, then b's; with top=k the k pairs with the most lines,
+        ties in that order (sorted on the host).  The key of a line, where, lines and ignore_case as in number_stats_by_pair, whose
+        call without a number pattern this is.  Needs build_line_table()."""
+        out = self._by_pair(None, by_a, by_b, stop, max_len, where, lines, (), 0, ignore_case)
+        rows = [(a, b, count) for (a, b), count in _pair_values(out, 0)]
+        if top is not None:  # (a stable sort: equal line counts keep the pair order)
+            rows = sorted(rows, key=lambda r: -r[2])[:max(int(top), 0)]
+        return rows
 
     def number_stats_by_histogram(self, pattern, by, edges=None, top=10, stop=" \t\r\n", max_len=32, where=None, permille=(500, 950), frac_digits=0,
                                   ignore_case=False):
